@@ -1,6 +1,6 @@
 """CVCL contrastive train-step benchmark on MI355X (driver contract: see the task prompt / DESIGN.md section 7).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -513,10 +513,65 @@ def static_traffic_vit(cfg):
     return None, None
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def step_outputs(lit, out):
+    """What a caller of the timed path holds after its last step, copied to the host: the scalars ``training_step`` returned
+    (loss, InfoNCE loss, accuracies, entropies) as float64, and as float32 every trainable parameter after the optimizer update,
+    its gradient, and the floating-point buffers the step updates (BatchNorm running statistics).  Each tensor once, under its
+    first name (the module tree holds its encoders and tied weights under several).  -> {name: ndarray}."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        if (torch.is_tensor(v) and v.numel() == 1) or isinstance(v, (int, float)):
+            arrays[f"step.{k}"] = np.asarray(float(v.detach() if torch.is_tensor(v) else v), dtype=np.float64)
+    for k, p in lit.named_parameters():
+        if p.requires_grad:
+            arrays[f"param.{k}"] = p.detach().float().cpu().numpy()
+            if p.grad is not None:
+                arrays[f"grad.{k}"] = p.grad.detach().float().cpu().numpy()
+    for k, b in lit.named_buffers():
+        if b.is_floating_point():
+            arrays[f"buffer.{k}"] = b.detach().float().cpu().numpy()
+    return arrays
+
+
+def write_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
+    """``out_dir/<name>.npy`` for every array, at most ``budget`` bytes of files in all: when the whole set is larger, each file
+    above a common cap (the largest that fits the budget) holds a fixed sample of its array instead -- elements of the flattened
+    array at sorted positions drawn by a generator seeded from the array's name, the same positions in every run."""
+    import io
+    import zlib
+    import numpy as np
+
+    def header(shape, dtype):                      # bytes np.save writes ahead of the data
+        buf = io.BytesIO()
+        np.lib.format.write_array_header_1_0(buf, {"descr": np.lib.format.dtype_to_descr(dtype), "fortran_order": False,
+                                                   "shape": shape})
+        return buf.tell()
+    sizes = sorted(header(a.shape, a.dtype) + a.nbytes for a in arrays.values())
+    cap, left = None, budget
+    for i, s in enumerate(sizes):
+        share = left // (len(sizes) - i)
+        if s > share:
+            cap = share
+            break
+        left -= s
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if cap is not None and header(a.shape, a.dtype) + a.nbytes > cap:
+            n = (cap - header((a.size,), a.dtype)) // a.itemsize
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def measure(cfg, precision, batch_size, steps, warmup, device, world, rank, *, roofline=True, parity=True, yardstick=False,
-            seed=None):
+            seed=None, dump=False):
     """One benchmark configuration end to end: build the module, (parity check), warm up, time ``steps`` steps between
-    barriers, (instrumented passes for the roofline).  -> dict of results (rank-local; ``elapsed`` is the max over ranks)."""
+    barriers, (instrumented passes for the roofline).  -> dict of results (rank-local; ``elapsed`` is the max over ranks).
+    ``dump``: rank 0 also returns what the last timed step computed (``step_outputs``) under ``outputs``."""
     from multimodal import _hip as H
     from multimodal import parallel
     lit, ve, opt = build_model(cfg, device, precision)
@@ -635,6 +690,8 @@ def measure(cfg, precision, batch_size, steps, warmup, device, world, rank, *, r
         per_rank = [float(t.item()) for t in per_rank]
         res["ms_per_step_per_rank"] = {"min": round(min(per_rank) / steps * 1e3, 3), "max": round(max(per_rank) / steps * 1e3, 3)}
         elapsed = max(per_rank)
+    if dump and rank == 0:                          # after the clock, before the roofline / tail passes take further steps
+        res["outputs"] = step_outputs(lit, out)
     res["elapsed"] = elapsed
     res["final_loss"] = float(out["loss"].detach())
     res["value"] = world * batch_size * steps / elapsed
@@ -905,7 +962,11 @@ def main(argv=None):
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the bounded sub-records of the default C2 line (fp32 parity mode, C4, C5)")
     ap.add_argument("--precision", default=None, choices=["bf16", "32", "fp8"])
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     a = ap.parse_args(argv)
+    if a.steps is not None and a.steps < 1:
+        raise SystemExit(f"--steps {a.steps}: at least one timed step")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -950,7 +1011,9 @@ def main(argv=None):
     warmup = a.warmup if a.warmup is not None else (10 if batch_size <= 1024 else 2)
     default_line = cfg == "c2" and a.precision is None and a.batch in (None, "") and world == 1
     r = measure(cfg, precision, batch_size, steps, warmup, device, world, rank, roofline=not a.no_roofline, parity=not a.no_parity,
-                yardstick=default_line and not a.no_parity)
+                yardstick=default_line and not a.no_parity, dump=a.dump_outputs is not None)
+    if "outputs" in r:
+        write_outputs(r.pop("outputs"), a.dump_outputs)
 
     extras = {}
     if default_line and not a.no_extras:

@@ -1,4 +1,4 @@
-"""Worker for the multi-rank GPU tests (tests/test_parallel_gpu.py): started by torch.distributed.run with two (or eight) ranks that
+"""Worker for the multi-rank GPU tests (tests/test_parallel_gpu.py): started by torch.distributed.run with two (or four) ranks that
 share the box's one GPU over the gloo backend (CVCL_DIST_BACKEND=gloo; RCCL refuses two ranks on one device).
 
     dist_worker.py bench_step OUT            one C2 step at 256 pairs per rank through DataParallelEngine + OverlappedUpdate

@@ -65,7 +65,8 @@ def _worker(rank, world, port, global_negatives, out, deferred=False):
     elif deferred:
         proj.grad = proj_used.grad
     engine.reduce_gradients()
-    out.put((rank, float(loss), proj.grad.clone(), table.grad.clone(), nlt.grad.clone()))
+    # numpy arrays travel by value; a tensor would travel as a file descriptor that is gone once this process has exited
+    out.put((rank, float(loss), proj.grad.numpy().copy(), table.grad.numpy().copy(), nlt.grad.numpy().copy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -112,6 +113,7 @@ def test_world2_gradients_equal_single_process(global_negatives, deferred):
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
+    res = [(rank, loss, *map(torch.from_numpy, grads)) for rank, loss, *grads in res]
     ref_loss, g_proj, g_table, g_nlt = _single_process_reference(world, global_negatives)
     res.sort(key=lambda t: t[0])
     for rank, loss, gp, gt, gn in res:
@@ -153,7 +155,7 @@ def _centre_worker(rank, world, port, out):
     assert parallel.COLLECTIVES["broadcast"] == n0 + 1 and net.__dict__["_centre_sync_pending"] is False
     third = net._calibrated_centres(x, None, None, None, 0, key).clone()         # cached again: no further collective
     assert parallel.COLLECTIVES["broadcast"] == n0 + 1
-    out.put((rank, first, second, third))
+    out.put((rank, first.numpy(), second.numpy(), third.numpy()))                # by value (see _worker)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -170,6 +172,7 @@ def test_world2_storage_centres_sync_is_rank_synchronous():
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
+    res = [(rank, *map(torch.from_numpy, c)) for rank, *c in res]
     for rank, first, second, third in res:
         assert float(first[0, 0]) == rank + 1                    # rank-local state before the engine is attached
         assert torch.equal(second, res[0][1]) and torch.equal(third, res[0][1])      # rank 0's centres on every rank afterwards
