@@ -19,6 +19,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "multimodal-baby_amd"))
@@ -77,9 +78,11 @@ def results_filename(args, cfg):
 
 
 @torch.no_grad()
-def evaluate_trials(model, trials, eval_type, device, datamodule=None):
+def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention_maps=False):
     """trials: list of collated batch-1 items (img, label, label_len, raw_label).  Returns per trial (soft-max list, pred).
-    All trials of the list are encoded in one pass; trial t's logits are the t-th diagonal block."""
+    All trials of the list are encoded in one pass; trial t's logits are the t-th diagonal block.
+    ``attention_maps``: returns (per-trial results, Grad-CAM maps [T, 4, h, w]) -- per trial the maps of its 4 images w.r.t. its
+    label (``image``) or of its image w.r.t. its 4 labels (``text``), from the same encoder pass as the logits."""
     T = len(trials)
     if eval_type == "image":
         imgs = torch.cat([t[0].squeeze(0) for t in trials], 0).to(device)                    # [4T, ...]
@@ -99,7 +102,12 @@ def evaluate_trials(model, trials, eval_type, device, datamodule=None):
         lens = torch.cat([t[2].reshape(-1) for t in trials]).long()
     if imgs.dtype == torch.uint8 and datamodule is not None:                                 # --device_frames: base transform on the GPU
         imgs = datamodule.on_after_batch_transfer((imgs,), 1, training=False)[0]
-    logits_per_image, logits_per_text = model(imgs, labels.to(device), lens.to(device))
+    maps = None
+    if attention_maps:                                    # label t with images 4t .. 4t + 3, or image t with labels 4t .. 4t + 3
+        pairs = ("block", n_per, "text" if eval_type == "image" else "image")
+        logits_per_image, logits_per_text, maps = model.attention_maps(imgs, labels.to(device), lens.to(device), pairs=pairs)
+    else:
+        logits_per_image, logits_per_text = model(imgs, labels.to(device), lens.to(device))
     out = []
     for i in range(T):
         if eval_type == "image":
@@ -107,7 +115,24 @@ def evaluate_trials(model, trials, eval_type, device, datamodule=None):
         else:
             row = logits_per_image[i, i * n_per:(i + 1) * n_per]
         out.append((torch.softmax(row.float(), dim=-1).cpu().numpy().tolist(), int(torch.argmax(row))))
-    return out
+    return (out, maps) if attention_maps else out
+
+
+def plot_attention(path, image, cam):
+    """One overlay PNG (reference eval_shuffled.py:195-228): the frame with its Grad-CAM map blended in."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError as e:
+        raise SystemExit(f"--plot_attention needs matplotlib ({e})")
+    from multimodal.attention_maps import bicubic_resize, getAttMap, imshow, n_inv
+    att = bicubic_resize(cam[None], image.shape[1:])[0].cpu().numpy()
+    img = n_inv(image.float().cpu()).permute(1, 2, 0).clamp(0, 1).numpy()
+    fig, ax = plt.subplots()
+    imshow(ax, getAttMap(img, att))
+    plt.savefig(path, bbox_inches="tight")
+    plt.close(fig)
 
 
 def main(args):
@@ -145,10 +170,18 @@ def main(args):
     total_pred = {c: 0 for c in classes}
 
     results, pending, first = [], [], 0
+    want_maps = bool(args.attention_maps or args.plot_attention)
+    cams = []
+    if args.plot_attention:
+        os.makedirs(args.attention_maps or "results", exist_ok=True)
 
     def flush():
         nonlocal first
-        for k, (logits_list, pred) in enumerate(evaluate_trials(model, pending, args.eval_type, device, data)):
+        res = evaluate_trials(model, pending, args.eval_type, device, data, attention_maps=want_maps)
+        if want_maps:
+            res, maps = res
+            cams.append(maps.cpu())
+        for k, (logits_list, pred) in enumerate(res):
             i = first + k
             class_label = pending[k][3][0][0]
             correct = pred == 0                            # the target is always at index 0
@@ -162,6 +195,12 @@ def main(args):
                 "eval_dataset": args.eval_dataset, "stage": args.stage, "trial_idx": i,
                 "categories": [trial["target_category"]] + trial["foil_categories"],
                 "logits": logits_list, "pred": pred, "correct": bool(correct)})
+            if args.plot_attention:                        # the target (index 0): its frame and its map w.r.t. the label
+                frames = pending[k][0].squeeze(0).to(device)
+                if frames.dtype == torch.uint8:
+                    frames = data.on_after_batch_transfer((frames,), 1, training=False)[0]
+                name = f"{cfg['model']}_{class_label}_{i % 100}_attn_map.png"
+                plot_attention(os.path.join(args.attention_maps or "results", name), frames[0], maps[k, 0])
         first += len(pending)
         pending.clear()
 
@@ -175,6 +214,12 @@ def main(args):
     for classname, correct_count in correct_pred.items():
         print(f"Accuracy for class {classname:8s} is: {float(correct_count) / total_pred[classname]:.1%}")
     print(f"Total accuracy: {sum(correct_pred.values()) / sum(total_pred.values()):%}")
+
+    if args.attention_maps:
+        os.makedirs(args.attention_maps, exist_ok=True)
+        out = os.path.join(args.attention_maps, "cams.npy")
+        print(f"Saving attention maps to {out}")
+        np.save(out, torch.cat(cams, 0).numpy())
 
     if args.save_predictions:
         filename = results_filename(args, cfg)
@@ -205,6 +250,12 @@ def _parser():
                                                                   "shape and replay it (removes the host's launch lead; same results)")
     parser.add_argument("--checkpoints_root", type=str, default="checkpoints", help="where run names resolve to checkpoints")
     parser.add_argument("--n_trials", type=int, default=32, help="number of synthetic trials")
+    parser.add_argument("--attention_maps", type=str, default=None, metavar="DIR",
+                        help="write the Grad-CAM maps of every trial (layer 4, same pass as the logits) to DIR/cams.npy "
+                             "[n_trials, 4, h, w]: the trial's 4 images w.r.t. its label (image) or its image w.r.t. its 4 labels (text)")
+    parser.add_argument("--plot_attention", action="store_true",
+                        help="save one overlay PNG per trial, {model}_{class}_{i %% 100}_attn_map.png, under the --attention_maps "
+                             "directory (results/ without it); needs matplotlib")
     return parser
 
 

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define CVCL_ABI_VERSION 5
+#define CVCL_ABI_VERSION 6
 
 enum { CVCL_OK = 0, CVCL_EINVAL = -1, CVCL_ELAUNCH = -2, CVCL_EWORKSPACE = -3, CVCL_EUNSUPPORTED = -4 };
 enum { CVCL_F32 = 0, CVCL_BF16 = 1 };
@@ -595,6 +595,31 @@ int cvcl_gemm_fp8_ln_supported(int M, int N, int K);
 int cvcl_quant_rows_mx(const void* x, long x_row_stride, void* q, void* block_scales, long rows, int K, void* stream);
 int cvcl_gemm_fp8(const void* A8, const float* a_scale, int lda, const void* W8, const float* w_scale, int ldw, void* C, int ldc,
                   const float* bias, int act, const void* R, int ldr, int M, int N, int K, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Grad-CAM attention maps of the flat ResNeXt encoder (csrc/gradcam.hip).  Replace the forward + backward per image of
+ * gradCAM (multimodal/attention_maps.py:125-165) and gradCAM_with_act_and_grad (:112-122).  With f = fc(avgpool(A)) the gradient
+ * at the layer-4 map A is the same at every position, so every (image, target) map is one contraction over the map's channels:
+ *   cam[n, m, p] = relu((R - s[n, m] U[n, p]) / (max(norm[n], eps) hw)),  R = sum_c P[m, c] A[n, p, c],  U = sum_c Q[n, c] A[n, p, c]
+ * (normalised features: P = T W, Q = n^ W, s = n^ . t, norm = ||f||; below eps the s U term drops, as in cvcl_l2norm_bwd), or
+ * relu(R / hw) with Q = s = norm = NULL.  map [N, HW, C] (NHWC, the trunk's layer-4 output) f32 or bf16, P [M, C] f32,
+ * Q [N, C] f32, s [N, M] f32 (row-major over ALL M targets), norm [N] f32; C % 32 == 0, map / P / Q 16-byte aligned.
+ * Exact-fp32 MFMA in both storage modes (R and s U cancel where a target is close to the feature).  Modes:
+ *   CVCL_GRADCAM_ALL          k = 0:      cam [N, M, HW]  (every image with every target)
+ *   CVCL_GRADCAM_BLOCK_IMAGE  M = N k:    cam [N, k, HW]  (image n with targets n k .. n k + k - 1; k = 1 is the diagonal)
+ *   CVCL_GRADCAM_BLOCK_TEXT   N = M k:    cam [M, k, HW]  (target j with images j k .. j k + k - 1)
+ * Profiling class CVCL_K_HEAD.  The hook bridge's avgpool backward (d_map = d_pooled / hw) is cvcl_avgpool_bwd.             */
+enum { CVCL_GRADCAM_ALL = 0, CVCL_GRADCAM_BLOCK_IMAGE = 1, CVCL_GRADCAM_BLOCK_TEXT = 2 };
+int cvcl_gradcam_pairs(int dtype, const void* map, int N, int HW, int C, const float* P, int M, int mode, int k, const float* Q,
+                       const float* s, const float* norm, float eps, float* cam, void* stream);
+/* F.interpolate(x, (H, W), mode='bicubic', align_corners=False) (attention_maps.py:158-163): x [maps, h, w] f32 -> y [maps, H, W]
+ * f32 (16-byte aligned), torch's source coordinates, clamped taps and A = -0.75, any sizes with w <= 4096.  CVCL_K_OTHER.    */
+int cvcl_bicubic_resize(const float* x, float* y, int maps, int h, int w, int H, int W, void* stream);
+/* gradCAM_with_act_and_grad (attention_maps.py:112-122) for any layer: act, grad [N, C, HW] logical, each f32 or bf16 and each
+ * NCHW-contiguous (nhwc = 0) or channels-last (nhwc = 1) in memory -> cam [N, HW] f32 = relu(sum_c mean_p(grad[n, c]) act[n, c, p]).
+ * C <= 8192.  CVCL_K_OTHER.                                                                                                  */
+int cvcl_gradcam_act_grad(int act_dtype, const void* act, int act_nhwc, int grad_dtype, const void* grad, int grad_nhwc, float* cam,
+                          int N, int C, int HW, void* stream);
 
 #ifdef __cplusplus
 }

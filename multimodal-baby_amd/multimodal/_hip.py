@@ -17,8 +17,9 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libcvcl_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
-ABI_VERSION = 5
+ABI_VERSION = 6
 PACK_DENSE, PACK_STEM7, PACK_GCONV3 = 0, 1, 2
+GRADCAM_ALL, GRADCAM_BLOCK_IMAGE, GRADCAM_BLOCK_TEXT = 0, 1, 2      # cvcl_hip.h CVCL_GRADCAM_*
 KERNEL_CLASSES = ("gemm", "gconv3x3", "stem7x7", "bn_finalize", "bn_add_relu", "bn_relu_maxpool", "avgpool", "head",
                   "other", "attention", "layernorm", "lstm", "gemm_f32", "bn_relu_apply", "bn_bwd", "wgrad", "gemm8w", "gemm_pro")
 
@@ -187,6 +188,9 @@ SIGNATURES = {
     "cvcl_resnext50_moments_floats": (_SZ, []),
     "cvcl_resnext50_fwd_deferred_stats": (_I, [_I, _I, _I, _I, _P, C.POINTER(ConvBnParams), _I, _P, _SZ, _P, _P, _F, _P, _P, _P]),
     "cvcl_resnext50_apply_moments": (_I, [C.POINTER(ConvBnParams), _I, _P, _F, _P]),
+    "cvcl_gradcam_pairs": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _F, _P, _P]),
+    "cvcl_bicubic_resize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "cvcl_gradcam_act_grad": (_I, [_I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -1,17 +1,25 @@
-"""Forward-hook helper with the reference's ``Hook`` contract (reference multimodal/attention_maps.py:83-105).
+"""Grad-CAM attention maps and the forward-hook helper, with the reference's public names (reference
+multimodal/attention_maps.py: ``Hook`` :83-105, ``gradCAM_with_act_and_grad`` :112-122, ``gradCAM`` :125-165 and the
+plotting helpers :15-80).  The bodies are this repository's own.
 
-Only the hook used inside ``VisionEncoder.forward`` is on the hot path; the Grad-CAM plotting helpers of
-the reference file are visualisation code and out of scope.
-
-The public names are the contract callers of the reference rely on and are therefore the same: the constructor
-``Hook(module, requires_grad=True)``, use as a context manager, the attributes ``data`` / ``hook`` / ``requires_grad``
-and the read-only views ``activation`` / ``gradient``.  The body is this repository's own."""
+Device work runs on libcvcl_hip (csrc/gradcam.hip): ``gradCAM`` is the reference's one forward + backward per call (the
+backward reaches the hooked layer-4 map through the trunk's avgpool bridge, ``resnext._PooledFromMap``), and
+``gradCAM_pairs`` is the batched form for the flat ResNeXt encoder -- one trunk pass, then every requested (image, target)
+map as one exact-fp32 MFMA contraction over the layer-4 map (cvcl_hip.h, "Grad-CAM").  The plotting helpers are host-side
+numpy / matplotlib; matplotlib and scipy are imported only when a helper needs them."""
 from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
+
+from . import _hip as H
+from . import ops
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
 class Hook:
@@ -38,3 +46,243 @@ class Hook:
 
     activation = property(lambda self: self.data, doc="the captured output tensor (None before the first forward)")
     gradient = property(lambda self: self.data.grad, doc="d loss / d activation after backward (requires_grad=True)")
+
+
+# ---- device side ---------------------------------------------------------------------------------------------------------
+
+def _nhwc_flag(t: torch.Tensor) -> int:
+    """0: NCHW-contiguous, 1: channels-last storage (the trunk's layer-4 view); anything else is refused."""
+    if t.dim() != 4:
+        raise H.CvclError(f"expected an [N, C, h, w] tensor, got {tuple(t.shape)}")
+    if t.is_contiguous():
+        return 0
+    if t.permute(0, 2, 3, 1).is_contiguous():
+        return 1
+    raise H.CvclError("act / grad must be NCHW-contiguous or channels-last")
+
+
+def gradCAM_with_act_and_grad(act: torch.Tensor, grad: torch.Tensor) -> torch.Tensor:
+    """relu(sum_c mean_hw(grad)[c] act[c]) -> [N, 1, h, w] fp32 (reference :112-122) for any layer's act / grad, fp32 or bf16,
+    NCHW or channels-last."""
+    if not (act.is_cuda and grad.is_cuda):
+        raise H.CvclError("gradCAM_with_act_and_grad needs device tensors (there is no CPU fallback)")
+    if act.shape != grad.shape:
+        raise H.CvclError(f"act {tuple(act.shape)} and grad {tuple(grad.shape)} differ in shape")
+    N, C, h, w = act.shape
+    fa, fg = _nhwc_flag(act), _nhwc_flag(grad)
+    cam = torch.empty(N, 1, h, w, dtype=torch.float32, device=act.device)
+    H.check(H.lib().cvcl_gradcam_act_grad(H.cvcl_dtype(act.dtype), act.data_ptr(), fa, H.cvcl_dtype(grad.dtype), grad.data_ptr(), fg,
+                                          H.ptr(cam), N, C, h * w, H.stream_ptr()), "cvcl_gradcam_act_grad")
+    return cam
+
+
+def bicubic_resize(x: torch.Tensor, size) -> torch.Tensor:
+    """F.interpolate(x, size, mode='bicubic', align_corners=False) over the last two dimensions of an fp32 tensor."""
+    Hh, Ww = int(size[0]), int(size[1])
+    x = x.contiguous()
+    h, w = x.shape[-2:]
+    maps = x.numel() // (h * w)
+    y = torch.empty(*x.shape[:-2], Hh, Ww, dtype=torch.float32, device=x.device)
+    H.check(H.lib().cvcl_bicubic_resize(H.ptr(x, torch.float32), H.ptr(y), maps, h, w, Hh, Ww, H.stream_ptr()), "cvcl_bicubic_resize")
+    return y
+
+
+def gradCAM(model: nn.Module, input: torch.Tensor, target: torch.Tensor, layer: nn.Module, normalize_features: bool = False,
+            resize: bool = True) -> torch.Tensor:
+    """Reference :125-165: one forward + backward of ``model`` (the vision encoder's ResNeXt) with ``layer`` hooked; returns
+    [N, 1, H, W] fp32 (``resize``: bicubic to the input's size) or [N, 1, h, w].  A batch of N images with N targets gives the
+    row-wise (diagonal) pairs.  Every parameter's ``requires_grad`` is switched off for the call and restored afterwards."""
+    if input.grad is not None:
+        input.grad.zero_()
+    saved = {name: p.requires_grad for name, p in model.named_parameters()}
+    for p in model.parameters():
+        p.requires_grad_(False)
+    if not isinstance(layer, nn.Module):
+        raise TypeError("layer must be an nn.Module")
+    try:
+        with Hook(layer) as hook, torch.enable_grad():
+            output = model(input)
+            if normalize_features:
+                output = ops.l2_normalize(output)
+            output.backward(target)
+            act, grad = hook.activation, hook.gradient
+    finally:
+        for name, p in model.named_parameters():
+            p.requires_grad_(saved[name])
+    if grad is None:
+        raise H.CvclError("no gradient reached the hooked layer")
+    cam = gradCAM_with_act_and_grad(act.detach(), grad)
+    if resize:
+        cam = bicubic_resize(cam, input.shape[2:])
+    return cam
+
+
+def _resnet_of(vision_model):
+    """The flat ResNeXt behind ``vision_model`` (a VisionEncoder or its ``.model``); NotImplementedError for the encoders the
+    reference's gradCAM cannot run on either."""
+    from .resnext import ResNet, SpatialResNet
+    if getattr(vision_model, "vit_dino", False):
+        raise NotImplementedError("Grad-CAM is defined for the ResNeXt encoder only (the ViT encoder has no layer4 map)")
+    if getattr(vision_model, "embedding_type", None) == "spatial":
+        raise NotImplementedError("Grad-CAM is not defined for embedding_type spatial (no pooled fc output to differentiate)")
+    model = getattr(vision_model, "model", vision_model)
+    if isinstance(model, SpatialResNet):
+        raise NotImplementedError("Grad-CAM is not defined for embedding_type spatial (no pooled fc output to differentiate)")
+    if not isinstance(model, ResNet) or not isinstance(model.fc, nn.Linear):
+        raise NotImplementedError(f"Grad-CAM is defined for the ResNeXt encoder with a linear fc only (got {type(model).__name__})")
+    return model
+
+
+def _parse_pairs(pairs, N, M):
+    """-> (mode, k, output shape prefix)."""
+    if pairs == "all":
+        return H.GRADCAM_ALL, 0, (N, M)
+    if pairs == "diagonal":
+        if M != N:
+            raise ValueError(f"diagonal pairs need as many targets as images (N {N}, M {M})")
+        return H.GRADCAM_BLOCK_IMAGE, 1, (N,)
+    if isinstance(pairs, (tuple, list)) and len(pairs) == 3 and pairs[0] == "block" and pairs[2] in ("image", "text"):
+        k = int(pairs[1])
+        if pairs[2] == "image":
+            if k <= 0 or M != N * k:
+                raise ValueError(f"('block', {k}, 'image') pairs image n with targets n k .. n k + k - 1: needs M = N k (N {N}, M {M})")
+            return H.GRADCAM_BLOCK_IMAGE, k, (N, k)
+        if k <= 0 or N != M * k:
+            raise ValueError(f"('block', {k}, 'text') pairs target j with images j k .. j k + k - 1: needs N = M k (N {N}, M {M})")
+        return H.GRADCAM_BLOCK_TEXT, k, (M, k)
+    raise ValueError(f"pairs must be 'all', 'diagonal' or ('block', k, 'image' | 'text'), got {pairs!r}")
+
+
+def gradcam_from_features(fmap, features, fc_weight, targets, normalize_features=False, pairs="all", resize=False, eps=1e-12):
+    """Grad-CAM maps from one trunk pass's outputs: ``fmap`` the layer-4 map ([N, C, h, w] view of NHWC storage), ``features``
+    [N, E] = fc(pooled) of the same pass, ``fc_weight`` [E, C], ``targets`` [M, E].  See gradCAM_pairs for pairs / resize."""
+    for t in (fmap, features, fc_weight, targets):
+        if not t.is_cuda:
+            raise H.CvclError("Grad-CAM needs device tensors (got a CPU tensor); there is no CPU fallback")
+    N, C, h, w = fmap.shape
+    rows = fmap.permute(0, 2, 3, 1)
+    if not rows.is_contiguous():
+        raise H.CvclError("the layer-4 map must be channels-last storage (the trunk's output)")
+    f = features.detach().contiguous()
+    W = fc_weight.detach().contiguous()
+    T = targets.detach().to(torch.float32).contiguous()
+    M = T.shape[0]
+    if f.shape != (N, W.shape[0]) or T.shape[1] != W.shape[0] or W.shape[1] != C:
+        raise H.CvclError(f"shapes: map {tuple(fmap.shape)}, features {tuple(f.shape)}, fc weight {tuple(W.shape)}, targets {tuple(T.shape)}")
+    mode, k, prefix = _parse_pairs(pairs, N, M)
+    P = H.gemm(T, W, w_trans=True)                             # [M, C] = T W
+    Q = S = norm = None
+    if normalize_features:
+        y = torch.empty_like(f)
+        norm = torch.empty(N, dtype=torch.float32, device=f.device)
+        H.check(H.lib().cvcl_l2norm_fwd(H.ptr(f, torch.float32), H.ptr(y), H.ptr(norm), N, f.shape[1], eps, H.stream_ptr()), "cvcl_l2norm_fwd")
+        S = H.gemm(y, T)                                       # [N, M] = n^ . t
+        Q = H.gemm(y, W, w_trans=True)                         # [N, C] = n^ W
+    cam = torch.empty(*prefix, h, w, dtype=torch.float32, device=f.device)
+    H.check(H.lib().cvcl_gradcam_pairs(H.cvcl_dtype(fmap.dtype), rows.data_ptr(), N, h * w, C, H.ptr(P), M, mode, k, H.ptr(Q), H.ptr(S),
+                                       H.ptr(norm), eps, H.ptr(cam), H.stream_ptr()), "cvcl_gradcam_pairs")
+    if resize is not False and resize is not None:
+        if resize is True:
+            raise ValueError("resize=True needs the input images' size: pass resize=(H, W)")
+        cam = bicubic_resize(cam, resize)
+    return cam
+
+
+@torch.no_grad()
+def gradCAM_pairs(vision_model, images, targets, normalize_features=False, pairs="all", resize=False):
+    """Batched Grad-CAM of the flat ResNeXt encoder: one trunk pass over ``images`` [N, 3, H, W], then the maps of the requested
+    (image, target) pairs for ``targets`` [M, E] -- the values gradCAM(model, image, target, model.layer4, normalize_features)
+    gives pair by pair, without a backward pass.
+      pairs = "all"                    -> [N, M, h, w]
+              "diagonal" (M = N)       -> [N, h, w]      image n with target n
+              ("block", k, "image")    -> [N, k, h, w]   image n with targets n k .. n k + k - 1  (M = N k)
+              ("block", k, "text")     -> [M, k, h, w]   target j with images j k .. j k + k - 1  (N = M k)
+      resize = False | True (bicubic to H x W) | (H', W')."""
+    resnet = _resnet_of(vision_model)
+    if not (images.is_cuda and targets.is_cuda):
+        raise H.CvclError("gradCAM_pairs needs device tensors (got a CPU tensor); there is no CPU fallback")
+    with Hook(resnet.layer4, requires_grad=False) as hook:
+        features = resnet(images)
+        fmap = hook.activation
+    size = tuple(images.shape[2:]) if resize is True else resize
+    return gradcam_from_features(fmap, features, resnet.fc.weight, targets, normalize_features, pairs, size)
+
+
+# ---- host-side visualisation (numpy / matplotlib) ------------------------------------------------------------------------
+
+class _Normalize:
+    """Per-channel (x - mean) / std over the channel dimension -3 of a tensor or array (torchvision's Normalize arithmetic)."""
+
+    def __init__(self, mean, std):
+        self.mean, self.std = tuple(float(m) for m in mean), tuple(float(s) for s in std)
+
+    def __call__(self, x):
+        if torch.is_tensor(x):
+            m = torch.tensor(self.mean, dtype=x.dtype, device=x.device).view(-1, 1, 1)
+            s = torch.tensor(self.std, dtype=x.dtype, device=x.device).view(-1, 1, 1)
+        else:
+            x = np.asarray(x)
+            m = np.asarray(self.mean, dtype=x.dtype).reshape(-1, 1, 1)
+            s = np.asarray(self.std, dtype=x.dtype).reshape(-1, 1, 1)
+        return (x - m) / s
+
+
+# undoes the ImageNet normalisation of the frames (reference :15-17)
+n_inv = _Normalize([-m / s for m, s in zip(IMAGENET_MEAN, IMAGENET_STD)], [1.0 / s for s in IMAGENET_STD])
+
+
+def normalize(x: np.ndarray, vmin=None, vmax=None) -> np.ndarray:
+    """Affine map of x onto [0, 1] from [vmin, vmax] (default: x's own range); a constant array maps to 0."""
+    lo = x.min() if vmin is None else vmin
+    hi = x.max() if vmax is None else vmax
+    print(f"normalizing: [vmin, vmax] = [{lo:.6f}, {hi:.6f}] to [0, 1]")
+    span = hi - lo
+    y = x - lo
+    return y / span if span > 0 else y
+
+
+def preprocess_attn_map(attn_map, shape, interpolation="cubic", blur=False, vmin=None, vmax=None, cmap=None, **kwargs):
+    """-> (map at ``shape`` normalised to [0, 1], its RGB colouring under ``cmap`` or None).  Resizing a map of another shape
+    needs OpenCV; a map already at ``shape`` (what gradCAM(resize=True) returns) does not."""
+    attn_map = np.asarray(attn_map)
+    shape = tuple(shape)
+    if attn_map.shape != shape:
+        import cv2
+        flag = getattr(cv2, "INTER_" + interpolation.upper())
+        attn_map = cv2.resize(attn_map, (shape[1], shape[0]), interpolation=flag)
+    if blur:
+        from scipy.ndimage import gaussian_filter
+        attn_map = gaussian_filter(attn_map, 0.02 * max(shape))
+    attn_map = normalize(attn_map, vmin=vmin, vmax=vmax)
+    coloured = None
+    if cmap is not None:
+        import matplotlib
+        coloured = matplotlib.colormaps[cmap](attn_map)[..., :3]
+    return attn_map, coloured
+
+
+def getAttMap(img, attn_map, blur=True, cmap="viridis", **kwargs):
+    """Blend of ``img`` [H, W, 3] with the coloured map: weight attn^0.7 on the colour, the rest on the image."""
+    attn_map, coloured = preprocess_attn_map(attn_map, img.shape[:2], blur=blur, cmap=cmap, **kwargs)
+    weight = (attn_map ** 0.7)[..., None]
+    return (1 - weight) * img + weight * coloured
+
+
+def imshow(ax, img: np.ndarray):
+    ax.imshow(img)
+    ax.axis("off")
+
+
+def plot_image(ax, img, attn_map=None, text=None, overlying=True, alpha=0.8, cmap="Greys_r", **kwargs):
+    """Draw ``img`` on ``ax`` with the map either laid over it (``overlying``) or blended into it (getAttMap), and a caption."""
+    if overlying:
+        imshow(ax, img)
+        if attn_map is not None:
+            attn_map, _ = preprocess_attn_map(attn_map, img.shape[:2], cmap=None, **kwargs)
+            ax.imshow(attn_map, alpha=alpha, cmap=cmap)
+    else:
+        if attn_map is not None:
+            img = getAttMap(img, attn_map, cmap=cmap, **kwargs)
+        imshow(ax, img)
+    if text is not None:
+        ax.text(0, 1, text, color="black", backgroundcolor="white")

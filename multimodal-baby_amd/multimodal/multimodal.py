@@ -514,6 +514,22 @@ class MultiModalModel(nn.Module):
             ret = ret + (text_outputs,)
         return ret
 
+    def attention_maps(self, image, text, text_length, pairs="all", resize=False):
+        """Grad-CAM maps of the images w.r.t. the texts' features, from the SAME encoder pass as the logits (flat ResNeXt
+        encoder): -> (logits_per_image, logits_per_text, maps).  The targets are the text features as the logits use them
+        (L2-normalised with normalize_features), and the maps those of gradCAM(image_embed.model, image, target, layer4,
+        normalize_features) -- see attention_maps.gradCAM_pairs for ``pairs`` and ``resize``.  Evaluation use: run it under
+        torch.no_grad(); the logits are those of forward() on the same inputs."""
+        from .attention_maps import _resnet_of, gradcam_from_features
+        resnet = _resnet_of(self.image_embed)
+        features, feature_map = self.image_embed(image)
+        fi = ops.l2_normalize(features) if self.normalize_features else features          # as encode_image
+        ft, _ = self.encode_text(text, text_length)
+        logits_per_image = ops.sim_logits(fi, ft, self._temperature_on(fi.device))
+        size = tuple(image.shape[2:]) if resize is True else resize
+        maps = gradcam_from_features(feature_map, features, resnet.fc.weight, ft, self.normalize_features, pairs, size)
+        return logits_per_image, logits_per_image.t(), maps
+
     def calculate_contrastive_loss(self, x, y, y_len):
         logits_per_image, logits_per_text, image_features, image_feature_map, text_outputs = self(
             x, y, y_len, return_image_features=True, return_text_outputs=True)

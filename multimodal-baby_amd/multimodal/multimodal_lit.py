@@ -126,6 +126,10 @@ class MultiModalLitModel(LightningModule):
     def forward(self, x, y, y_len):
         return self.model(x, y, y_len)
 
+    def attention_maps(self, x, y, y_len, pairs="all", resize=False):
+        """(logits_per_image, logits_per_text, Grad-CAM maps) of one encoder pass: MultiModalModel.attention_maps."""
+        return self.model.attention_maps(x, y, y_len, pairs=pairs, resize=resize)
+
     @staticmethod
     def load_model(model_name="cvcl", checkpoint_path=None):
         """Reference :134-149 downloads ``wkvong/cvcl_s_dino_resnext50_embedding`` from the HF hub; without a

@@ -361,9 +361,32 @@ class ResNet(nn.Module):
         # also works when layer4 is a plain nn.Sequential unpickled from a torchvision-built checkpoint
         for hook in list(self.layer4._forward_hooks.values()):
             hook(self.layer4, (fmap,), fmap)
+        if fmap.requires_grad and pooled.grad_fn is None and torch.is_grad_enabled():
+            # a hook asked for the map's gradient (Grad-CAM: attention_maps.gradCAM) and the frozen trunk's pooled vector is not
+            # connected to it: route it through the avgpool's backward so the gradient reaches the map
+            pooled = _PooledFromMap.apply(pooled, fmap)
         if isinstance(self.fc, nn.Linear):
             return ops.linear_f32(pooled, self.fc.weight, self.fc.bias)
         return self.fc(pooled)                           # e.g. nn.Identity (utils.build_dino_mugs)
+
+
+class _PooledFromMap(torch.autograd.Function):
+    """The frozen trunk's adaptive avgpool as autograd sees it: forward hands back the trunk's own pooled vector unchanged, backward
+    is d_map[n, p, c] = d_pooled[n, c] / hw (cvcl_avgpool_bwd) in the map's dtype and NHWC storage, returned as the map's NCHW view."""
+
+    @staticmethod
+    def forward(ctx, pooled, fmap):
+        ctx.map_shape, ctx.map_dtype = tuple(fmap.shape), fmap.dtype
+        return pooled
+
+    @staticmethod
+    def backward(ctx, d_pooled):
+        B, C, Hh, Ww = ctx.map_shape
+        d_pooled = d_pooled.contiguous()
+        dx = torch.empty(B, Hh, Ww, C, dtype=ctx.map_dtype, device=d_pooled.device)
+        H.check(H.lib().cvcl_avgpool_bwd(H.cvcl_dtype(ctx.map_dtype), H.ptr(d_pooled, torch.float32), H.ptr(dx), B, Hh * Ww, C,
+                                         H.stream_ptr()), "cvcl_avgpool_bwd")
+        return None, dx.permute(0, 3, 1, 2)
 
 
 class _RowsToF32(torch.autograd.Function):
