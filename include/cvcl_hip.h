@@ -487,7 +487,7 @@ int cvcl_gemm_tn(int dtype, const void* A, int lda, const void* B, int ldb, long
 size_t cvcl_gemm_tn_colsum_workspace_bytes(long M, int N, int K);
 int cvcl_gemm_tn_colsum(const void* A, int lda, const void* B, int ldb, long M, int N, int K, float* C, int k_keep, float* colsum,
                         void* workspace, size_t workspace_bytes, void* stream);
-/* grouped 3x3 (pad 1, stride 1|2) weight gradient, bf16 activations: dW [C][C/groups][3][3] f32 (reference OIHW) */
+/* grouped 3x3 (pad 1, stride 1|2) weight gradient, bf16 activations: dW [C][C/groups][3][3] f32 (reference OIHW); x and dy 16-byte aligned */
 size_t cvcl_gconv3x3_wgrad_workspace_bytes(int B, int H, int W, int C, int stride);
 int cvcl_gconv3x3_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int C, int groups, int stride,
                         void* workspace, size_t workspace_bytes, void* stream);

@@ -690,11 +690,13 @@ extern "C" int cvcl_gconv3x3_wgrad(const void* x, const void* dy, float* dw, int
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const long M = (long)B * Ho * Wo;
     CVCL_CHECK_ARG(M < (1L << 31), "cvcl_gconv3x3_wgrad: B * Ho * Wo must be below 2^31");
+    // both forms read 16-byte chunks of x and dy (rows of C % 128 == 0 channels are whole chunks): as cvcl_gemm_tn, refused up front
+    CVCL_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0, "cvcl_gconv3x3_wgrad: bf16 operands x and dy need 16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
     // one pass over the operands with all nine taps (band kernel) when a band fits the LDS; $CVCL_GCONV_WGRAD_BAND=0: the tap-at-a-time form
     static const bool band_on = cvcl_lab_int("CVCL_GCONV_WGRAD_BAND", 1) != 0;
     const GwPlan gw = gw_plan(B, H, W, C, stride);
-    if (band_on && gw.ok && cg <= 32 && 32 % cg == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0) {
+    if (band_on && gw.ok && cg <= 32 && 32 % cg == 0) {
         if (workspace_bytes < gw.ws) {
             cvcl_set_error("cvcl_gconv3x3_wgrad: workspace too small");
             return CVCL_EWORKSPACE;
