@@ -148,6 +148,8 @@ def main(args):
     model = MultiModalLitModel.load_from_checkpoint(checkpoint, map_location=device)
     model.to(device)
     model.eval()
+    if args.precision != "32":                             # (32: the exact-fp32 mode a loaded model starts in)
+        model.set_precision(args.precision)
     if args.hip_graph:                                     # replay the image encoder's launches as a HIP graph per batch shape
         model.vision_encoder.enable_hip_graphs(True)
 
@@ -248,6 +250,8 @@ def _parser():
     parser.add_argument("--trial_batch", type=int, default=64, help="trials encoded per device pass (1 = the reference's loop)")
     parser.add_argument("--hip_graph", action="store_true", help="capture the eval-mode image encoder into a HIP graph per batch "
                                                                   "shape and replay it (removes the host's launch lead; same results)")
+    parser.add_argument("--precision", type=str, default="32", choices=["32", "bf16", "32-split"],
+                        help="image/text encoder arithmetic: exact fp32 (default), bf16, or fp32 storage with split-bf16 trunk products")
     parser.add_argument("--checkpoints_root", type=str, default="checkpoints", help="where run names resolve to checkpoints")
     parser.add_argument("--n_trials", type=int, default=32, help="number of synthetic trials")
     parser.add_argument("--attention_maps", type=str, default=None, metavar="DIR",

@@ -15,7 +15,19 @@
  *    dynamic-LDS attributes are cached per process on first use, for the device that is current then; a process that
  *    switches devices afterwards gets the first device's grid and statistics-row counts and unraised LDS limits there.
  *  - dtype: CVCL_F32 = fp32 storage + exact-fp32 MFMA (parity mode, the reference numerics);
- *           CVCL_BF16 = bf16 storage + bf16 MFMA with fp32 accumulation/statistics (perf mode).
+ *           CVCL_BF16 = bf16 storage + bf16 MFMA with fp32 accumulation/statistics (perf mode);
+ *           CVCL_F32X3 (ABI v7) = fp32 storage as CVCL_F32, with every trunk convolution's products formed from split-bf16 parts
+ *           (x = x0 + x1 + x2, x_i bf16, six part products on the bf16 MFMA, fp32 accumulation: ~fp32 products at a fraction of
+ *           the exact fp32 MFMA's time; csrc/gemm_split.hip for the 1x1 / downsample products, csrc/conv_split.hip for the stem
+ *           and the grouped 3x3, BatchNorm partial rows fused).  Accepted by cvcl_pack_conv_weight / cvcl_packed_weight_bytes
+ *           (the split parts: CVCL_PACK_DENSE [3][cout][cin] bf16, CVCL_PACK_STEM7 / _GCONV3 [3][cout / 32][steps][32][16] bf16),
+ *           cvcl_gemm (A / C fp32, W a packed dense weight with ldw
+ *           its row pitch inside a part; plain products + BN partial rows + row gather only, N % 128 == 0, K % 32 == 0;
+ *           cvcl_gemm_stats_rows sizes the rows), cvcl_stem_conv7x7 / cvcl_stem_conv_stats_rows, cvcl_gconv3x3 /
+ *           cvcl_gconv3x3_stats_rows, cvcl_resnext50_fwd / _fwd_deferred_stats / _workspace_bytes, cvcl_resnext50_block_fwd /
+ *           _block_workspace_bytes, and the storage-side entries the trunk calls (cvcl_col_stats, cvcl_bn_relu_maxpool,
+ *           cvcl_bn_add_relu, cvcl_bn_relu_apply, cvcl_avgpool: treated as CVCL_F32).  Every other entry that takes a dtype
+ *           returns CVCL_EINVAL for it (and for any unknown value) before it enqueues anything; size queries return 0.
  *  - image activations inside the library are NHWC ("channels last"); the API takes the
  *    reference's NCHW fp32 images (multimodal_data_module.py:98-109) and hands back the layer4
  *    map in NHWC memory, which the host exposes as a logical NCHW tensor view.
@@ -43,10 +55,10 @@
 extern "C" {
 #endif
 
-#define CVCL_ABI_VERSION 6
+#define CVCL_ABI_VERSION 7
 
 enum { CVCL_OK = 0, CVCL_EINVAL = -1, CVCL_ELAUNCH = -2, CVCL_EWORKSPACE = -3, CVCL_EUNSUPPORTED = -4 };
-enum { CVCL_F32 = 0, CVCL_BF16 = 1 };
+enum { CVCL_F32 = 0, CVCL_BF16 = 1, CVCL_F32X3 = 2 };
 enum { CVCL_ACT_NONE = 0, CVCL_ACT_RELU = 1, CVCL_ACT_GELU = 2 };
 /* BatchNorm accumulators (round 6).  A convolution hands its per-channel batch statistics on either as partial ROWS (one per
  * workgroup, reduced by cvcl_bn_finalize) or, with stats_rows == CVCL_STATS_ACCUMULATE, by atomically ADDING them to a caller-zeroed

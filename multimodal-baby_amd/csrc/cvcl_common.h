@@ -69,6 +69,35 @@ struct CvclLdsAttr {
 
 __host__ __device__ static inline int cvcl_div_up(long a, long b) { return (int)((a + b - 1) / b); }
 
+// dtype validation (ABI v7).  An entry that takes a dtype accepts CVCL_F32 and CVCL_BF16 and refuses everything else with CVCL_EINVAL
+// before it enqueues anything; the entries of the trunk forward (include/cvcl_hip.h "Conventions") accept CVCL_F32X3 as well, and the
+// storage-side ones among them (elementwise passes, statistics) treat it as CVCL_F32: the "32-split" mode stores fp32.
+static inline bool cvcl_dtype_plain(int d) { return d == CVCL_F32 || d == CVCL_BF16; }
+static inline bool cvcl_dtype_trunk(int d) { return cvcl_dtype_plain(d) || d == CVCL_F32X3; }
+static inline int cvcl_storage_dtype(int d) { return d == CVCL_F32X3 ? CVCL_F32 : d; }
+#define CVCL_CHECK_DTYPE(d, fn) CVCL_CHECK_ARG(cvcl_dtype_plain(d), "%s: dtype %d is not accepted here (CVCL_F32 / CVCL_BF16)", fn, (int)(d))
+#define CVCL_CHECK_DTYPE_TRUNK(d, fn) CVCL_CHECK_ARG(cvcl_dtype_trunk(d), "%s: unknown dtype %d", fn, (int)(d))
+
+// CVCL_F32X3 products (csrc/gemm_split.hip): split terms per product (3: hi/lo x hi/lo without lo.lo; 6: three-way split of both
+// operands) and the bf16 parts per operand that go with them.  6: the 3-term form measured ~7e-4 relative on the pooled trunk output
+// at the noise point, too close to the 1e-3 gate (DESIGN.md "32-split").  The kernels are templates on the term count; both forms
+// are compiled.
+constexpr int kSplitTerms = 6;
+constexpr int kSplitParts = kSplitTerms == 3 ? 2 : 3;
+int cvcl_gemm_split(const cvcl_gemm_args* a, void* stream);
+int cvcl_gemm_split_stats_rows(int M, int N);
+size_t cvcl_split_dense_bytes(long elems);
+int cvcl_pack_split_dense(const float* w, void* out, long elems, void* stream);
+// the stem and the grouped 3x3 in CVCL_F32X3 (csrc/conv_split.hip); stem != 0 selects the 7x7 stem layout
+size_t cvcl_split_conv_bytes(int stem, int cout);
+int cvcl_pack_split_conv(int stem, const float* w, void* out, int cout, int cg, void* stream);
+int cvcl_stem_split_stats_rows(int B, int H, int W);
+int cvcl_gconv_split_stats_rows(int B, int H, int W, int C, int stride);
+int cvcl_stem_split(const float* x, const void* w, float* y, float* stats, int stats_rows, const float* centre, int B, int H, int W,
+                    void* stream);
+int cvcl_gconv_split(const float* x, const float* a_scale, const float* a_shift, float act_floor, const void* w, float* y, float* stats,
+                     int stats_rows, const float* centre, int B, int H, int W, int C, int cg, int stride, void* stream);
+
 #ifdef __HIPCC__
 // ---- element type traits -------------------------------------------------------------------
 template <typename T> struct ElemTraits;

@@ -1366,13 +1366,15 @@ int grid_m_query(int M, int N) {
 
 extern "C" int cvcl_gemm_grid_m(int dtype, int M, int N, int has_prologue) {
     (void)has_prologue;
+    if (!cvcl_dtype_plain(dtype)) return 0;
     return dtype == CVCL_BF16 ? grid_m_query<bf16_t>(M, N) : grid_m_query<float>(M, N);
 }
 
 // exact number of BN-statistics rows cvcl_gemm will write for these arguments (a->stats / a->stats_rows need not be set:
 // the answer assumes a buffer of that many rows will be passed)
 extern "C" int cvcl_gemm_stats_rows(int dtype, const cvcl_gemm_args* a) {
-    if (!a) return 0;
+    if (!a || !cvcl_dtype_trunk(dtype)) return 0;
+    if (dtype == CVCL_F32X3) return cvcl_gemm_split_stats_rows(a->M, a->N);
     cvcl_gemm_args t = *a;
     static float dummy;
     t.stats = &dummy;
@@ -1385,6 +1387,7 @@ extern "C" int cvcl_gemm_stats_rows(int dtype, const cvcl_gemm_args* a) {
 extern "C" int cvcl_gemm_ln_supported(const cvcl_gemm_args* a) { return a && pick_gemm8w(CVCL_BF16, a) == 1; }
 
 extern "C" int cvcl_gemm(int dtype, const cvcl_gemm_args* a, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_gemm");
     CVCL_CHECK_ARG(a && a->A && a->W && (a->C || a->stats), "cvcl_gemm: null operand");
     if ((a->ln_stats || a->ln_colsum || a->row_part) && !(dtype == CVCL_BF16 && pick_gemm8w(dtype, a) == 1)) {
         cvcl_set_error("cvcl_gemm: ln_stats / row_part (LayerNorm folded into the linear) exist in the 8-wave bf16 kernel only; these "
@@ -1399,6 +1402,7 @@ extern "C" int cvcl_gemm(int dtype, const cvcl_gemm_args* a, void* stream) {
                                   (a->c_scale || (!a->R && a->act == CVCL_ACT_NONE))),
                    "cvcl_gemm: centre goes with the convolution epilogues only (16-byte aligned, no bias / activation / residual)");
     if (dtype == CVCL_F32) return launch_gemm<float>(a, (hipStream_t)stream);
+    if (dtype == CVCL_F32X3) return cvcl_gemm_split(a, stream);
     if (dtype == CVCL_BF16) return launch_gemm<bf16_t>(a, (hipStream_t)stream);
     cvcl_set_error("cvcl_gemm: unknown dtype %d", dtype);
     return CVCL_EINVAL;

@@ -438,6 +438,7 @@ int f8_num_cus() {
 
 extern "C" int cvcl_quant_rows_fp8(int src_dtype, const void* x, long x_row_stride, const float* ln_gamma, const float* ln_beta,
                                    float ln_eps, void* q, float* scale, long rows, int K, void* stream) {
+    CVCL_CHECK_DTYPE(src_dtype, "cvcl_quant_rows_fp8");
     CVCL_CHECK_ARG(x && q && scale && rows > 0 && K > 0 && K % 8 == 0 && K <= 4096 && x_row_stride % 8 == 0 &&
                        ((uintptr_t)x & 15) == 0 && ((uintptr_t)q & 7) == 0 && (!ln_gamma == !ln_beta),
                    "cvcl_quant_rows_fp8: bad args (K %d)", K);

@@ -260,8 +260,8 @@ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int cvcl_gradcam_pairs(int dtype, const void* map, int N, int HW, int C, const float* P, int M, int mode, int k,
                                   const float* Q, const float* S, const float* norm, float eps, float* cam, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_gradcam_pairs");
     CVCL_CHECK_ARG(map && P && cam, "cvcl_gradcam_pairs: null map / P / cam");
-    CVCL_CHECK_ARG(dtype == CVCL_F32 || dtype == CVCL_BF16, "cvcl_gradcam_pairs: dtype %d", dtype);
     CVCL_CHECK_ARG(N > 0 && HW > 0 && C > 0 && M > 0, "cvcl_gradcam_pairs: sizes must be positive (N %d HW %d C %d M %d)", N, HW, C, M);
     CVCL_CHECK_ARG(C % GC_K == 0, "cvcl_gradcam_pairs: C = %d is not a multiple of %d", C, GC_K);
     CVCL_CHECK_ARG((Q && S && norm) || (!Q && !S && !norm), "cvcl_gradcam_pairs: Q, s and norm go together (normalised features) or not at all");
@@ -309,6 +309,8 @@ extern "C" int cvcl_bicubic_resize(const float* x, float* y, int maps, int h, in
 
 extern "C" int cvcl_gradcam_act_grad(int act_dtype, const void* act, int act_nhwc, int grad_dtype, const void* grad, int grad_nhwc,
                                      float* cam, int N, int C, int HW, void* stream) {
+    CVCL_CHECK_DTYPE(act_dtype, "cvcl_gradcam_act_grad");
+    CVCL_CHECK_DTYPE(grad_dtype, "cvcl_gradcam_act_grad");
     CVCL_CHECK_ARG(act && grad && cam, "cvcl_gradcam_act_grad: null act / grad / cam");
     CVCL_CHECK_ARG(N > 0 && C > 0 && HW > 0, "cvcl_gradcam_act_grad: sizes must be positive (N %d C %d HW %d)", N, C, HW);
     CVCL_CHECK_ARG(C <= AG_MAXC, "cvcl_gradcam_act_grad: C = %d > %d", C, AG_MAXC);

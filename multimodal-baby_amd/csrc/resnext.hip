@@ -1215,6 +1215,8 @@ extern "C" int cvcl_col_stats_rows(long rows) {
 }
 
 extern "C" int cvcl_col_stats(int dtype, const void* x, long rows, int C, float* stats, int stats_rows, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_col_stats");
+    dtype = cvcl_storage_dtype(dtype);
     CVCL_CHECK_ARG(x && stats && rows > 0 && C > 0, "cvcl_col_stats: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     const int g = cvcl_col_stats_rows(rows);
@@ -1229,6 +1231,13 @@ extern "C" int cvcl_col_stats(int dtype, const void* x, long rows, int C, float*
 }
 
 extern "C" size_t cvcl_packed_weight_bytes(int dtype, int kind, int cout, int cin_per_group, int k) {
+    if (!cvcl_dtype_trunk(dtype)) return 0;
+    if (dtype == CVCL_F32X3) {                         // split parts: csrc/gemm_split.hip (dense), csrc/conv_split.hip (stem, grouped 3x3)
+        if (kind == CVCL_PACK_DENSE) return cvcl_split_dense_bytes((long)cout * cin_per_group * k * k);
+        if (kind == CVCL_PACK_STEM7) return cout == 64 && cin_per_group == 3 && k == 7 ? cvcl_split_conv_bytes(1, cout) : 0;
+        if (kind == CVCL_PACK_GCONV3) return k == 3 && cout % 32 == 0 ? cvcl_split_conv_bytes(0, cout) : 0;
+        return 0;
+    }
     const size_t es = dtype == CVCL_BF16 ? 2 : 4;
     if (dtype == CVCL_F32 || kind == CVCL_PACK_DENSE) return (size_t)cout * cin_per_group * k * k * es;
     if (kind == CVCL_PACK_STEM7) return (size_t)4 * 6 * 512 * 2;
@@ -1238,10 +1247,24 @@ extern "C" size_t cvcl_packed_weight_bytes(int dtype, int kind, int cout, int ci
 
 extern "C" int cvcl_pack_conv_weight(int dtype, int kind, const float* w_oihw, void* out, int cout, int cin_per_group,
                                      int k, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_pack_conv_weight");
     CVCL_CHECK_ARG(w_oihw && out && cout > 0 && cin_per_group > 0, "cvcl_pack_conv_weight: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     hipStream_t s = (hipStream_t)stream;
     const long n = (long)cout * cin_per_group * k * k;
+    if (dtype == CVCL_F32X3) {
+        if (kind == CVCL_PACK_DENSE) return cvcl_pack_split_dense(w_oihw, out, n, stream);     // [parts][cout][cin] bf16
+        if (kind == CVCL_PACK_STEM7) {
+            CVCL_CHECK_ARG(cout == 64 && cin_per_group == 3 && k == 7, "cvcl_pack_conv_weight: stem must be 64x3x7x7");
+            return cvcl_pack_split_conv(1, w_oihw, out, cout, 3, stream);
+        }
+        if (kind == CVCL_PACK_GCONV3) {
+            CVCL_CHECK_ARG(k == 3, "cvcl_pack_conv_weight: grouped conv must be 3x3");
+            return cvcl_pack_split_conv(0, w_oihw, out, cout, cin_per_group, stream);
+        }
+        cvcl_set_error("cvcl_pack_conv_weight: unknown kind %d", kind);
+        return CVCL_EINVAL;
+    }
     if (dtype == CVCL_F32) {                       // parity mode keeps the reference layout
         hipLaunchKernelGGL(cast_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s, w_oihw, (float*)out, n);
     } else if (kind == CVCL_PACK_DENSE) {
@@ -1269,12 +1292,17 @@ static int stem_grid(int B, int Hin) {
 }
 
 extern "C" int cvcl_stem_conv_stats_rows(int dtype, int B, int H, int W) {
+    if (!cvcl_dtype_trunk(dtype)) return 0;
+    if (dtype == CVCL_F32X3) return cvcl_stem_split_stats_rows(B, H, W);
     if (dtype == CVCL_BF16) return stem_grid(B, H);
     return cvcl_col_stats_rows((long)B * (H / 2) * (W / 2));
 }
 
 extern "C" int cvcl_stem_conv7x7(int dtype, const float* x_nchw, const void* w_packed, void* y_nhwc, float* stats,
                                  int stats_rows, const float* centre, int B, int H, int W, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_stem_conv7x7");
+    if (dtype == CVCL_F32X3)                           // split-bf16 products, statistics fused (csrc/conv_split.hip)
+        return cvcl_stem_split(x_nchw, w_packed, (float*)y_nhwc, stats, stats_rows, centre, B, H, W, stream);
     CVCL_CHECK_ARG(x_nchw && w_packed && (y_nhwc || (dtype == CVCL_BF16 && stats)) && B > 0 && H % 2 == 0 && W % 2 == 0,
                    "cvcl_stem_conv7x7: bad args");                 // (bf16: y_nhwc NULL = statistics only)
     hipStream_t s = (hipStream_t)stream;
@@ -1331,6 +1359,7 @@ extern "C" int cvcl_stem_pool_supported(int dtype, int H, int W) {
 
 extern "C" int cvcl_stem_pool(int dtype, const float* x_nchw, const void* w_packed, const float* scale, const float* shift,
                               const float* centre, void* y_nhwc, int B, int H, int W, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_stem_pool");
     CVCL_CHECK_ARG(x_nchw && w_packed && scale && shift && y_nhwc && B > 0, "cvcl_stem_pool: bad args");
     CVCL_CHECK_ARG(cvcl_stem_pool_supported(dtype, H, W), "cvcl_stem_pool: bf16 and a width <= %d only (got dtype %d, %d x %d)",
                    2 * (STEMP_BW - 2), dtype, H, W);
@@ -1357,6 +1386,8 @@ extern "C" int cvcl_stem_pool(int dtype, const float* x_nchw, const void* w_pack
 
 extern "C" int cvcl_bn_relu_maxpool(int dtype, const void* x, const float* scale, const float* shift, void* y, int B,
                                     int H, int W, int C, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_bn_relu_maxpool");
+    dtype = cvcl_storage_dtype(dtype);
     CVCL_CHECK_ARG(x && scale && shift && y && C % 8 == 0, "cvcl_bn_relu_maxpool: bad args");
     CvclProfScope prof(stream, CVCL_K_MAXPOOL);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
@@ -1405,6 +1436,8 @@ GconvPlan gconv_plan(int B, int H, int W, int C, int stride) {
 }  // namespace
 
 extern "C" int cvcl_gconv3x3_stats_rows(int dtype, int B, int H, int W, int C, int stride) {
+    if (!cvcl_dtype_trunk(dtype)) return 0;
+    if (dtype == CVCL_F32X3) return C % 32 == 0 ? cvcl_gconv_split_stats_rows(B, H, W, C, stride) : 0;
     if (dtype == CVCL_BF16) return gconv_plan(B, H, W, C, stride).grid_x;
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     return cvcl_col_stats_rows((long)B * Ho * Wo);
@@ -1415,6 +1448,7 @@ extern "C" int cvcl_gconv3x3_stats_rows(int dtype, int B, int H, int W, int C, i
 static int gconv3x3_impl(int dtype, const void* x, const float* a_scale, const float* a_shift, const BnSrc* src, const void* w_packed,
                          void* y, float* stats, int stats_rows, const float* centre, int B, int H, int W, int C, int groups,
                          int stride, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_gconv3x3");
     CVCL_CHECK_ARG(x && w_packed && y && (!a_scale == !a_shift), "cvcl_gconv3x3: null pointer");
     CVCL_CHECK_ARG(!src || (dtype == CVCL_BF16 && src->acc && src->gamma && src->beta && src->C == C && src->count > 0 &&
                             (const void*)src->acc != (const void*)stats),
@@ -1425,6 +1459,9 @@ static int gconv3x3_impl(int dtype, const void* x, const float* a_scale, const f
     const int cg = C / groups;
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     hipStream_t s = (hipStream_t)stream;
+    if (dtype == CVCL_F32X3)                           // split-bf16 products, statistics fused (csrc/conv_split.hip)
+        return cvcl_gconv_split((const float*)x, a_scale, a_shift, act_floor, w_packed, (float*)y, stats, stats_rows, centre, B, H, W, C,
+                                cg, stride, stream);
     if (dtype == CVCL_BF16) {
         CVCL_CHECK_ARG((cg == 4 || cg == 8 || cg == 16 || cg == 32) && C % GC_CS == 0,
                        "cvcl_gconv3x3: unsupported channels-per-group %d (C=%d)", cg, C);
@@ -1523,6 +1560,8 @@ extern "C" int cvcl_gconv3x3(int dtype, const void* x, const float* a_scale, con
 
 extern "C" int cvcl_bn_add_relu(int dtype, const void* raw, const float* scale, const float* shift, const void* idn,
                                 const float* idn_scale, const float* idn_shift, void* out, long rows, int C, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_bn_add_relu");
+    dtype = cvcl_storage_dtype(dtype);
     CVCL_CHECK_ARG(raw && scale && shift && idn && out && rows > 0 && C % 8 == 0, "cvcl_bn_add_relu: bad args");
     CvclProfScope prof(stream, CVCL_K_BN_ADD_RELU);
     CVCL_CHECK_ARG((idn_scale == nullptr) == (idn_shift == nullptr), "cvcl_bn_add_relu: idn_scale/idn_shift pair");
@@ -1548,6 +1587,8 @@ extern "C" int cvcl_bn_add_relu(int dtype, const void* raw, const float* scale, 
 
 extern "C" int cvcl_bn_relu_apply(int dtype, const void* x, const float* scale, const float* shift, void* y, long rows,
                                   int C, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_bn_relu_apply");
+    dtype = cvcl_storage_dtype(dtype);
     CVCL_CHECK_ARG(x && scale && shift && y && rows > 0, "cvcl_bn_relu_apply: bad args");
     CvclProfScope prof(stream, CVCL_K_BN_APPLY);
     const int epc = dtype == CVCL_F32 ? 4 : 8;
@@ -1569,6 +1610,8 @@ extern "C" int cvcl_bn_relu_apply(int dtype, const void* x, const float* scale, 
 }
 
 extern "C" int cvcl_avgpool(int dtype, const void* x, float* out, int B, int HW, int C, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_avgpool");
+    dtype = cvcl_storage_dtype(dtype);
     CVCL_CHECK_ARG(x && out && B > 0 && HW > 0 && C > 0, "cvcl_avgpool: bad args");
     CvclProfScope prof(stream, CVCL_K_AVGPOOL);
     if (dtype == CVCL_F32)
@@ -1593,6 +1636,7 @@ inline size_t act_elems(int B, int H, int W) {
 }  // namespace
 
 extern "C" size_t cvcl_resnext50_workspace_bytes(int dtype, int B, int H, int W) {
+    if (!cvcl_dtype_trunk(dtype)) return 0;
     const size_t es = dtype == CVCL_BF16 ? 2 : 4;
     return 5 * al256(act_elems(B, H, W) * es) + al256((size_t)kMaxStatsRows * 2 * 2048 * 4) + al256((size_t)53 * 2 * 2048 * 4) +
            al256((size_t)53 * 2048 * 4) + al256(cvcl_conv1x1_gram_workspace_bytes(256)) + al256(53 * kTrunkAccLayer * 8);
@@ -1798,6 +1842,7 @@ inline size_t block_act_bytes(int dtype, int B, int h, int w, int stage) {
 }  // namespace
 
 extern "C" size_t cvcl_resnext50_block_workspace_bytes(int dtype, int B, int h, int w, int stage) {
+    if (!cvcl_dtype_trunk(dtype)) return 0;
     return 3 * block_act_bytes(dtype, B, h, w, stage) + al256((size_t)kMaxStatsRows * 2 * 2048 * 4) + al256((size_t)4 * 4096 * 4) +
            al256(cvcl_conv1x1_gram_workspace_bytes(256)) + al256(4 * kAccLayer * 8);
 }
@@ -1805,6 +1850,7 @@ extern "C" size_t cvcl_resnext50_block_workspace_bytes(int dtype, int B, int h, 
 extern "C" int cvcl_resnext50_block_fwd(int dtype, int B, int h, int w, int stage, int first, int training, const void* x_nhwc,
                                         const cvcl_convbn_params* layers, int n_layers, void* workspace, size_t workspace_bytes,
                                         void* out_nhwc, float momentum, float eps, const float* centres, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_resnext50_block_fwd");
     CVCL_CHECK_ARG(x_nhwc && layers && workspace && out_nhwc, "cvcl_resnext50_block_fwd: null pointer");
     CVCL_CHECK_ARG(((uintptr_t)centres & 15) == 0, "cvcl_resnext50_block_fwd: centres must be 16-byte aligned");
     CVCL_CHECK_ARG(stage >= 0 && stage < 4 && n_layers == (first ? 4 : 3), "cvcl_resnext50_block_fwd: stage %d with %d layers", stage, n_layers);
@@ -1844,6 +1890,7 @@ static int resnext50_fwd_impl(int dtype, int B, int H, int W, int training, cons
                               const cvcl_convbn_params* layers, int n_layers, void* workspace, size_t workspace_bytes,
                               void* layer4_out_nhwc, float* pooled, float momentum, float eps, float* moments,
                               const float* centres, void* stream) {
+    CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_resnext50_fwd");
     CVCL_CHECK_ARG(x_nchw && layers && workspace && layer4_out_nhwc && pooled, "cvcl_resnext50_fwd: null pointer");
     CVCL_CHECK_ARG(((uintptr_t)centres & 15) == 0, "cvcl_resnext50_fwd: centres must be 16-byte aligned");
     CVCL_CHECK_ARG(n_layers == 53, "cvcl_resnext50_fwd: expected 53 conv+bn layers, got %d", n_layers);

@@ -545,6 +545,7 @@ int bn_bwd_rows(int dtype, long rows, int C) {
 
 extern "C" int cvcl_bn_apply(int dtype, const void* x, const float* scale, const float* shift, void* y, long rows, int C, int relu,
                              void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_bn_apply");
     CVCL_CHECK_ARG(x && scale && shift && y && rows > 0 && C > 0 && C % epc_of(dtype) == 0, "cvcl_bn_apply: bad args");
     const int cc = C / epc_of(dtype);
     CVCL_CHECK_ARG((cc & (cc - 1)) == 0 || 256 % cc == 0 || cc % 256 == 0, "cvcl_bn_apply: unsupported channel count %d", C);
@@ -560,12 +561,13 @@ extern "C" int cvcl_bn_apply(int dtype, const void* x, const float* scale, const
     return CVCL_OK;
 }
 
-extern "C" int cvcl_bn_bwd_partial_rows(int dtype, long rows, int C) { return bn_bwd_rows(dtype, rows, C); }
+extern "C" int cvcl_bn_bwd_partial_rows(int dtype, long rows, int C) { return cvcl_dtype_plain(dtype) ? bn_bwd_rows(dtype, rows, C) : 0; }
 
 extern "C" int cvcl_bn_bwd(int dtype, int mode, const void* x, const void* out, const void* dy, const float* scale,
                            const float* shift, const float* mean, const float* rstd, const float* gamma, float* dgamma,
                            float* dbeta, void* dx, void* g_out, long rows, int C, float* partial, int partial_rows, float* coef,
                            void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_bn_bwd");
     CVCL_CHECK_ARG(x && dy && mean && rstd && gamma && dgamma && dbeta && dx && partial && coef && rows > 0 && C > 0,
                    "cvcl_bn_bwd: null pointer");
     CVCL_CHECK_ARG(mode >= 0 && mode <= 2 && (mode != 1 || (scale && shift)) && (mode != 2 || out), "cvcl_bn_bwd: bad mode %d", mode);
@@ -619,6 +621,7 @@ extern "C" int cvcl_gconv_weight_dgrad(const float* w, float* out, int C, int ci
 }
 
 extern "C" int cvcl_transpose(int dtype, const void* in, void* out, long rows, int cols, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_transpose");
     CVCL_CHECK_ARG(in && out && rows > 0 && cols > 0, "cvcl_transpose: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     dim3 grid(cvcl_div_up(cols, 32), cvcl_div_up(rows, 32));
@@ -631,6 +634,7 @@ extern "C" int cvcl_transpose(int dtype, const void* in, void* out, long rows, i
 }
 
 extern "C" int cvcl_add(int dtype, const void* a, const void* b, void* y, long n, int relu, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_add");
     CVCL_CHECK_ARG(a && b && y && n > 0 && n % epc_of(dtype) == 0, "cvcl_add: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     if (dtype == CVCL_F32)
@@ -642,6 +646,7 @@ extern "C" int cvcl_add(int dtype, const void* a, const void* b, void* y, long n
 }
 
 extern "C" int cvcl_relu_mask(int dtype, const void* y, const void* dy, void* dx, long n, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_relu_mask");
     CVCL_CHECK_ARG(y && dy && dx && n > 0 && n % epc_of(dtype) == 0, "cvcl_relu_mask: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     if (dtype == CVCL_F32)
@@ -653,6 +658,7 @@ extern "C" int cvcl_relu_mask(int dtype, const void* y, const void* dy, void* dx
 }
 
 extern "C" int cvcl_maxpool3x3s2(int dtype, const void* x, const void* dy, void* out, int B, int H, int W, int C, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_maxpool3x3s2");
     CVCL_CHECK_ARG(x && out && B > 0 && H > 0 && W > 0 && C > 0 && C % epc_of(dtype) == 0, "cvcl_maxpool3x3s2: bad args");
     CvclProfScope prof(stream, CVCL_K_MAXPOOL);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
@@ -670,6 +676,7 @@ extern "C" int cvcl_maxpool3x3s2(int dtype, const void* x, const void* dy, void*
 
 extern "C" int cvcl_maxpool3x3s2_idx(int dtype, const void* x, const void* dy, void* out, uint8_t* idx, int B, int H, int W, int C,
                                      void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_maxpool3x3s2_idx");
     CVCL_CHECK_ARG(out && idx && (x || dy) && B > 0 && H > 0 && W > 0 && C > 0 && C % epc_of(dtype) == 0, "cvcl_maxpool3x3s2_idx: bad args");
     CvclProfScope prof(stream, CVCL_K_MAXPOOL);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
@@ -689,6 +696,7 @@ extern "C" int cvcl_maxpool3x3s2_idx(int dtype, const void* x, const void* dy, v
 }
 
 extern "C" int cvcl_avgpool_bwd(int dtype, const float* d_pooled, void* dx, int B, int HW, int C, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_avgpool_bwd");
     CVCL_CHECK_ARG(d_pooled && dx && B > 0 && HW > 0 && C > 0, "cvcl_avgpool_bwd: bad args");
     CvclProfScope prof(stream, CVCL_K_AVGPOOL);
     if (dtype == CVCL_F32) hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(grid_for((long)B * HW * C)), dim3(256), 0, (hipStream_t)stream, d_pooled, (float*)dx, B, HW, C);
@@ -698,6 +706,7 @@ extern "C" int cvcl_avgpool_bwd(int dtype, const float* d_pooled, void* dx, int 
 }
 
 extern "C" int cvcl_zero_stuff2(int dtype, const void* dy, void* z, int B, int Ho, int Wo, int C, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_zero_stuff2");
     CVCL_CHECK_ARG(dy && z && B > 0 && Ho > 0 && Wo > 0 && C > 0 && C % epc_of(dtype) == 0, "cvcl_zero_stuff2: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     const long total = (long)B * 4 * Ho * Wo * C / epc_of(dtype);
@@ -709,6 +718,7 @@ extern "C" int cvcl_zero_stuff2(int dtype, const void* dy, void* z, int B, int H
 
 extern "C" int cvcl_conv_wgrad_direct(int dtype, const void* x, const void* dy, float* dw, int B, int H, int W, int Cin, int Cout,
                                       int cin_per_group, int k, int stride, int pad, int x_is_nchw_f32, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_conv_wgrad_direct");
     CVCL_CHECK_ARG(x && dy && dw && B > 0 && k > 0 && stride > 0 && cin_per_group > 0 && Cin % cin_per_group == 0 &&
                        Cout % (Cin / cin_per_group) == 0, "cvcl_conv_wgrad_direct: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);

@@ -688,6 +688,7 @@ int grid_for(long total, int per_block = 256, int cap = 8192) {
 // ================================================================================================
 extern "C" int cvcl_im2col_patches(int dtype, const float* x_nchw, void* cols, int B, int H, int W, int patch, int Kpad,
                                    void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_im2col_patches");
     CVCL_CHECK_ARG(x_nchw && cols && B > 0 && patch > 0 && H % patch == 0 && W % patch == 0 && Kpad >= 3 * patch * patch,
                    "cvcl_im2col_patches: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
@@ -707,6 +708,7 @@ extern "C" int cvcl_im2col_patches(int dtype, const float* x_nchw, void* cols, i
 
 extern "C" int cvcl_vit_assemble_tokens(int dtype, const void* tok, const float* cls, const float* pos, void* h, int B, int T,
                                         int D, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_vit_assemble_tokens");
     CVCL_CHECK_ARG(tok && cls && pos && h && B > 0 && T > 1 && D > 0, "cvcl_vit_assemble_tokens: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     const long total = (long)B * T * D;
@@ -725,6 +727,7 @@ extern "C" int cvcl_vit_assemble_tokens(int dtype, const void* tok, const float*
 
 extern "C" int cvcl_layernorm(int dtype, const void* x, long x_row_stride, const float* gamma, const float* beta, float eps,
                               void* y, int y_is_f32, long rows, int D, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_layernorm");
     CVCL_CHECK_ARG(x && gamma && beta && y && rows > 0 && D > 0 && x_row_stride >= D, "cvcl_layernorm: bad args");
     CvclProfScope prof(stream, CVCL_K_LAYERNORM);
     dim3 grid(cvcl_div_up(rows, 4));
@@ -760,6 +763,7 @@ extern "C" int cvcl_layernorm(int dtype, const void* x, long x_row_stride, const
 }
 
 extern "C" int cvcl_row_stats(int dtype, const void* x, long x_row_stride, float* out, long rows, int D, float eps, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_row_stats");
     CVCL_CHECK_ARG(x && out && rows > 0 && D > 0, "cvcl_row_stats: bad args");
     CVCL_CHECK_ARG(dtype == CVCL_BF16 && D % 8 == 0 && D <= 1024 && x_row_stride % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 7) == 0,
                    "cvcl_row_stats: bf16 rows with D %% 8 == 0, D <= 1024, 16-byte aligned (D %d)", D);
@@ -844,6 +848,7 @@ extern "C" int cvcl_attention_train(const void* qkv, void* out, float* lse, int 
 
 extern "C" int cvcl_attention(int dtype, const void* qkv, const int64_t* key_tok, void* out, int B, int T, int heads,
                               int head_dim, float scale, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_attention");
     CVCL_CHECK_ARG(qkv && out && B > 0 && T > 0 && heads > 0 && head_dim > 0 && head_dim <= 128, "cvcl_attention: bad args");
     // [lab: CVCL_SKIP_ATTENTION_AFTER=n -- what the image encoder's attention launches cost the STEP: after n calls they are skipped
     //  (timing only: the blocks then multiply whatever the output buffer holds)]

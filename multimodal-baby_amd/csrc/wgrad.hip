@@ -338,12 +338,14 @@ int reduce_grid(long total) {
 }  // namespace
 
 extern "C" size_t cvcl_gemm_tn_workspace_bytes(int dtype, long M, int N, int K) {
+    if (!cvcl_dtype_plain(dtype)) return 0;
     const TnPlan pl = tn_plan(M, N, K, 1, false, dtype == CVCL_BF16 ? TN_T : 64);
     return tn_ws_bytes(pl, N, K, 1, false);
 }
 
 extern "C" int cvcl_gemm_tn(int dtype, const void* A, int lda, const void* B, int ldb, long M, int N, int K, float* C,
                             int k_keep, void* workspace, size_t workspace_bytes, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_gemm_tn");
     CVCL_CHECK_ARG(A && B && C && workspace && M > 0 && N > 0 && K > 0 && lda >= N && ldb >= K && k_keep > 0 && k_keep <= K,
                    "cvcl_gemm_tn: bad args");
     hipStream_t st = (hipStream_t)stream;

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, parallel, resnext, text_train
+from ._hip import CvclError
 from .attention_maps import Hook
 from .multimodal_data_module import MAX_LEN_UTTERANCE, PAD_TOKEN_ID
 from .utils import load_model
@@ -130,7 +131,7 @@ class VisionEncoder(nn.Module):
 
     def _graph_forward(self, x):
         graphs = self.__dict__.setdefault("_graphs", {})
-        key = (tuple(x.shape), str(x.device), getattr(self.model, "compute_dtype", None))
+        key = (tuple(x.shape), str(x.device), getattr(self.model, "compute_dtype", None), getattr(self.model, "trunk_arithmetic", None))
         # (the parameter LIST is cached: the module-tree walk of ~160 parameters cost more host time per call than reading their
         # pointers and versions.  It is valid while no nn.Module anywhere registered a parameter or a sub-module since it was
         # taken -- ``model.fc = nn.Linear(...)``, ``load_state_dict(assign=True)``, ``register_parameter`` all pass torch's
@@ -205,8 +206,21 @@ class VisionEncoder(nn.Module):
     def last_cnn_out_dim(self):
         return 768 if self.vit_dino else 2048
 
-    def set_compute_dtype(self, dtype):
+    def set_compute_dtype(self, dtype, trunk_arithmetic="exact"):
+        """Storage dtype of the encoder; trunk_arithmetic "split" (fp32 storage, ResNeXt only) forms the trunk's convolution
+        products from split-bf16 parts -- the "32-split" precision.  The ViT and --finetune_cnn have no split form: refused here."""
+        if trunk_arithmetic not in ("exact", "split"):
+            raise ValueError(f"trunk_arithmetic must be 'exact' or 'split', got {trunk_arithmetic!r}")
+        if trunk_arithmetic == "split":
+            if dtype != torch.float32:
+                raise CvclError("the 32-split precision stores fp32")
+            if getattr(self, "vit_dino", False):
+                raise CvclError("the 32-split precision exists for the ResNeXt encoders only, not the ViT (use 32 or bf16)")
+            if getattr(self, "finetune_cnn", False):
+                raise CvclError("--finetune_cnn is not available in the 32-split precision (use 32 or bf16)")
         self.model.compute_dtype = dtype
+        if trunk_arithmetic == "split" or hasattr(self.model, "trunk_arithmetic"):
+            self.model.trunk_arithmetic = trunk_arithmetic
 
     def _load_pretrained_cnn(self):
         if self.cnn_dino:

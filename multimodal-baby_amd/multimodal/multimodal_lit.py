@@ -83,13 +83,16 @@ class MultiModalLitModel(LightningModule):
 
     def set_precision(self, precision):
         """Trainer ``--precision``: 'bf16' / '16' -> bf16 storage + bf16 MFMA trunk; '32' -> exact-fp32 parity mode;
+        '32-split' -> fp32 storage with split-bf16 products in the ResNeXt trunk's convolutions and in the text linears
+        (~fp32 numerics; refused for the ViT and with --finetune_cnn);
         'fp8' -> bf16 storage with e4m3 weights / activations in the ViT linears (BASELINE configs[4]; the ResNeXt trunk
         has no fp8 path and runs in bf16)."""
         p = str(precision)
+        split = p == "32-split"                       # fp32 storage, split-bf16 products in the ResNeXt trunk (CVCL_F32X3)
         dt = torch.bfloat16 if p in ("bf16", "16", "bf16-mixed", "16-mixed", "fp8", "8") else torch.float32
-        self.vision_encoder.set_compute_dtype(dt)
+        self.vision_encoder.set_compute_dtype(dt, "split" if split else "exact")
         # the text transformer's fp32 linears: exact-fp32 MFMA in the parity mode, hi / lo split bf16 MFMA (~2^-16) otherwise
-        self.text_encoder.__dict__["fp32_split"] = dt == torch.bfloat16
+        self.text_encoder.__dict__["fp32_split"] = dt == torch.bfloat16 or split
         if getattr(self.vision_encoder, "vit_dino", False):
             self.vision_encoder.model.fp8_linears = p in ("fp8", "8")
 

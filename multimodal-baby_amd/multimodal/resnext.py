@@ -80,6 +80,9 @@ class ResNet(nn.Module):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         self.compute_dtype = torch.float32             # torch.bfloat16 = perf mode
+        # products of the trunk's convolutions when compute_dtype is fp32: "exact" (fp32 MFMA, the parity mode) or "split"
+        # (split-bf16 parts on the bf16 MFMA, CVCL_F32X3: the "32-split" precision; storage stays fp32)
+        self.trunk_arithmetic = "exact"
         self._pack_cache = {}
         self._ws_cache = {}
         self._pre_head_callback = None                  # parallel.OverlappedUpdate: runs between the trunk and fc
@@ -245,6 +248,8 @@ class ResNet(nn.Module):
         """conv1 .. layer4 + avgpool.  -> (pooled [B,2048] f32, layer4 map as a logical NCHW view).  With a trunk stream and
         ``defer_wait`` the result is a handle for ``self._trunk_stream.wait`` (the caller's stream has not waited yet)."""
         if torch.is_grad_enabled() and any(p.requires_grad for c, b, _ in self.conv_bn_pairs() for p in (c.weight, b.weight, b.bias)):
+            if self.trunk_dtype() == H.F32X3:
+                raise H.CvclError("--finetune_cnn is not available in the 32-split precision (use 32 or bf16)")
             from .trunk_train import trunk_train       # --finetune_cnn: differentiable twin (saves activations)
             return trunk_train(self, x)
         if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
@@ -269,9 +274,15 @@ class ResNet(nn.Module):
         self.__dict__["_ema_done"] = None
         return self.__dict__["_trunk_stream"]
 
+    def trunk_dtype(self) -> int:
+        """The library dtype the trunk forward runs in: compute_dtype's, or CVCL_F32X3 for fp32 storage with split products."""
+        if self.compute_dtype == torch.float32 and self.__dict__.get("trunk_arithmetic", "exact") == "split":
+            return H.F32X3
+        return H.cvcl_dtype(self.compute_dtype)
+
     def _trunk_launch(self, x, slot=None):
         B, _, Hh, Ww = x.shape
-        dt = H.cvcl_dtype(self.compute_dtype)
+        dt = self.trunk_dtype()
         lib = H.lib()
         with torch.no_grad():
             arr, _keep = self._packed_layers(dt, x.device)
@@ -342,6 +353,7 @@ class ResNet(nn.Module):
     def __setstate__(self, d):
         self.__dict__.update(d)
         self.__dict__.setdefault("compute_dtype", torch.float32)      # objects pickled by torchvision lack these
+        self.__dict__.setdefault("trunk_arithmetic", "exact")
         self.__dict__.setdefault("_pack_cache", {})
         self.__dict__.setdefault("_ws_cache", {})
         self.__dict__.setdefault("_pre_head_callback", None)
@@ -427,6 +439,14 @@ class SpatialResNet(nn.Sequential):
     @compute_dtype.setter
     def compute_dtype(self, dt):
         self._resnet.compute_dtype = dt
+
+    @property
+    def trunk_arithmetic(self):
+        return self._resnet.trunk_arithmetic
+
+    @trunk_arithmetic.setter
+    def trunk_arithmetic(self, a):
+        self._resnet.trunk_arithmetic = a
 
     def train(self, mode: bool = True):
         super().train(mode)
