@@ -633,6 +633,44 @@ int cvcl_bicubic_resize(const float* x, float* y, int maps, int h, int w, int H,
 int cvcl_gradcam_act_grad(int act_dtype, const void* act, int act_nhwc, int grad_dtype, const void* grad, int grad_nhwc, float* cam,
                           int N, int C, int HW, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Beam-search decoding of the LSTM language model (csrc/textgen.hip).  Replaces the reference's LanguageModel.beam_search_decode
+ * (multimodal/multimodal.py:893-960) over beam_search (multimodal/beam_search.py:232-703): per decode step the torch composition
+ * of grow_topk / grow_alive / grow_finished (:418-611) plus the host `.item()` of the stop test (:613-667) becomes one launch.
+ *
+ * cvcl_beam_step: step i (0 <= i < T, T = decode_length) for B items of K beams over a vocabulary of V, one workgroup per item.
+ *   logits [B K, V] f32 (output layer, bias included); alive / finished log-probs and scores are ping-pong pairs [B, K] f32 (step i
+ *   reads *_in, writes *_out); alive_seq, fin_seq [B, K, T + 1] int64 and fin_flags [B, K] int32 are updated in place (columns
+ *   0..i + 1); h, c [B K, Hd] f32: the rows of each new beam's parent are gathered from *_in into *_out; next_tok [B K] int64.
+ *   The step first evaluates the stop test (stop_early) for the whole batch from *_in: every item's max finished score above its
+ *   alive_lp[:, 0] / ((5 + T) / 6)^alpha.  When it holds, the step only copies *_in to *_out and atomically lowers *steps to i, so
+ *   a stopped decode stays stopped and *steps (initialised to T by the caller) is the reference's final loop index.
+ *   Otherwise: scores = (log_softmax(logits) + alive_lp) / lp, lp = ((5 + i + 1) / 6)^alpha rounded to fp32; the top 2K of the K V
+ *   scores ordered by (score desc, flat index asc) -- ties go to the lower index; then grow_alive (top K of score + flag * -1e7)
+ *   and grow_finished (top K of [finished K ; score + (1 - flag) * -1e7]), both with the same tie rule.  eos_id marks a finished
+ *   candidate.  Limits: 1 <= K <= CVCL_BEAM_MAX_K, 2K <= V, 1 <= T <= CVCL_BEAM_MAX_T, no null pointers, distinct ping-pong
+ *   buffers; anything else is CVCL_EINVAL with nothing written.  CVCL_K_HEAD.
+ * cvcl_beam_finalize: per item, finished sequences and scores if any finished flag is set, else the alive ones (:683-703), into
+ *   out_seq [B, K, T + 1] int64 and out_scores [B, K] f32.  The caller trims to *steps + 1 columns.  CVCL_K_HEAD.
+ * cvcl_lstm_cell_tok: the decode step's LSTM cell on N beam rows: gates [N, 4 Hd] = h W_hh^T, G [V, 4 Hd] = table W_ih^T + b_ih + b_hh
+ *   computed once per decode; row tok[n] of G is added and the cell (gate order i, f, g, o as nn.LSTM) updates h, c [N, Hd] in
+ *   place (the reference's inputs_to_outputs, multimodal.py:391-417).  A token outside [0, V) leaves its row unchanged.
+ *   CVCL_K_LSTM.                                                                                                                 */
+enum { CVCL_BEAM_MAX_K = 16, CVCL_BEAM_MAX_T = 128 };
+int cvcl_beam_step(const float* logits, int B, int K, int V, int T, int step, double alpha, int eos_id, const float* alive_lp_in,
+                   float* alive_lp_out, const float* fin_scores_in, float* fin_scores_out, int64_t* alive_seq, int64_t* fin_seq,
+                   int32_t* fin_flags, const float* h_in, const float* c_in, float* h_out, float* c_out, int Hd, int64_t* next_tok,
+                   int32_t* steps, void* stream);
+int cvcl_beam_finalize(int B, int K, int T, const int64_t* alive_seq, const float* alive_lp, const int64_t* fin_seq,
+                       const float* fin_scores, const int32_t* fin_flags, int64_t* out_seq, float* out_scores, void* stream);
+int cvcl_lstm_cell_tok(const float* gates, const float* G, const int64_t* tok, int V, float* h, float* c, int N, int Hd,
+                       void* stream);
+/* BPTT step t = 0 of the training LSTM started from (h0, c0) (captioning: the connector's state, reference init_hidden
+ * :671-688 feeding train_greedy): cvcl_lstm_cell_bwd at t = 0 with c_{-1} = c0 [B, Hd] f32 instead of zeros; dc leaves as the
+ * gradient wrt c0, and dh_{-1} = d_gates[t = 0] W_hh + dh_carry (the caller's GEMM) is the gradient wrt h0.  CVCL_K_LSTM.          */
+int cvcl_lstm_cell_bwd_first(const float* gates_act, const float* c_save, const float* c0, const int64_t* len, const float* dh,
+                             float* dc, float* d_gates, float* dh_carry, int B, int L, int Hd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 ABI_VERSION = 7
 PACK_DENSE, PACK_STEM7, PACK_GCONV3 = 0, 1, 2
 GRADCAM_ALL, GRADCAM_BLOCK_IMAGE, GRADCAM_BLOCK_TEXT = 0, 1, 2      # cvcl_hip.h CVCL_GRADCAM_*
+BEAM_MAX_K, BEAM_MAX_T = 16, 128                                 # cvcl_hip.h CVCL_BEAM_MAX_*
 KERNEL_CLASSES = ("gemm", "gconv3x3", "stem7x7", "bn_finalize", "bn_add_relu", "bn_relu_maxpool", "avgpool", "head",
                   "other", "attention", "layernorm", "lstm", "gemm_f32", "bn_relu_apply", "bn_bwd", "wgrad", "gemm8w", "gemm_pro")
 
@@ -191,6 +192,11 @@ SIGNATURES = {
     "cvcl_gradcam_pairs": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _F, _P, _P]),
     "cvcl_bicubic_resize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cvcl_gradcam_act_grad": (_I, [_I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P]),
+    # beam-search decoding (csrc/textgen.hip)
+    "cvcl_beam_step": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "cvcl_beam_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cvcl_lstm_cell_tok": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P]),
+    "cvcl_lstm_cell_bwd_first": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

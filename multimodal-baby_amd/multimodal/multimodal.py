@@ -19,7 +19,7 @@ import torch.nn as nn
 from . import ops, parallel, resnext, text_train
 from ._hip import CvclError
 from .attention_maps import Hook
-from .multimodal_data_module import MAX_LEN_UTTERANCE, PAD_TOKEN_ID
+from .multimodal_data_module import EOS_TOKEN_ID, MAX_LEN_UTTERANCE, PAD_TOKEN_ID, SOS_TOKEN_ID
 from .utils import load_model
 
 TEXT_ENCODER = "embedding"
@@ -293,8 +293,8 @@ class TextEncoder(nn.Module):
         self.dropout_o = self.args.get("dropout_o")
         self.pos_embed_type = self.args.get("pos_embed_type", POS_EMBED_TYPE)
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
-        if self._captioning or self._attention:
-            raise NotImplementedError("captioning / attention LM branches are outside the contrastive hot path")
+        if self._attention:
+            raise NotImplementedError("attention language models are outside the implemented path")
         self.vocab = vocab
         self.word2idx = self.vocab
         self.idx2word = {idx: word for word, idx in self.vocab.items()}
@@ -318,6 +318,9 @@ class TextEncoder(nn.Module):
                 self.register_buffer("pos_embed", pe.unsqueeze(1))
             elif self.pos_embed_type == "learned":
                 self.pos_embed = nn.Parameter(torch.zeros(MAX_LEN_UTTERANCE, 1, self.embedding_dim))
+        if self._captioning:                                                # reference :346-353
+            assert self.regressional, "only regressional text encoder supports captioning"
+            self.connector = nn.Linear(self.embedding_dim, 2 * self.lstm.num_layers * self.hidden_dim)
         self.lockdrop = LockedDropout()
         self.output_dropout = nn.Dropout(self.dropout_o)
 
@@ -335,10 +338,42 @@ class TextEncoder(nn.Module):
         parser.add_argument("--pos_embed_type", type=str, default=POS_EMBED_TYPE,
                             choices=["no_pos_embed", "sinusoidal", "learned"])
 
+    def initial_state(self, image_features):
+        """Captioning: the LSTM's (h0, c0), each [B, H], from flat image features [B, E] through the connector (reference
+        init_hidden :671-688: connector(f).reshape(B, 2, 1, H).permute(1, 2, 0, 3) -> h0 = out[:, :H], c0 = out[:, H:]).
+        The connector is an fp32 GEMM; gradients flow into it and into the image features."""
+        if image_features.dim() != 2:
+            raise NotImplementedError("captioning from spatial image features (embedding_type spatial) is outside the implemented "
+                                      "path: it needs flat image features [B, E]")
+        out = ops.linear_f32(image_features.contiguous(), self.connector.weight, self.connector.bias)
+        Hd = self.hidden_dim
+        return out[:, :Hd].contiguous(), out[:, Hd:].contiguous()
+
+    def init_hidden(self, batch_size, image_features=None):
+        """reference :671-688 -> (h0, c0), each [1, B, H]: zeros, or the connector's state of ``image_features``."""
+        if image_features is not None:
+            h0, c0 = self.initial_state(image_features)
+            return h0.unsqueeze(0), c0.unsqueeze(0)
+        d = 2 if self.text_encoder == "bilstm" else 1
+        z = torch.zeros(d * self.lstm.num_layers, batch_size, self.hidden_dim, device=self.lstm.weight_hh_l0.device)
+        return z, z.clone()
+
     def forward(self, x, x_len, image_features=None, image_feature_map=None):
         attns = None
         if self.dropout_o and self.training:
             raise NotImplementedError("output dropout > 0 is not used by any contrastive configuration")
+        if image_feature_map is not None:
+            raise NotImplementedError("attention language models are outside the implemented path")
+        if image_features is not None:                                      # captioning: image-initialised LSTM (:513-520)
+            if not self.captioning:
+                raise ValueError("image_features are only used by a captioning text encoder")
+            h0, c0 = self.initial_state(image_features)
+            if self.training or torch.is_grad_enabled():
+                ret, raw_output = text_train.lstm_text_train(self.embedding.weight, self.lstm, x, x_len, self.dropout_i,
+                                                             self.training, h0, c0)
+            else:
+                ret, raw_output = ops.lstm_text(self.embedding.weight, self.lstm, x, x_len, h0, c0)
+            return ret, raw_output, attns
         spatial = self.embedding_type == "spatial"
         if self.text_encoder == "embedding" and spatial:
             # per-word embeddings are the features (reference :499, :579-580); differentiable gather
@@ -555,7 +590,8 @@ class MultiModalModel(nn.Module):
 class LanguageModel(nn.Module):
     """Tied output layer + token-wise cross entropy (reference multimodal.py:825-890): the ``lambda_lm > 0`` branch of the
     joint loss.  The projection is an fp32 GEMM (LinearF32: its weight gradient adds into the tied embedding table), the
-    loss ``cvcl_token_ce_fwd/bwd``.  Captioning / attention decoders and beam search stay out of scope."""
+    loss ``cvcl_token_ce_fwd/bwd``.  Captioning LMs start the LSTM from the connector's state of the image features; beam-search
+    decoding runs on HIP (plain and captioning LSTM LMs).  Attention decoders stay out of scope."""
 
     def __init__(self, text_encoder, args):
         super().__init__()
@@ -571,10 +607,12 @@ class LanguageModel(nn.Module):
         parser.add_argument("--bias", type=lambda s: bool(eval(s)), default=True)
 
     def forward(self, y, y_len, outputs=None, image_features=None, image_feature_map=None):
-        if image_features is not None or image_feature_map is not None:
-            raise NotImplementedError("captioning / attention language models are outside the implemented path")
+        if image_feature_map is not None:
+            raise NotImplementedError("attention language models are outside the implemented path")
         te = self.text_encoder
-        if te.text_encoder == "embedding":
+        if image_features is not None and outputs is None:
+            _feat, outputs, _attns = te(y, y_len, image_features=image_features)
+        elif te.text_encoder == "embedding":
             # per-word embeddings, gathered differentiably (the mean-pool op marks its per-word output non-differentiable)
             B, L = y.shape
             outputs = text_train.EmbedGatherPos.apply(te.embedding.weight, None, y).view(B, L, te.embedding_dim)
@@ -591,7 +629,7 @@ class LanguageModel(nn.Module):
         te = self.text_encoder
         if te.regressional:                                  # predict token l+1 from position l (:879-883)
             if te.text_encoder != "embedding" and outputs is None:
-                _feat, outputs, _attns = te(y, y_len)
+                _feat, outputs, _attns = te(y, y_len, image_features=image_features)
             outputs_in = outputs[:, :-1].contiguous() if outputs is not None else None
             outs, logits, attns = self(y[:, :-1], y_len, outputs=outputs_in)
             labels = y[:, 1:1 + logits.size(1)].contiguous()
@@ -607,8 +645,24 @@ class LanguageModel(nn.Module):
             loss = ops.lm_loss_summaries(loss, labels.reshape(-1))[0][0]
         return loss, outputs, logits, attns, labels
 
-    def beam_search_decode(self, *a, **k):
-        raise NotImplementedError("beam search decoding (text generation evaluation) is outside the implemented path")
+    def beam_search_decode(self, batch_size, beam_width, decode_length, length_penalty_alpha, image_features=None,
+                           image_feature_map=None):
+        """reference :893-960 -> (beam_seq [B, K, steps + 1] int64, log_prob [B, K]).  Plain LSTM LMs start from zeros,
+        captioning ones from the connector's state of ``image_features`` [B, E].  One HIP launch chain per step with the stop
+        test on the device (ops.beam_search_lstm)."""
+        te = self.text_encoder
+        assert te.regressional, "only regressional text encoder supports beam search decoding"
+        if image_feature_map is not None or te.has_attention:
+            raise NotImplementedError("attention language models are outside the implemented path")
+        h0 = c0 = None
+        if image_features is not None:
+            if not te.captioning:
+                raise ValueError("image_features are only used by a captioning text encoder")
+            with torch.no_grad():
+                h0, c0 = te.initial_state(image_features.detach())
+        bias = self.output_layer.bias
+        return ops.beam_search_lstm(te.embedding.weight, te.lstm, self.output_layer.weight, bias, batch_size, beam_width,
+                                    decode_length, length_penalty_alpha, h0, c0, sos_id=SOS_TOKEN_ID, eos_id=EOS_TOKEN_ID)
 
 
 def calculate_attn_reg_loss(attns):

@@ -1,8 +1,9 @@
 """MultiModalLitModel with the reference's surface (reference multimodal/multimodal_lit.py:35-542).
 
 training_step / calculate_joint_loss / configure_optimizers / encode_* / tokenize / validation trial step for
-the contrastive objective (lambda_mm); the language-model and text-generation branches (lambda_lm,
-eval_textgen) are outside the hot path and raise.  Logging keeps the reference's metric names."""
+the contrastive objective (lambda_mm), the language-model loss (lambda_lm; plain or image-initialised captioning LSTM),
+LM-scored trials of a captioning model and beam-search text generation (eval_textgen).  Attention LMs raise.  Logging keeps
+the reference's metric names."""
 from __future__ import annotations
 
 import functools
@@ -26,6 +27,7 @@ PATIENCE = 20
 WEIGHT_DECAY = 0.01
 BEAM_WIDTH = 3
 DECODE_LENGTH = MAX_LEN_UTTERANCE
+PRINT_EVAL_TEXTGEN_EXAMPLE_IDS = range(10)
 LENGTH_PENALTY_ALPHA = 0.0
 
 
@@ -50,6 +52,9 @@ class MultiModalLitModel(LightningModule):
         self.lambda_ar = self.args.get("lambda_ar", 0.)
         self.optimize_unused = self.args.get("optimize_unused", False)
         self.eval_textgen = self.args.get("eval_textgen", False)
+        self.beam_width = self.args.get("beam_width", BEAM_WIDTH)
+        self.decode_length = self.args.get("decode_length", DECODE_LENGTH)
+        self.length_penalty_alpha = self.args.get("length_penalty_alpha", LENGTH_PENALTY_ALPHA)
         self.vision_encoder = vision_encoder
         self.text_encoder = text_encoder
         self.model = MultiModalModel(self.vision_encoder, self.text_encoder, args)
@@ -167,13 +172,22 @@ class MultiModalLitModel(LightningModule):
 
     def calculate_ce_loss(self, y, y_len, x=None, outputs=None, image_features=None, image_feature_map=None,
                           return_image_features=False, **kwargs):
-        """Wraps language_model.calculate_ce_loss (reference :192-225; captioning / attention variants out of scope)."""
+        """Wraps language_model.calculate_ce_loss (reference :192-225).  Captioning: the LSTM starts from the connector's state of
+        the image features -- those of the contrastive pass when given, else one encoder pass over ``x`` -- and the contrastive
+        pass's text outputs (from zero state) are not reused.  Attention LMs are outside the implemented path."""
         te = self.language_model.text_encoder
-        if te.captioning or te.has_attention:
-            raise NotImplementedError("captioning / attention language models are outside the implemented path")
-        ret = self.language_model.calculate_ce_loss(y, y_len, outputs=outputs, **kwargs)
+        if te.has_attention:
+            raise NotImplementedError("attention language models are outside the implemented path")
+        if te.captioning:
+            if image_features is None:
+                image_features, image_feature_map = self.model.encode_image(x)
+            outputs = None
+        else:
+            image_features, image_feature_map = None, None
+        ret = self.language_model.calculate_ce_loss(y, y_len, outputs=outputs,
+                                                    image_features=image_features if te.captioning else None, **kwargs)
         if return_image_features:
-            ret = ret + (None, None)
+            ret = ret + (image_features, image_feature_map)
         return ret
 
     def calculate_joint_loss(self, batch, stage, log, eval_textgen=False, ce_weight=None):
@@ -193,20 +207,26 @@ class MultiModalLitModel(LightningModule):
                         "text_accuracy": text_accuracy, "image_entropy": image_entropy.detach(),
                         "text_entropy": text_entropy.detach()})
             text_outputs = _rest[-1]
+            image_features = _rest[2]                                        # reused by a captioning LM (reference :240-282)
         else:
             infonce_loss = 0.
-            text_outputs = None
+            text_outputs = image_features = None
         if self.lambda_lm or not self.optimize_unused:                       # reference :266-309
-            if eval_textgen:
-                raise NotImplementedError("text generation evaluation (beam search) is outside the implemented path")
-            ce_loss, _o, _l, _attns, labels = self.calculate_ce_loss(y, y_len, x=x, outputs=text_outputs, tokenwise=True,
-                                                                      weight=ce_weight)
+            ce_loss, _o, _l, _attns, labels, image_features, _ifm = self.calculate_ce_loss(
+                y, y_len, x=x, outputs=text_outputs, image_features=image_features, return_image_features=True, tokenwise=True,
+                weight=ce_weight)
             means, counts = ops.lm_loss_summaries(ce_loss.reshape(-1), labels.reshape(-1), PAD_TOKEN_ID, SOS_TOKEN_ID, EOS_TOKEN_ID)
             lm_ce_loss = means[0]
             for i, suffix in enumerate(("", "_wo_sos", "_wo_sos_eos")):
                 log(f"{stage}_ce_loss{suffix}", means[i].detach())
                 ret[f"ce_loss{suffix}"] = means[i].detach()
                 ret[f"n_tokens{suffix}"] = counts[i]
+            if eval_textgen:                                                 # reference :325-357
+                te = self.language_model.text_encoder
+                beam_seq, _log_prob = self.language_model.beam_search_decode(
+                    ret["batch_size"], self.beam_width, self.decode_length, self.length_penalty_alpha,
+                    image_features=image_features if te.captioning else None)
+                ret.update({"raw_y": raw_y, "gen_text": [self._ids_to_sentence(s) for s in beam_seq[:, 0].tolist()]})
         else:
             lm_ce_loss = 0.
         # data-parallel, global negatives: InfoNCE is the replicated full-batch loss and per-rank gradients are SUMMED; the LM
@@ -225,6 +245,18 @@ class MultiModalLitModel(LightningModule):
         log(f"{stage}_loss", logged)
         ret.update({"loss": loss})
         return ret
+
+    def _ids_to_sentence(self, ids):
+        """reference :339-350: up to the first <pad>, without a trailing <eos> and a leading <sos>."""
+        n = 0
+        while n < len(ids) and ids[n] != PAD_TOKEN_ID:
+            n += 1
+        ids = ids[:n]
+        if ids and ids[-1] == EOS_TOKEN_ID:
+            ids = ids[:-1]
+        if ids and ids[0] == SOS_TOKEN_ID:
+            ids = ids[1:]
+        return " ".join(self.text_encoder.idx2word[i] for i in ids)
 
     def joint_loss_epoch_end(self, outputs, stage, log, eval_textgen=False):
         def mean_over_examples(name):
@@ -247,6 +279,23 @@ class MultiModalLitModel(LightningModule):
                 value_mean = mean_over_tokens(f"ce_loss{suffix}", f"n_tokens{suffix}")
                 log(f"{stage}_ce_loss{suffix}", value_mean)
                 log(f"{stage}_perplexity{suffix}", float(np.exp(value_mean)))
+            if eval_textgen:                                                 # reference :430-440
+                from .textgen_eval import evaluate as textgen_eval
+                references, hypotheses = [], []
+                for o in outputs:
+                    references += list(o["raw_y"])
+                    hypotheses += list(o["gen_text"])
+                for example_id in PRINT_EVAL_TEXTGEN_EXAMPLE_IDS:
+                    if example_id >= len(hypotheses):
+                        break
+                    print(f"example #{example_id}:")
+                    print("references:")
+                    print("\n".join(references[example_id]) if isinstance(references[example_id], (list, tuple))
+                          else references[example_id])
+                    print("hypothesis:")
+                    print(hypotheses[example_id])
+                for metric, score in textgen_eval(references, hypotheses).items():
+                    log(f"{stage}_{metric}", score)
         log(f"{stage}_loss", mean_over_examples("loss"))
 
     def training_step(self, batch, batch_idx):
@@ -264,9 +313,18 @@ class MultiModalLitModel(LightningModule):
         elif dataloader_idx == 1:                        # one 4-way trial per batch (reference :466-511)
             x, y, y_len, raw_y = batch
             x = x.view(-1, *x.shape[-3:])
+            te = self.language_model.text_encoder
             if self.lambda_mm:
                 logits_per_image, logits_per_text = self.model(x, y, y_len)
                 logits = logits_per_text[0]
+            elif self.lambda_lm and te.captioning and int(y[0, 0]) == SOS_TOKEN_ID:      # reference :478-495
+                # the LM scores the trial: - cross entropy of the first predicted token for each image
+                yy, yl = y.expand(x.size(0), -1).contiguous(), y_len.expand(x.size(0)).contiguous()
+                ce_loss = self.calculate_ce_loss(yy, yl, x=x, tokenwise=True)[0]
+                logits = -ce_loss[:, 0]
+            else:
+                logits = None
+            if logits is not None:
                 pred = torch.argmax(logits).item()
                 accuracy = int(pred == 0)
                 log(f"{stage}_accuracy", accuracy)

@@ -313,11 +313,12 @@ def _embed_gather(table, tok, pos=None):
     return x
 
 
-def lstm_text(table, lstm, tok, length):
+def lstm_text(table, lstm, tok, length, h0=None, c0=None):
     """Embedding + one-layer uni-directional nn.LSTM over variable-length sequences, eval mode
     (reference multimodal/multimodal.py:513-552).  -> (h at each sequence's last step [B,H], outputs [B,Lmax,H]).
     x W_ih^T for all steps is one GEMM; each step is one recurrent GEMM (gates of the input added through the
-    residual epilogue) plus the cell kernel."""
+    residual epilogue) plus the cell kernel.  ``h0``, ``c0`` [B, H]: the initial state (captioning, init_hidden :671-688);
+    zeros when absent."""
     if lstm.bidirectional or lstm.num_layers != 1:
         raise NotImplementedError("only the one-layer uni-directional LSTM text encoder is on the contrastive path")
     B, L = tok.shape
@@ -330,6 +331,11 @@ def lstm_text(table, lstm, tok, length):
         w_hh = lstm.weight_hh_l0.detach().contiguous()
         h = torch.zeros(B, Hd, dtype=_F, device=dev)                                   # init_hidden zeros (:671-688)
         c = torch.zeros(B, Hd, dtype=_F, device=dev)
+        if (h0 is None) != (c0 is None):
+            raise ValueError("lstm_text: give both h0 and c0 or neither")
+        if h0 is not None:
+            h.copy_(h0.detach().reshape(B, Hd))
+            c.copy_(c0.detach().reshape(B, Hd))
         out = torch.empty(B, L, Hd, dtype=_F, device=dev)
         gates = torch.empty(B, 4 * Hd, dtype=_F, device=dev)
         lib, s = H.lib(), H.stream_ptr()
@@ -343,6 +349,67 @@ def lstm_text(table, lstm, tok, length):
                     "cvcl_lstm_cell")
         lmax = int(length.max())              # pad_packed_sequence trims to the longest sequence (the reference syncs here too)
     return h, out[:, :lmax]
+
+
+def beam_search_lstm(table, lstm, out_weight, out_bias, batch_size, beam_width, decode_length, alpha, h0=None, c0=None,
+                     sos_id=2, eos_id=3, return_steps=False):
+    """Beam-search decoding of the one-layer LSTM language model (reference beam_search_decode, multimodal.py:893-960, over
+    beam_search.py:232-703) -> (seq [B, K, steps + 1] int64, scores [B, K] f32).  ``h0``, ``c0`` [B, H]: the image-initialised
+    state of a captioning model (zeros when absent).  Per step: h W_hh^T (fp32 GEMM), cvcl_lstm_cell_tok (adds row tok of
+    G = table W_ih^T + b_ih + b_hh, computed once), the output layer (fp32 GEMM, bias included) and cvcl_beam_step; the stop test
+    runs on the device, so the only host sync is the read of the final step count.  ``return_steps``: also return it."""
+    if lstm.bidirectional or lstm.num_layers != 1:
+        raise NotImplementedError("beam search decodes the one-layer uni-directional LSTM language model")
+    if (h0 is None) != (c0 is None):
+        raise ValueError("beam_search_lstm: give both h0 and c0 or neither")
+    B, K, T = int(batch_size), int(beam_width), int(decode_length)
+    V, E = table.shape
+    Hd = lstm.hidden_size
+    if out_weight.shape != (V, Hd):
+        raise ValueError(f"output layer {tuple(out_weight.shape)} does not map H = {Hd} to V = {V}")
+    dev = table.device
+    lib, s = H.lib(), H.stream_ptr()
+    N = B * K
+    with torch.no_grad():
+        bias = (lstm.bias_ih_l0 + lstm.bias_hh_l0).detach().contiguous()
+        G = H.gemm(table.detach().contiguous(), lstm.weight_ih_l0.detach().contiguous(), bias=bias)      # [V, 4H]
+        w_hh = lstm.weight_hh_l0.detach().contiguous()
+        w_out = out_weight.detach().contiguous()
+        b_out = None if out_bias is None else out_bias.detach().contiguous()
+        h = torch.zeros(2, N, Hd, dtype=_F, device=dev)
+        c = torch.zeros(2, N, Hd, dtype=_F, device=dev)
+        if h0 is not None:                                  # _expand_to_beam_size: every beam of item b starts from b's state
+            h[0].copy_(h0.detach().reshape(B, 1, Hd).expand(B, K, Hd).reshape(N, Hd))
+            c[0].copy_(c0.detach().reshape(B, 1, Hd).expand(B, K, Hd).reshape(N, Hd))
+        alive_lp = torch.full((2, B, K), -float("inf"), dtype=_F, device=dev)
+        alive_lp[0, :, 0] = 0.
+        fin = torch.full((2, B, K), -1e7, dtype=_F, device=dev)                    # beam_search.py INF = 1e7
+        alive_seq = torch.zeros(B, K, T + 1, dtype=torch.int64, device=dev)
+        alive_seq[:, :, 0] = sos_id
+        fin_seq = torch.zeros(B, K, T + 1, dtype=torch.int64, device=dev)
+        flags = torch.zeros(B, K, dtype=torch.int32, device=dev)
+        tok = torch.full((N,), sos_id, dtype=torch.int64, device=dev)
+        steps = torch.full((1,), T, dtype=torch.int32, device=dev)
+        gates = torch.empty(N, 4 * Hd, dtype=_F, device=dev)
+        logits = torch.empty(N, V, dtype=_F, device=dev)
+        for i in range(T):
+            a, b = i & 1, (i + 1) & 1
+            H.gemm(h[a], w_hh, out=gates)
+            H.check(lib.cvcl_lstm_cell_tok(H.ptr(gates), H.ptr(G), H.ptr(tok), V, H.ptr(h[a]), H.ptr(c[a]), N, Hd, s),
+                    "cvcl_lstm_cell_tok")
+            H.gemm(h[a], w_out, out=logits, bias=b_out)
+            H.check(lib.cvcl_beam_step(H.ptr(logits), B, K, V, T, i, float(alpha), int(eos_id), H.ptr(alive_lp[a]),
+                                       H.ptr(alive_lp[b]), H.ptr(fin[a]), H.ptr(fin[b]), H.ptr(alive_seq), H.ptr(fin_seq),
+                                       H.ptr(flags), H.ptr(h[a]), H.ptr(c[a]), H.ptr(h[b]), H.ptr(c[b]), Hd, H.ptr(tok),
+                                       H.ptr(steps), s), "cvcl_beam_step")
+        f = T & 1
+        out_seq = torch.empty(B, K, T + 1, dtype=torch.int64, device=dev)
+        out_scores = torch.empty(B, K, dtype=_F, device=dev)
+        H.check(lib.cvcl_beam_finalize(B, K, T, H.ptr(alive_seq), H.ptr(alive_lp[f]), H.ptr(fin_seq), H.ptr(fin[f]), H.ptr(flags),
+                                       H.ptr(out_seq), H.ptr(out_scores), s), "cvcl_beam_finalize")
+        n = int(steps.item())                               # the one host sync: the reference's final loop index
+    seq = out_seq[:, :, :n + 1].contiguous()
+    return (seq, out_scores, n) if return_steps else (seq, out_scores)
 
 
 def transformer_text(table, layer, pos_embed, tok, length):

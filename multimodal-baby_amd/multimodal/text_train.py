@@ -205,18 +205,28 @@ def transformer_text_train(table, layer, pos_embed, tok, length, training: bool,
 class LstmCore(torch.autograd.Function):
     """One-layer uni-directional nn.LSTM over [B*L, E] inputs with per-sequence lengths; returns the hidden state at
     each sequence's last step.  Forward saves gate activations / cell states / previous hidden states; backward is
-    BPTT: per step one recurrent GEMM + the cell kernel, then three big GEMMs for dW_ih, dW_hh, dX."""
+    BPTT: per step one recurrent GEMM + the cell kernel, then three big GEMMs for dW_ih, dW_hh, dX.  ``h0``, ``c0`` [B, H]: the
+    initial state (captioning, reference init_hidden :671-688; zeros when absent); their gradients are the dh, dc left after the
+    t = 0 step of BPTT (cvcl_lstm_cell_bwd_first uses c0 as c_{-1})."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, length, B, L):
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, length, B, L, h0=None, c0=None):
         Hd = w_hh.shape[1]
         dev = x.device
         lib, s = H.lib(), H.stream_ptr()
         bias = (b_ih + b_hh).contiguous()
         gx = H.gemm(x.contiguous(), w_ih.contiguous(), bias=bias)                       # [B*L, 4H]
         w_hh_c = w_hh.contiguous()
-        h = torch.zeros(B, Hd, dtype=_F, device=dev)
-        c = torch.zeros(B, Hd, dtype=_F, device=dev)
+        if (h0 is None) != (c0 is None):
+            raise ValueError("LstmCore: give both h0 and c0 or neither")
+        if h0 is None:
+            h = torch.zeros(B, Hd, dtype=_F, device=dev)
+            c = torch.zeros(B, Hd, dtype=_F, device=dev)
+            c0_saved = None
+        else:
+            h = h0.detach().reshape(B, Hd).contiguous().clone()
+            c = c0.detach().reshape(B, Hd).contiguous().clone()
+            c0_saved = c.clone()
         gates = torch.empty(B, 4 * Hd, dtype=_F, device=dev)
         gact = torch.zeros(B * L, 4 * Hd, dtype=_F, device=dev)
         csave = torch.empty(B * L, Hd, dtype=_F, device=dev)
@@ -230,14 +240,14 @@ class LstmCore(torch.autograd.Function):
             H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
             H.check(lib.cvcl_lstm_cell_train(H.ptr(gates), H.ptr(length, torch.int64), t, H.ptr(h), H.ptr(c), H.ptr(out), H.ptr(gact),
                                              H.ptr(csave), H.ptr(hprev), B, L, Hd, s), "cvcl_lstm_cell_train")
-        ctx.save_for_backward(x, w_ih, w_hh_c, length, gact, csave, hprev)
+        ctx.save_for_backward(x, w_ih, w_hh_c, length, gact, csave, hprev, c0_saved)
         ctx.dims = (B, L, Hd)
         ctx.set_materialize_grads(False)       # the unused one of (h, out) arrives as None instead of a zero tensor
         return h, out
 
     @staticmethod
     def backward(ctx, dh_final, d_out):
-        x, w_ih, w_hh, length, gact, csave, hprev = ctx.saved_tensors
+        x, w_ih, w_hh, length, gact, csave, hprev, c0 = ctx.saved_tensors
         B, L, Hd = ctx.dims
         dev = x.device
         lib, s = H.lib(), H.stream_ptr()
@@ -251,8 +261,12 @@ class LstmCore(torch.autograd.Function):
         for t in range(L - 1, -1, -1):
             if d_out is not None:             # per-step outputs feed the language-model branch: out[b,t] = h_t while running
                 H.check(lib.cvcl_lstm_add_dout(H.ptr(dh), H.ptr(d_out, _F), H.ptr(length), t, B, L, Hd, s), "cvcl_lstm_add_dout")
-            H.check(lib.cvcl_lstm_cell_bwd(H.ptr(gact), H.ptr(csave), H.ptr(length), t, H.ptr(dh), H.ptr(dc), H.ptr(dG), H.ptr(carry),
-                                           B, L, Hd, s), "cvcl_lstm_cell_bwd")
+            if t == 0 and c0 is not None:
+                H.check(lib.cvcl_lstm_cell_bwd_first(H.ptr(gact), H.ptr(csave), H.ptr(c0), H.ptr(length), H.ptr(dh), H.ptr(dc), H.ptr(dG),
+                                                     H.ptr(carry), B, L, Hd, s), "cvcl_lstm_cell_bwd_first")
+            else:
+                H.check(lib.cvcl_lstm_cell_bwd(H.ptr(gact), H.ptr(csave), H.ptr(length), t, H.ptr(dh), H.ptr(dc), H.ptr(dG),
+                                               H.ptr(carry), B, L, Hd, s), "cvcl_lstm_cell_bwd")
             a = H.GemmArgs()                                                       # dh_{t-1} = dG_t . W_hh + carry
             a.A, a.W, a.C = dG.data_ptr() + t * 4 * Hd * 4, H.ptr(w_hh), H.ptr(dh_next)      # W' = W_hh^T: W_hh read K-major in place
             a.M, a.N, a.K, a.lda, a.ldw, a.ldc = B, Hd, 4 * Hd, L * 4 * Hd, Hd, Hd
@@ -276,7 +290,10 @@ class LstmCore(torch.autograd.Function):
             H.check(lib.cvcl_colsum_f32(H.ptr(dG), H.ptr(db), B * L, 4 * Hd, s), "cvcl_colsum_f32")
         if needs[0]:
             dx = H.gemm(dG, w_ih.contiguous(), w_trans=True)
-        return dx, dwi, dwh, db, (db.clone() if db is not None else None), None, None, None
+        if c0 is None:
+            return dx, dwi, dwh, db, (db.clone() if db is not None else None), None, None, None
+        # after the t = 0 step: dh = dG_0 W_hh + carry = dL/dh0, dc = dL/dc0
+        return dx, dwi, dwh, db, (db.clone() if db is not None else None), None, None, None, dh, dc
 
 
 class SeqReverse(torch.autograd.Function):
@@ -364,8 +381,9 @@ def bilstm_text_train(table, lstm, tok, length, dropout_i: float, training: bool
     return ret, out[:, :int(length.max())]
 
 
-def lstm_text_train(table, lstm, tok, length, dropout_i: float, training: bool):
-    """Differentiable embedding -> LockedDropout(dropout_i) -> LSTM -> last hidden state (multimodal.py:513-552)."""
+def lstm_text_train(table, lstm, tok, length, dropout_i: float, training: bool, h0=None, c0=None):
+    """Differentiable embedding -> LockedDropout(dropout_i) -> LSTM -> last hidden state (multimodal.py:513-552).  ``h0``, ``c0``
+    [B, H]: the captioning initial state (differentiable); zeros when absent."""
     if lstm.bidirectional or lstm.num_layers != 1:
         raise NotImplementedError("only the one-layer uni-directional LSTM text encoder is on the contrastive path")
     B, L = tok.shape
@@ -373,5 +391,8 @@ def lstm_text_train(table, lstm, tok, length, dropout_i: float, training: bool):
     x = EmbedGatherPos.apply(table, None, tok)
     if training and dropout_i:
         x = DropoutAdd.apply(x, None, float(dropout_i), _seed(), L, E)        # mask [B,1,E] shared over time (:46-53)
-    h, out = LstmCore.apply(x, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, length, B, L)
+    if h0 is None:
+        h, out = LstmCore.apply(x, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, length, B, L)
+    else:
+        h, out = LstmCore.apply(x, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, length, B, L, h0, c0)
     return h, out[:, :int(length.max())]       # pad_packed_sequence trims to the longest sequence (reference syncs too)
