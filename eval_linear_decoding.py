@@ -1,0 +1,10 @@
+"""The reference's eval_linear_decoding.py on the HIP trunk (multimodal/linear_probe.py)."""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "multimodal-baby_amd"))
+
+from multimodal import linear_probe  # noqa: E402
+
+if __name__ == "__main__":
+    linear_probe.eval_main(linear_probe.eval_parser("saycam").parse_args(), "saycam")

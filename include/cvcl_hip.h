@@ -374,6 +374,19 @@ int cvcl_resnext50_fwd_deferred_stats(int dtype, int B, int H, int W, const floa
                                       void* stream);
 int cvcl_resnext50_apply_moments(const cvcl_convbn_params* layers, int n_layers, const float* moments, float momentum,
                                  void* stream);
+/* Grouped train-mode pass (ABI v7, additive): the reference's linear-probe evaluation (eval_linear_decoding.py:53-57, 89-91;
+ * eval_object_categories_linear_decoding.py:52-56, 90-92) never calls .eval(), so every 4-image trial runs the trunk with
+ * that trial's own BatchNorm batch statistics.  B = T * group images in T consecutive groups: every one of the 53
+ * BatchNorm layers normalises each group with the group's mean and biased variance over its group * h * w rows (eps, affine
+ * as nn.BatchNorm2d in train mode), so each group's layer4_out_nhwc / pooled rows equal cvcl_resnext50_fwd(training = 1) on
+ * those images alone.  The running statistics are neither read nor written (layers[l].running_* may be NULL).
+ * CVCL_F32 and CVCL_F32X3 only (fp32 storage); CVCL_BF16, group < 1, B % group != 0, H or W not a multiple of 32, a null
+ * pointer: CVCL_EINVAL before anything is enqueued.  The workspace query returns 0 for those.  Kernels: bn_group_stats
+ * (centred two-pass partial moments), bn_group_finalize, bn_group_relu, bn_group_add_relu, bn_group_relu_maxpool.       */
+size_t cvcl_resnext50_fwd_grouped_workspace_bytes(int dtype, int B, int H, int W, int group);
+int cvcl_resnext50_fwd_grouped(int dtype, int B, int H, int W, int group, const float* x_nchw,
+                               const cvcl_convbn_params* layers, int n_layers, void* workspace, size_t workspace_bytes,
+                               void* layer4_out_nhwc, float* pooled, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * DINO ViT image encoder (multimodal/vision_transformer_dino_mugs.py:87-250), the one-layer text

@@ -1172,6 +1172,148 @@ int grid_for(long total, int per_block = 256, int cap = 4096) {
     return (int)(g > cap ? cap : g);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Grouped train-mode BatchNorm (linear-probe scoring, cvcl_resnext50_fwd_grouped): the batch is T consecutive groups of
+// rows_g rows, and each group is normalised on its own mean and biased variance.  fp32 storage only (CVCL_F32, CVCL_F32X3).
+// ------------------------------------------------------------------------------------------------
+// partial moments of one row slice of one group -> part[T][S][2][C] = (slice mean, slice sum of squared deviations), centred
+// two-pass: the slice's mean first, then sum (x - mean)^2 over the same rows (no E[x^2] - E[x]^2 cancellation).
+// grid (S, T, C / 64); a thread owns 4 channels (one 16-byte load) of every 16th row of the slice.
+__global__ __launch_bounds__(256) void bn_group_stats_kernel(const float* __restrict__ x, long rows_g, int C, int S,
+                                                             float* __restrict__ part) {
+    __shared__ f32x4 red[16][16];
+    const int q = threadIdx.x & 15, lane = threadIdx.x >> 4;
+    const int s = blockIdx.x, t = blockIdx.y, c0 = blockIdx.z * 64 + q * 4;
+    const long r0 = rows_g * s / S, r1 = rows_g * (s + 1) / S;
+    const float* xg = x + (long)t * rows_g * C + c0;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (long r = r0 + lane; r < r1; r += 16) acc += *reinterpret_cast<const f32x4*>(xg + r * C);
+    red[lane][q] = acc;
+    __syncthreads();
+    f32x4 tot = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tot += red[i][q];                  // same fixed order in every thread of the column
+    const float inv_n = 1.f / (float)(r1 - r0);
+    const f32x4 mean = tot * inv_n;
+    __syncthreads();                                                // every thread has read red before it is reused
+    acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (long r = r0 + lane; r < r1; r += 16) {
+        const f32x4 d = *reinterpret_cast<const f32x4*>(xg + r * C) - mean;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = fmaf(d[k], d[k], acc[k]);
+    }
+    red[lane][q] = acc;
+    __syncthreads();
+    if (lane == 0) {
+        f32x4 m2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m2 += red[i][q];
+        float* p = part + ((long)t * S + s) * 2 * C + c0;
+        *reinterpret_cast<f32x4*>(p) = mean;
+        *reinterpret_cast<f32x4*>(p + C) = m2;
+    }
+}
+
+// the S slices of every group merged in a fixed order in fp64 (Chan et al.: M2 = sum M2_s + n_s (mean_s - mean)^2), then the
+// train-mode affine of nn.BatchNorm2d with the biased variance: scale = gamma / sqrt(var + eps), shift = beta - mean * scale.
+// -> scale [T][C], shift [T][C]; grid (C / 256 rounded up, T)
+__global__ __launch_bounds__(256) void bn_group_finalize_kernel(const float* __restrict__ part, long rows_g, int S, int C,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                float eps, float* __restrict__ scale, float* __restrict__ shift) {
+    const int ch = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
+    if (ch >= C) return;
+    const float* p = part + (long)t * S * 2 * C + ch;
+    double mean = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const double n = (double)(rows_g * (s + 1) / S - rows_g * s / S);
+        mean += n * (double)p[(long)s * 2 * C];
+    }
+    mean /= (double)rows_g;
+    double m2 = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const double n = (double)(rows_g * (s + 1) / S - rows_g * s / S);
+        const double d = (double)p[(long)s * 2 * C] - mean;
+        m2 += (double)p[(long)s * 2 * C + C] + n * d * d;
+    }
+    const double var = m2 / (double)rows_g;
+    const float sc = gamma[ch] / sqrtf((float)var + eps);
+    scale[(long)t * C + ch] = sc;
+    shift[(long)t * C + ch] = beta[ch] - (float)mean * sc;
+}
+
+// y = relu(x * scale[g] + shift[g]) over [rows, C], g = row / rows_g (may run in place)
+__global__ __launch_bounds__(256) void bn_group_relu_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, float* __restrict__ y, long rows,
+                                                            int C, long rows_g) {
+    const int CC = C / 4;
+    const long total = rows * CC;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / CC;
+        const long a = r / rows_g * C + (i - r * CC) * 4;
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + a), sh = *reinterpret_cast<const f32x4*>(shift + a);
+        f32x4 v = *reinterpret_cast<const f32x4*>(x + i * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = fmaxf(fmaf(v[k], sc[k], sh[k]), 0.f);
+        *reinterpret_cast<f32x4*>(y + i * 4) = v;
+    }
+}
+
+// out = relu(raw * scale[g] + shift[g] + identity), identity = idn or idn * idn_scale[g] + idn_shift[g]; g = row / rows_g
+__global__ __launch_bounds__(256) void bn_group_add_relu_kernel(const float* __restrict__ raw, const float* __restrict__ scale,
+                                                                const float* __restrict__ shift, const float* __restrict__ idn,
+                                                                const float* __restrict__ idn_scale,
+                                                                const float* __restrict__ idn_shift, float* __restrict__ out,
+                                                                long rows, int C, long rows_g) {
+    const int CC = C / 4;
+    const long total = rows * CC;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / CC;
+        const long a = r / rows_g * C + (i - r * CC) * 4;
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + a), sh = *reinterpret_cast<const f32x4*>(shift + a);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(raw + i * 4);
+        f32x4 d = *reinterpret_cast<const f32x4*>(idn + i * 4);
+        if (idn_scale) {
+            const f32x4 isc = *reinterpret_cast<const f32x4*>(idn_scale + a), ish = *reinterpret_cast<const f32x4*>(idn_shift + a);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d[k] = fmaf(d[k], isc[k], ish[k]);
+        }
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = fmaxf(fmaf(v[k], sc[k], sh[k]) + d[k], 0.f);
+        *reinterpret_cast<f32x4*>(out + i * 4) = o;
+    }
+}
+
+// relu(bn(x)) then maxpool 3x3/2 pad 1: [B,H,W,C] -> [B,ceil(H/2),ceil(W/2),C], image b normalised with group b / G's affine.
+// The ReLU output is >= 0 and every window holds at least one pixel, so a maximum started at 0 over the in-image taps equals
+// torch's -inf padding.
+__global__ __launch_bounds__(256) void bn_group_relu_maxpool_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                                                    const float* __restrict__ shift, float* __restrict__ y,
+                                                                    int B, int H, int W, int C, int G) {
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, CC = C / 4;
+    const long total = (long)B * Ho * Wo * CC;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int cc = (int)(i % CC);
+        const long p = i / CC;
+        const int ox = (int)(p % Wo), oy = (int)((p / Wo) % Ho), b = (int)(p / ((long)Wo * Ho));
+        const long a = (long)(b / G) * C + cc * 4;
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + a), sh = *reinterpret_cast<const f32x4*>(shift + a);
+        f32x4 m = {0.f, 0.f, 0.f, 0.f};
+        for (int ky = 0; ky < 3; ++ky) {
+            const int yin = 2 * oy - 1 + ky;
+            if (yin < 0 || yin >= H) continue;
+            for (int kx = 0; kx < 3; ++kx) {
+                const int xin = 2 * ox - 1 + kx;
+                if (xin < 0 || xin >= W) continue;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(x + (((long)b * H + yin) * W + xin) * C + cc * 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) m[k] = fmaxf(m[k], fmaf(v[k], sc[k], sh[k]));
+            }
+        }
+        *reinterpret_cast<f32x4*>(y + p * C + cc * 4) = m;
+    }
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -2040,4 +2182,149 @@ extern "C" int cvcl_resnext50_apply_moments(const cvcl_convbn_params* layers, in
     hipLaunchKernelGGL(bn_apply_moments_kernel, dim3(53), dim3(256), 0, (hipStream_t)stream, t, moments, momentum);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Grouped train-mode pass (linear-probe scoring: the reference's eval_linear_decoding.py:53-57, 89-91 and
+// eval_object_categories_linear_decoding.py:52-56, 90-92 never call .eval(), so each 4-image trial is normalised with that
+// trial's own batch statistics).  The B = T * group images form T consecutive groups; every BatchNorm normalises each group
+// on the group's own mean and biased variance, so each group's outputs are those of cvcl_resnext50_fwd(training = 1) run on
+// its images alone.  The convolutions run through the same entries as the batch pass with their statistics output off;
+// after each one bn_group_stats / bn_group_finalize form a per-group affine and the bn_group_* passes apply it.  fp32
+// storage only (CVCL_F32, CVCL_F32X3); the running statistics are read and written by nothing.
+// ------------------------------------------------------------------------------------------------
+namespace {
+// row slices per group for bn_group_stats: about 2048 workgroups in all, >= 64 rows a slice, at most 64 slices
+int group_slices(int T, long rows_g, int C) {
+    long s = 2048 / ((long)T * (C / 64));
+    if (s > 64) s = 64;
+    if (s > rows_g / 64) s = rows_g / 64;
+    return s < 1 ? 1 : (int)s;
+}
+// part[T][S][2][C] holds 128 T S (C / 64) floats; group_slices keeps T S (C / 64) <= max(2048, 32 T)
+size_t group_part_floats(int T) { return (size_t)128 * std::max<size_t>(2048, (size_t)32 * T); }
+bool grouped_dtype(int dtype) { return dtype == CVCL_F32 || dtype == CVCL_F32X3; }
+}  // namespace
+
+extern "C" size_t cvcl_resnext50_fwd_grouped_workspace_bytes(int dtype, int B, int H, int W, int group) {
+    if (!grouped_dtype(dtype) || B <= 0 || group < 1 || B % group != 0 || H <= 0 || W <= 0) return 0;
+    const int T = B / group;
+    return 5 * al256(act_elems(B, H, W) * 4) + al256(group_part_floats(T) * 4) + 4 * al256((size_t)T * 2 * 2048 * 4);
+}
+
+extern "C" int cvcl_resnext50_fwd_grouped(int dtype, int B, int H, int W, int group, const float* x_nchw,
+                                          const cvcl_convbn_params* layers, int n_layers, void* workspace, size_t workspace_bytes,
+                                          void* layer4_out_nhwc, float* pooled, float eps, void* stream) {
+    CVCL_CHECK_ARG(grouped_dtype(dtype), "cvcl_resnext50_fwd_grouped: dtype %d not supported (CVCL_F32 / CVCL_F32X3)", dtype);
+    CVCL_CHECK_ARG(group >= 1, "cvcl_resnext50_fwd_grouped: group %d < 1", group);
+    CVCL_CHECK_ARG(B > 0 && B % group == 0, "cvcl_resnext50_fwd_grouped: B = %d is not a multiple of group = %d", B, group);
+    CVCL_CHECK_ARG(H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0, "cvcl_resnext50_fwd_grouped: H, W must be multiples of 32");
+    CVCL_CHECK_ARG(x_nchw && layers && workspace && layer4_out_nhwc && pooled, "cvcl_resnext50_fwd_grouped: null pointer");
+    CVCL_CHECK_ARG(n_layers == 53, "cvcl_resnext50_fwd_grouped: expected 53 conv+bn layers, got %d", n_layers);
+    for (int l = 0; l < 53; ++l)
+        CVCL_CHECK_ARG(layers[l].w && layers[l].gamma && layers[l].beta, "cvcl_resnext50_fwd_grouped: layer %d: null pointer", l);
+    if (workspace_bytes < cvcl_resnext50_fwd_grouped_workspace_bytes(dtype, B, H, W, group)) {
+        cvcl_set_error("cvcl_resnext50_fwd_grouped: workspace too small");
+        return CVCL_EWORKSPACE;
+    }
+    const int T = B / group;
+    hipStream_t s = (hipStream_t)stream;
+    char* w = (char*)workspace;
+    float* buf[5];
+    for (int i = 0; i < 5; ++i) { buf[i] = (float*)w; w += al256(act_elems(B, H, W) * 4); }
+    float* part = (float*)w; w += al256(group_part_floats(T) * 4);
+    float* aff[4];                                      // per-group (scale [T][C], shift [T][C]) of conv1, conv2, conv3, downsample
+    for (int i = 0; i < 4; ++i) { aff[i] = (float*)w; w += al256((size_t)T * 2 * 2048 * 4); }
+    auto shift_of = [&](const float* a, int C) { return a + (size_t)T * C; };
+    // layer l's raw output y ([T groups of rows_g rows, C]) -> its per-group affine in a
+    auto group_bn = [&](int l, const float* y, long rows_g, int C, float* a) -> int {
+        const int S = group_slices(T, rows_g, C);
+        {
+            CvclProfScope prof(stream, CVCL_K_OTHER);
+            hipLaunchKernelGGL(bn_group_stats_kernel, dim3(S, T, C / 64), dim3(256), 0, s, y, rows_g, C, S, part);
+            CVCL_LAUNCH_CHECK();
+        }
+        CvclProfScope prof(stream, CVCL_K_BN_FINALIZE);
+        hipLaunchKernelGGL(bn_group_finalize_kernel, dim3(cvcl_div_up(C, 256), T), dim3(256), 0, s, part, rows_g, S, C, layers[l].gamma,
+                           layers[l].beta, eps, a, a + (size_t)T * C);
+        CVCL_LAUNCH_CHECK();
+        return CVCL_OK;
+    };
+    auto group_relu = [&](float* x, const float* a, long rows, int C, long rows_g) -> int {
+        CvclProfScope prof(stream, CVCL_K_BN_APPLY);
+        hipLaunchKernelGGL(bn_group_relu_kernel, dim3(grid_for(rows * (C / 4), 256, 16384)), dim3(256), 0, s, x, a, shift_of(a, C), x,
+                           rows, C, rows_g);
+        CVCL_LAUNCH_CHECK();
+        return CVCL_OK;
+    };
+    int rc;
+    // ---- stem: conv1 -> bn1 + relu + maxpool ----
+    int h = H / 2, wd = W / 2;
+    if ((rc = cvcl_stem_conv7x7(dtype, x_nchw, layers[0].w, buf[2], nullptr, 0, nullptr, B, H, W, stream))) return rc;
+    if ((rc = group_bn(0, buf[2], (long)group * h * wd, 64, aff[0]))) return rc;
+    {
+        CvclProfScope prof(stream, CVCL_K_MAXPOOL);
+        const long total = (long)B * ((h - 1) / 2 + 1) * ((wd - 1) / 2 + 1) * 16;
+        hipLaunchKernelGGL(bn_group_relu_maxpool_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, s, buf[2], aff[0],
+                           shift_of(aff[0], 64), buf[0], B, h, wd, 64, group);
+        CVCL_LAUNCH_CHECK();
+    }
+    h = (h - 1) / 2 + 1; wd = (wd - 1) / 2 + 1;
+    // ---- layer1 .. layer4 (torchvision Bottleneck.forward) ----
+    float* X = buf[0];
+    float* OUT = buf[1];
+    float* R1 = buf[2]; float* R2 = buf[3]; float* R3 = buf[2]; float* RD = buf[4];      // R3 reuses R1 (read by conv2 before)
+    int li = 1;
+    for (int stage = 0; stage < 4; ++stage) {
+        for (int bi = 0; bi < kLayers[stage]; ++bi) {
+            const bool first = bi == 0;
+            const int planes = 64 << stage, width = planes * 2, outc = planes * 4;
+            const int inplanes = first ? (stage == 0 ? 64 : outc / 2) : outc;
+            const int stride = (stage > 0 && first) ? 2 : 1;
+            const int ho = h / stride, wo = wd / stride;
+            const long m_in = (long)B * h * wd, m_out = (long)B * ho * wo;
+            const long g_in = (long)group * h * wd, g_out = (long)group * ho * wo;
+            const cvcl_convbn_params* L = layers + li;
+            float* dst = (stage == 3 && bi == kLayers[3] - 1) ? (float*)layer4_out_nhwc : OUT;
+            if (first) {                                  // downsample 1x1 stride s: X -> RD [m_out, outc]
+                cvcl_gemm_args a = {};
+                a.A = X; a.W = L[3].w; a.C = RD;
+                a.M = (int)m_out; a.N = outc; a.K = inplanes; a.lda = inplanes; a.ldw = inplanes; a.ldc = outc;
+                if (stride > 1) { a.gather_ho = ho; a.gather_wo = wo; a.gather_hi = h; a.gather_wi = wd; a.gather_stride = stride; }
+                if ((rc = cvcl_gemm(dtype, &a, stream))) return rc;
+                if ((rc = group_bn(li + 3, RD, g_out, outc, aff[3]))) return rc;
+            }
+            {                                             // conv1 1x1: X -> R1 [m_in, width]; bn1 + relu in place
+                cvcl_gemm_args a = {};
+                a.A = X; a.W = L[0].w; a.C = R1;
+                a.M = (int)m_in; a.N = width; a.K = inplanes; a.lda = inplanes; a.ldw = inplanes; a.ldc = width;
+                if ((rc = cvcl_gemm(dtype, &a, stream))) return rc;
+            }
+            if ((rc = group_bn(li, R1, g_in, width, aff[0]))) return rc;
+            if ((rc = group_relu(R1, aff[0], m_in, width, g_in))) return rc;
+            // conv2 grouped 3x3 (stride here) on the normalised R1 (no affine on load): -> R2 [m_out, width]; bn2 + relu in place
+            if ((rc = gconv3x3_impl(dtype, R1, nullptr, nullptr, nullptr, L[1].w, R2, nullptr, 0, nullptr, B, h, wd, width, 32, stride,
+                                    stream))) return rc;
+            if ((rc = group_bn(li + 1, R2, g_out, width, aff[1]))) return rc;
+            if ((rc = group_relu(R2, aff[1], m_out, width, g_out))) return rc;
+            {                                             // conv3 1x1: R2 -> R3 [m_out, outc]
+                cvcl_gemm_args a = {};
+                a.A = R2; a.W = L[2].w; a.C = R3;
+                a.M = (int)m_out; a.N = outc; a.K = width; a.lda = width; a.ldw = width; a.ldc = outc;
+                if ((rc = cvcl_gemm(dtype, &a, stream))) return rc;
+            }
+            if ((rc = group_bn(li + 2, R3, g_out, outc, aff[2]))) return rc;
+            {                                             // bn3 + identity / bn(downsample) + relu -> dst
+                CvclProfScope prof(stream, CVCL_K_BN_ADD_RELU);
+                hipLaunchKernelGGL(bn_group_add_relu_kernel, dim3(grid_for(m_out * (outc / 4), 256, 16384)), dim3(256), 0, s, R3, aff[2],
+                                   shift_of(aff[2], outc), first ? RD : X, first ? aff[3] : nullptr,
+                                   first ? shift_of(aff[3], outc) : nullptr, dst, m_out, outc, g_out);
+                CVCL_LAUNCH_CHECK();
+            }
+            li += first ? 4 : 3;
+            float* t = X; X = dst; OUT = t;
+            h = ho; wd = wo;
+        }
+    }
+    return cvcl_avgpool(dtype, layer4_out_nhwc, pooled, B, h * wd, 2048, stream);
 }

@@ -189,6 +189,8 @@ SIGNATURES = {
     "cvcl_resnext50_moments_floats": (_SZ, []),
     "cvcl_resnext50_fwd_deferred_stats": (_I, [_I, _I, _I, _I, _P, C.POINTER(ConvBnParams), _I, _P, _SZ, _P, _P, _F, _P, _P, _P]),
     "cvcl_resnext50_apply_moments": (_I, [C.POINTER(ConvBnParams), _I, _P, _F, _P]),
+    "cvcl_resnext50_fwd_grouped_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "cvcl_resnext50_fwd_grouped": (_I, [_I, _I, _I, _I, _I, _P, C.POINTER(ConvBnParams), _I, _P, _SZ, _P, _P, _F, _P]),
     "cvcl_gradcam_pairs": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _F, _P, _P]),
     "cvcl_bicubic_resize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cvcl_gradcam_act_grad": (_I, [_I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P]),

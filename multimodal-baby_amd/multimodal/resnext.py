@@ -9,6 +9,7 @@ PyTorch-op fallback: CPU tensors raise.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -244,9 +245,14 @@ class ResNet(nn.Module):
         self.__dict__["_centres"] = (key, centres, ready)
         return centres
 
-    def trunk(self, x: torch.Tensor, defer_wait: bool = False):
+    def trunk(self, x: torch.Tensor, defer_wait: bool = False, bn_groups: int | None = None):
         """conv1 .. layer4 + avgpool.  -> (pooled [B,2048] f32, layer4 map as a logical NCHW view).  With a trunk stream and
-        ``defer_wait`` the result is a handle for ``self._trunk_stream.wait`` (the caller's stream has not waited yet)."""
+        ``defer_wait`` the result is a handle for ``self._trunk_stream.wait`` (the caller's stream has not waited yet).
+        ``bn_groups=G`` in train mode: every BatchNorm normalises each consecutive group of G images on that group's own batch
+        statistics (``cvcl_resnext50_fwd_grouped``; running statistics untouched) -- each group's outputs are those of a
+        train-mode pass over its G images alone.  In eval mode the running statistics serve every image and G changes nothing."""
+        if bn_groups is not None and self.training:
+            return self._trunk_grouped(x, int(bn_groups))
         if torch.is_grad_enabled() and any(p.requires_grad for c, b, _ in self.conv_bn_pairs() for p in (c.weight, b.weight, b.bias)):
             if self.trunk_dtype() == H.F32X3:
                 raise H.CvclError("--finetune_cnn is not available in the 32-split precision (use 32 or bf16)")
@@ -262,6 +268,46 @@ class ResNet(nn.Module):
                 return handle
             return ts.wait(handle)
         return self._trunk_launch(x)
+
+    @contextlib.contextmanager
+    def grouped_bn(self, bn_groups: int):
+        """``with model.grouped_bn(G): logits = model(imgs)`` -- forward with ``trunk(x, bn_groups=G)`` (the linear probe's
+        trial scoring: each G-image trial normalised on its own batch statistics, as the reference's train-mode model does)."""
+        prev = self.__dict__.get("_bn_groups")
+        self.__dict__["_bn_groups"] = int(bn_groups)
+        try:
+            yield self
+        finally:
+            self.__dict__["_bn_groups"] = prev
+
+    def _trunk_grouped(self, x, G):
+        dt = self.trunk_dtype()
+        if dt == H.BF16:
+            raise H.CvclError("grouped train-mode BatchNorm (bn_groups) is available in the 32 and 32-split precisions, not bf16")
+        if torch.is_grad_enabled() and any(p.requires_grad for c, b, _ in self.conv_bn_pairs() for p in (c.weight, b.weight, b.bias)):
+            raise H.CvclError("bn_groups runs the frozen trunk only (no --finetune_cnn backward)")
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+            raise H.CvclError(f"expected NCHW fp32 images, got {tuple(x.shape)} {x.dtype}")
+        B, _, Hh, Ww = x.shape
+        if G < 1 or B % G:
+            raise H.CvclError(f"bn_groups={G} does not divide the batch of {B} images")
+        x = x.contiguous()
+        lib = H.lib()
+        with torch.no_grad():
+            arr, _keep = self._packed_layers(dt, x.device)
+            nb = lib.cvcl_resnext50_fwd_grouped_workspace_bytes(dt, B, Hh, Ww, G)
+            wkey = ("grouped", nb, str(x.device))
+            ws = self._ws_cache.get(wkey)
+            if ws is None:
+                for k in [k for k in self._ws_cache if k[0] == "grouped"]:
+                    del self._ws_cache[k]
+                ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+                self._ws_cache[wkey] = ws
+            fmap = torch.empty(B, Hh // 32, Ww // 32, 2048, dtype=torch.float32, device=x.device)
+            pooled = torch.empty(B, 2048, dtype=torch.float32, device=x.device)
+            H.check(lib.cvcl_resnext50_fwd_grouped(dt, B, Hh, Ww, G, H.ptr(x), arr, len(arr), H.ptr(ws), nb, H.ptr(fmap), H.ptr(pooled),
+                                                   BN_EPS, H.stream_ptr()), "cvcl_resnext50_fwd_grouped")
+        return pooled, fmap.permute(0, 3, 1, 2)
 
     def enable_trunk_stream(self, device, inputs="caller", stream=None, n_streams=None):
         """Run the frozen trunk on a stream of its own so it overlaps the previous step's trainable tail (see H.TrunkStream).
@@ -362,7 +408,9 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         ts = self.__dict__.get("_trunk_stream")
-        out = self.trunk(x, defer_wait=True)
+        G = self.__dict__.get("_bn_groups")
+        # (the batch path keeps its call exactly: callers may stand a plain function in for ``trunk``)
+        out = self.trunk(x, defer_wait=True) if G is None else self.trunk(x, defer_wait=True, bn_groups=G)
         cb = self.__dict__.get("_pre_head_callback")
         if cb is not None:
             cb()                                         # deferred all-reduce wait + optimizer step of the previous step

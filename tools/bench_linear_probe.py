@@ -1,0 +1,155 @@
+"""Linear-probe throughput on the HIP trunk, in the 32 and 32-split precisions (random-init ResNeXt-50 + a 2048 -> 22 fc,
+224^2 frames):
+- probe training (linear_probe.train's step: train-mode forward with running-statistics update, cross entropy, fc backward,
+  Adam over all parameters): ms/step and images/s at B = 64 (the reference's batch) and B = 256;
+- trial scoring: T trials of G images each, scored either as T train-mode passes of G images (the reference's loop,
+  eval_linear_decoding.py:89-91, --trial_batch 1) or as one grouped pass (ResNet.trunk(x, bn_groups=G), --trial_batch T).
+
+    python tools/bench_linear_probe.py [--trials 64] [--group 4] [--size 224] [--iters 5] [--train-batches 64,256]
+    python tools/bench_linear_probe.py --kernel-stats DIR      # after `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python <this> --iters 2`
+
+Times with device events after warm-up; prints one JSON line.  With --kernel-stats it reads the kernel_stats.csv files under DIR
+and prints, for each grouped BatchNorm kernel, its share of the kernel time and the bytes per second it reached on the bytes
+the algorithm needs (each tensor element read once / written once; the statistics kernel's second, centred pass is counted
+once more as a re-read)."""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
+
+LAYERS = (3, 4, 6, 3)
+
+
+def grouped_bytes(B, S):
+    """bytes each grouped-BN kernel class moves in one pass over B images of S x S (fp32)"""
+    out = {"bn_group_stats": 0, "bn_group_relu": 0, "bn_group_add_relu": 0, "bn_group_relu_maxpool": 0}
+    h = S // 2
+    out["bn_group_stats"] += 2 * 4 * B * h * h * 64
+    out["bn_group_relu_maxpool"] += 4 * B * h * h * 64 + 4 * B * (h // 2) ** 2 * 64
+    h //= 2
+    for st, n in enumerate(LAYERS):
+        planes = 64 << st
+        width, outc = planes * 2, planes * 4
+        for bi in range(n):
+            stride = 2 if (st > 0 and bi == 0) else 1
+            ho = h // stride
+            m_in, m_out = B * h * h, B * ho * ho
+            out["bn_group_stats"] += 2 * 4 * (m_in * width + m_out * width + m_out * outc + (m_out * outc if bi == 0 else 0))
+            out["bn_group_relu"] += 8 * (m_in * width + m_out * width)
+            out["bn_group_add_relu"] += 12 * m_out * outc
+            h = ho
+    return out
+
+
+def kernel_report(d, B, S, passes):
+    rows = []
+    for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+        with open(f) as fh:
+            rows += list(csv.DictReader(fh))
+    if not rows:
+        sys.exit(f"no kernel_stats.csv under {d}")
+    total = sum(float(r["TotalDurationNs"]) for r in rows)
+    need = grouped_bytes(B, S)
+    rep = {"kernel_time_total_ms": total / 1e6, "kernels": {}}
+    for r in rows:
+        name = r["Name"]
+        key = next((k for k in sorted(need, key=len, reverse=True) if k + "_kernel" in name), None)
+        fin = "bn_group_finalize" in name
+        if key is None and not fin:
+            continue
+        ns = float(r["TotalDurationNs"])
+        e = {"calls": int(r["Calls"]), "total_ms": ns / 1e6, "share_of_kernel_time": ns / total}
+        if key is not None:
+            # the profiled run does `passes` grouped passes in each precision with the same shapes
+            e["GB_per_s"] = need[key] * passes / ns
+        rep["kernels"]["bn_group_finalize" if fin else key] = e
+    print(json.dumps(rep))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--trials", type=int, default=64)
+    ap.add_argument("--group", type=int, default=4)
+    ap.add_argument("--size", type=int, default=224)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--kernel-stats", default=None)
+    ap.add_argument("--grouped-only", action="store_true", help="time the grouped pass only (the profiled run)")
+    ap.add_argument("--train-batches", default="64,256", help="probe-training batch sizes to time ('' = none)")
+    a = ap.parse_args()
+    T, G, S = a.trials, a.group, a.size
+    if a.kernel_stats:
+        kernel_report(a.kernel_stats, T * G, S, 2 * (a.iters + 1))
+        return
+    import torch
+    from multimodal.resnext import ResNet
+    if not torch.cuda.is_available():
+        sys.exit("bench_linear_probe: no GPU")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    m = ResNet()
+    m.fc = torch.nn.Linear(2048, 22)
+    m = m.to(dev).train()
+    for p in m.parameters():
+        p.requires_grad_(False)
+    x = torch.randn(T * G, 3, S, S, device=dev)
+    res = {"trials": T, "group": G, "size": S}
+
+    def grouped():
+        with m.grouped_bn(G):
+            return m(x)
+
+    def loop():
+        return [m(x[t * G:(t + 1) * G]) for t in range(T)]
+
+    def timed(fn):
+        fn()                                   # warm-up: packs weights, allocates workspaces, loads code objects
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(a.iters):
+            fn()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) / a.iters
+
+    with torch.no_grad():
+        for prec, arith in (("32", "exact"), ("32-split", "split")):
+            m.trunk_arithmetic = arith
+            ms_g = timed(grouped)
+            res[f"{prec}_grouped_ms"] = ms_g
+            res[f"{prec}_grouped_trials_per_s"] = T / ms_g * 1e3
+            if not a.grouped_only:
+                ms_l = timed(loop)
+                res[f"{prec}_per_trial_ms"] = ms_l
+                res[f"{prec}_per_trial_trials_per_s"] = T / ms_l * 1e3
+                res[f"{prec}_speedup"] = ms_l / ms_g
+    if not a.grouped_only and a.train_batches:
+        from multimodal import linear_probe as L
+        opt = torch.optim.Adam(m.parameters(), 5e-4)
+        m.fc.weight.requires_grad_(True)
+        m.fc.bias.requires_grad_(True)
+        for B in (int(v) for v in a.train_batches.split(",")):
+            xb = torch.randn(B, 3, S, S, device=dev)
+            yb = torch.randint(0, 22, (B,), device=dev)
+
+            def step():
+                loss = L.cross_entropy(m(xb), yb)
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+
+            for prec, arith in (("32", "exact"), ("32-split", "split")):
+                m.trunk_arithmetic = arith
+                ms = timed(step)
+                res[f"train_{prec}_B{B}_ms_per_step"] = ms
+                res[f"train_{prec}_B{B}_images_per_s"] = B / ms * 1e3
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
