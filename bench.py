@@ -1,6 +1,6 @@
 """CVCL contrastive train-step benchmark on MI355X (driver contract: see the task prompt / DESIGN.md section 7).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,10 +15,15 @@ set, [RCCL gradient all-reduce], AdamW.  Weak scaling (the per-GPU batch is fixe
     c4            configs[3]: frozen DINO ViT-B/16 (bf16 MFMA linears) + trainable transformer text encoder, 256 / GPU
     c5            configs[4]: c4 with e4m3 weights / activations in the ViT linears (scaled MFMA); --batch grows the per-GPU batch
 
-Rank 0 prints ONE JSON line with the throughput, the measured deviation of the benchmarked precision from the exact-fp32
-parity mode on the same batch (``logits_rel_vs_fp32``), the roofline of the dominant kernel (timed live with HIP events on
-the launch stream in a second pass of the same steps, so the events do not perturb the headline number) and a CPU
-baseline (the oracle restatement of the reference step on the host cores, bounded sample).
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure needs: set up, warm up, time the steps, write
+``--dump-outputs`` if asked, print the throughput (``value``, ``ms_per_step``, ``whole_step``, ``final_loss``, ``hbm_peak_gb``).
+``--full`` adds everything else the benchmark measures, each from passes of its own around the timed steps: the measured
+deviation of the benchmarked precision from the exact-fp32 parity mode on the same batch (``logits_rel_vs_fp32``) and, on the
+default line, from torch's own ops; the roofline of the dominant kernel (timed live with HIP events on the launch stream in
+further passes of the same steps, so the events do not perturb the headline number); the trainable tail on its own; on the
+default line the sub-records of the other precisions / configurations (fp32 parity mode, C4, C5, C4 at patch 14, --finetune_cnn)
+and a CPU baseline (the oracle restatement of the reference step on the host cores, bounded sample); with N > 1 the
+collectives timed on their own.  The ``--no-*`` switches narrow what ``--full`` adds.
 """
 import argparse
 import contextlib
@@ -423,11 +428,12 @@ def spawn_ranks(a, argv):
     return subprocess.call(cmd, env=env)
 
 
-def dist_selfcheck(device, world, rank, local_rank):
+def dist_selfcheck(device, world, rank, local_rank, time_collectives=True):
     """What the multi-rank line carries so that the first 8-GPU run verifies itself: the backend torch.distributed resolved, how many
     ranks an all-reduce of ones saw, which physical device every rank sits on (two ranks on one device under RCCL = a mis-launch:
-    fail loudly), and the two collectives of the path timed on their own -- all-gather of the normalised features (2 x [256, 512]
-    f32 per rank) and all-reduce of the frozen configuration's gradient bucket (9 MB) -- with HIP events around collective + wait."""
+    fail loudly), and (``time_collectives``) the two collectives of the path timed on their own -- all-gather of the normalised
+    features (2 x [256, 512] f32 per rank) and all-reduce of the frozen configuration's gradient bucket (9 MB) -- with HIP events
+    around collective + wait."""
     backend = dist.get_backend()
     ones = torch.ones(1, device=device)
     dist.all_reduce(ones)
@@ -454,16 +460,18 @@ def dist_selfcheck(device, world, rank, local_rank):
         t = torch.tensor([a.elapsed_time(b) / n * 1e3], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return round(float(t.item()), 1)
-    feat = torch.randn(2 * PER_GPU_BATCH, EMBEDDING_DIM, device=device)
-    gathered = torch.empty(world * 2 * PER_GPU_BATCH, EMBEDDING_DIM, device=device)
-    bucket = torch.randn(9 * 1024 * 1024 // 4, device=device)
-    out = {"backend": backend, "ranks_seen": int(ones.item()), "ranks": seen, "shared_devices": dup,
-           "allgather_us": timed(lambda: dist.all_gather_into_tensor(gathered, feat)),
-           "allreduce_us": timed(lambda: dist.all_reduce(bucket)),
-           "collectives_note": "max over ranks of the HIP-event time per call (collective + the current stream's wait for it), 20 calls "
-                               "back to back: all-gather of 2 x [256, 512] f32 features per rank; all-reduce of a 9 MB f32 gradient bucket"}
+    out = {"backend": backend, "ranks_seen": int(ones.item()), "ranks": seen, "shared_devices": dup}
     if out["ranks_seen"] != world:
         raise SystemExit(f"bench.py: an all-reduce of ones over {world} ranks returned {out['ranks_seen']}")
+    if time_collectives:
+        feat = torch.randn(2 * PER_GPU_BATCH, EMBEDDING_DIM, device=device)
+        gathered = torch.empty(world * 2 * PER_GPU_BATCH, EMBEDDING_DIM, device=device)
+        bucket = torch.randn(9 * 1024 * 1024 // 4, device=device)
+        out.update({"allgather_us": timed(lambda: dist.all_gather_into_tensor(gathered, feat)),
+                    "allreduce_us": timed(lambda: dist.all_reduce(bucket)),
+                    "collectives_note": "max over ranks of the HIP-event time per call (collective + the current stream's wait for it), "
+                                        "20 calls back to back: all-gather of 2 x [256, 512] f32 features per rank; all-reduce of a 9 MB "
+                                        "f32 gradient bucket"})
     return out
 
 
@@ -568,10 +576,11 @@ def write_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
 
 
 def measure(cfg, precision, batch_size, steps, warmup, device, world, rank, *, roofline=True, parity=True, yardstick=False,
-            seed=None, dump=False):
+            tail=True, seed=None, dump=False):
     """One benchmark configuration end to end: build the module, (parity check), warm up, time ``steps`` steps between
-    barriers, (instrumented passes for the roofline).  -> dict of results (rank-local; ``elapsed`` is the max over ranks).
-    ``dump``: rank 0 also returns what the last timed step computed (``step_outputs``) under ``outputs``."""
+    barriers, (instrumented passes for the roofline), (the trainable tail timed on its own).  -> dict of results (rank-local;
+    ``elapsed`` is the max over ranks).  ``dump``: rank 0 also returns what the last timed step computed (``step_outputs``) under
+    ``outputs``."""
     from multimodal import _hip as H
     from multimodal import parallel
     lit, ve, opt = build_model(cfg, device, precision)
@@ -635,6 +644,8 @@ def measure(cfg, precision, batch_size, steps, warmup, device, world, rank, *, r
     #    what torch's own autocast(bf16) does on the same weights and batch -- the yardstick for the bf16 figure.
     # The ResNeXt trunk stores its raw convolution outputs centred on calibrated batch means (resnext.py): the calibration is
     # done on ANOTHER batch of the same distribution first, as in a training run (the calibration batch is not the evaluated one).
+    # The default line's structured_parity drops the centres again, so there -- as in a run without these checks -- the first
+    # warm-up step calibrates them on the benchmark batch: the timed steps compute the same with and without --full.
     if parity and batch_size <= 1024:
         set_trunk_streams(0)
         par = {}
@@ -845,7 +856,7 @@ def measure(cfg, precision, batch_size, steps, warmup, device, world, rank, *, r
     res["hbm_peak_gb"] = round(torch.cuda.max_memory_allocated(device) / 1e9, 2)
     set_trunk_streams(0)
     torch.cuda.synchronize()
-    if world == 1 and precision != "32" and batch_size <= 1024:
+    if tail and world == 1 and precision != "32" and batch_size <= 1024:
         # the trainable TAIL on its own (round 5): the frozen trunk replaced by its cached output, nothing else on the GPU -- fc / head,
         # text encoder forward + backward, L2 normalise, logits, InfoNCE forward + backward, AdamW.  Event-timed per step; launches =
         # every device activity torch's profiler sees in a step (library kernels, torch's own kernels, device-to-device copies)
@@ -957,10 +968,16 @@ def main(argv=None):
     ap.add_argument("--config", default="c2", choices=["c2", "c4", "c5", "c4p14"])
     ap.add_argument("--batch", default=None, help="per-GPU batch: a number, or 'auto' = as many pairs as fit the free HBM (frozen-ViT "
                                                   "configurations: ~5 MB per pair, capped at 16384); default 256")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the bounded sub-records of the default C2 line (fp32 parity mode, C4, C5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: parity against the fp32 mode and torch, roofline "
+                         "and per-kernel times, the trainable tail, the sub-records of the default C2 line, the CPU baseline, the "
+                         "collectives of a multi-rank run on their own")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline passes")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity checks")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the bounded sub-records of the default C2 line (fp32 parity mode, C4, C5, C4 at patch 14, "
+                         "--finetune_cnn)")
     ap.add_argument("--precision", default=None, choices=["bf16", "32", "fp8"])
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
@@ -988,7 +1005,7 @@ def main(argv=None):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend=backend)
-        selfcheck = dist_selfcheck(device, world, rank, local_rank)
+        selfcheck = dist_selfcheck(device, world, rank, local_rank, time_collectives=a.full)
 
     cfg = a.config
     precision = a.precision or ("fp8" if cfg == "c5" else "bf16")
@@ -1010,13 +1027,14 @@ def main(argv=None):
     steps = a.steps if a.steps is not None else (50 if batch_size <= 1024 else 5)
     warmup = a.warmup if a.warmup is not None else (10 if batch_size <= 1024 else 2)
     default_line = cfg == "c2" and a.precision is None and a.batch in (None, "") and world == 1
-    r = measure(cfg, precision, batch_size, steps, warmup, device, world, rank, roofline=not a.no_roofline, parity=not a.no_parity,
-                yardstick=default_line and not a.no_parity, dump=a.dump_outputs is not None)
+    parity = a.full and not a.no_parity
+    r = measure(cfg, precision, batch_size, steps, warmup, device, world, rank, roofline=a.full and not a.no_roofline, parity=parity,
+                yardstick=default_line and parity, tail=a.full, dump=a.dump_outputs is not None)
     if "outputs" in r:
         write_outputs(r.pop("outputs"), a.dump_outputs)
 
     extras = {}
-    if default_line and not a.no_extras:
+    if default_line and a.full and not a.no_extras:
         # bounded sub-records (>= 10 timed steps each at 256 pairs): the C2 step in the mode that meets the 1e-3 logits gate
         # (exact-fp32 MFMA / fp32 storage), and BASELINE configs[3] / [4] on one GPU, each with its own roofline and parity
         sub_steps = max(10, min(steps, 20))
@@ -1066,7 +1084,7 @@ def main(argv=None):
             line["tail_note"] = ("the step with the frozen trunk replaced by its cached output (fc / head, text encoder, loss, backward, "
                                  "AdamW), nothing else on the GPU; tail_launches_per_step = device activities torch.profiler sees per step")
         line.update(extras)
-        if world == 1 and not a.no_cpu_baseline and cfg == "c2":
+        if world == 1 and a.full and not a.no_cpu_baseline and cfg == "c2":
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if world > 1:

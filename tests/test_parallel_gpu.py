@@ -242,14 +242,14 @@ def test_trainer_fit_local_negatives_averages_gradients(tmp_path):
 
 
 def test_bench_spawns_its_own_ranks(tmp_path):
-    """``python bench.py --gpus 2`` outside torch.distributed.run starts two fresh ranks itself (before touching the GPU) and
-    rank 0 prints the one JSON line with the whole-job throughput."""
+    """``python bench.py --gpus 2 --full`` outside torch.distributed.run starts two fresh ranks itself (before touching the GPU)
+    and rank 0 prints the one JSON line with the whole-job throughput, the parity figures and the collectives' timings."""
     import json
     env = dict(os.environ)
     env.update(CVCL_DIST_BACKEND="gloo", CVCL_TRUNK_STREAMS="1")          # two ranks share this box's one GPU
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

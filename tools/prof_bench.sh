@@ -7,6 +7,6 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/prof_$CFG
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O -o $CFG --output-format csv -- python3 $R/bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-extras "$@" > $O/bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O -o $CFG --output-format csv -- python3 $R/bench.py --config $CFG --steps 10 --warmup 3 --full --no-cpu-baseline --no-parity --no-extras "$@" > $O/bench.log 2>&1
 find $O -name "*kernel_stats.csv" | head -3
 tail -1 $O/bench.log | cut -c1-200

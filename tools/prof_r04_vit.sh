@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/r04
 mkdir -p $O; rm -rf $O/c4 $O/c4p14 $O/c5
 cd /tmp && export TMPDIR=/tmp
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-extras"
+B="--steps 10 --warmup 3 --full --no-cpu-baseline --no-parity --no-extras"
 for c in c4 c4p14 c5; do
   CVCL_VIT_TRUNK_STREAMS=1 rocprofv3 --kernel-trace --stats -d $O/$c -o $c --output-format csv -- python3 $R/bench.py --config $c $B > $O/$c.log 2>&1
 done

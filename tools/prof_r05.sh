@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/r05
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-extras"
+B="--steps 10 --warmup 3 --full --no-cpu-baseline --no-parity --no-extras"
 rocprofv3 --kernel-trace --stats -d $O/c2 -o c2 --output-format csv -- python3 $R/bench.py $B > $O/c2.log 2>&1
 CVCL_TRUNK_STREAMS=1 rocprofv3 --kernel-trace --stats -d $O/c2_1s -o c2 --output-format csv -- python3 $R/bench.py $B > $O/c2_1s.log 2>&1
 for c in c4 c4p14 c5; do
