@@ -37,13 +37,10 @@
  *    CVCL_CENTRED_STORAGE   on       plain (un-centred) bf16 storage of the raw convolution outputs (the round-2 numerics)
  *    CVCL_GEMM8W            on       cvcl_gemm never selects the 8-wave 256 x 256 kernel (everything on the 128 x 128 kernels)
  *    CVCL_GEMM_PRO          on       cvcl_gemm refuses the BN-prologue kernel (callers normalise the operand themselves)
- *    CVCL_F32_TILED         on       fp32 parity mode: the direct (one thread per output) stem / grouped-conv kernels
  *    CVCL_FINALIZE_ON_LOAD  on       bf16 train-mode trunk: partial rows + a cvcl_bn_finalize launch behind EVERY convolution (the launch
  *                                    sequence of rounds 1-5) instead of accumulated statistics that the consumer of the raw tensor turns
  *                                    into its channels' affine itself ("BatchNorm accumulators" below; tests/test_finalize_on_load_gpu.py)
- *  Experiment switches of earlier rounds (CVCL_FUSED_TAIL_STAGES, CVCL_CONV3_PRO_STAGES, CVCL_DS_RECOMPUTE,
- *  CVCL_PRO_DEPTH, CVCL_GCONV_LDS_KB, CVCL_GEMM_MINW, CVCL_GEMM_GLDS, CVCL_GCONV_WGRAD_BAND) exist only in a library built with
- *  -DCVCL_LAB (tools/README.md); the kernel-variant switches of the 8-wave GEMM live in tools/gemm_lab/.
+ *  The kernel-variant switches of the 8-wave GEMM live in tools/gemm_lab/.
  */
 #ifndef CVCL_HIP_H
 #define CVCL_HIP_H

@@ -22,7 +22,7 @@ ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"] + os.environ.get("CVCL_EXTRA_FLAGS", "").split()
-# experiments: CVCL_EXTRA_FLAGS=-DCVCL_PLAIN_STORES CVCL_LIB_SUFFIX=_plain python build.py -> lib/libcvcl_hip_plain.so ($CVCL_HIP_LIB)
+# a second library next to the product one: CVCL_LIB_SUFFIX=_prev python build.py -> lib/libcvcl_hip_prev.so ($CVCL_HIP_LIB)
 SUFFIX = os.environ.get("CVCL_LIB_SUFFIX", "")
 if SUFFIX:
     LIB = os.path.join(LIBDIR, f"libcvcl_hip{SUFFIX}.so")

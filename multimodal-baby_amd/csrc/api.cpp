@@ -22,15 +22,6 @@ bool cvcl_env_on(const char* name) {
     const char* e = getenv(name);
     return !(e && e[0] == '0');
 }
-int cvcl_lab_int(const char* name, int dflt) {
-#ifdef CVCL_LAB
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
 
 // co-scheduling hint for the one-workgroup-per-CU GEMM kernels (cvcl_hip.h): how many CUs a launch may fill; 0 = all
 static int g_gemm_cu_share = 0;

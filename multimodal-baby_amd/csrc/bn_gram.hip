@@ -34,12 +34,6 @@
 
 namespace {
 
-// phase ablation for timing studies (build option, as in resnext.hip's grouped convolution): 1 no BN math, 2 no MFMA loop, 4 no column
-// sums, 8 no LDS staging writes
-#ifndef CVCL_GRAM_ABLATE
-#define CVCL_GRAM_ABLATE 0
-#endif
-constexpr int GP_ABL = CVCL_GRAM_ABLATE;
 constexpr int GP_PM = 64;                  // rows per tile
 constexpr int GP_MAXG = 256;               // workgroups (= partials)
 
@@ -121,16 +115,13 @@ __device__ __forceinline__ void gram_producer(const GramDev& p, char* smem, cons
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 unsigned y = araw[slot][i][e];
-                if constexpr (!(GP_ABL & 1)) {
-                    y = round2(__builtin_elementwise_fma(widen2(y), sc[e], sh[e]));
-                    y = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, y), floor2));
-                }
+                y = round2(__builtin_elementwise_fma(widen2(y), sc[e], sh[e]));
+                y = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, y), floor2));
                 y &= keep;
                 v[e] = y;
-                if constexpr (!(GP_ABL & 4)) csum[e] += widen2(y);
+                csum[e] += widen2(y);
             }
-            if constexpr (!(GP_ABL & 8)) *reinterpret_cast<u32x4*>(dst + r * PITCH + s_c * 16) = v;
-            else if (v[0] == 0x12345678u && v[1] == 0x9abcdef0u) *reinterpret_cast<u32x4*>(dst + r * PITCH + s_c * 16) = v;
+            *reinterpret_cast<u32x4*>(dst + r * PITCH + s_c * 16) = v;
         }
     };
     const int first = blockIdx.x, G = gridDim.x;
@@ -190,7 +181,7 @@ __device__ __forceinline__ void gram_consumer(const GramDev& p, char* smem, cons
     const int n = rounds * NPF;
     for (int t = 0; t < n; ++t) {
         __syncthreads();
-        if (t < my_tiles && !(GP_ABL & 2)) {
+        if (t < my_tiles) {
             const char* tb = smem + (t & 1) * ABUF + frag_off;
 #pragma unroll
             for (int k2 = 0; k2 < KS; ++k2) {
@@ -475,19 +466,13 @@ int cvcl_conv1x1_gram_src(const void* A, int lda, long M, int K, const float* a_
     d.CS = d.P + (size_t)GP_MAXG * T * 1024;
     double* out = (double*)(((uintptr_t)(d.CS + (size_t)GP_MAXG * K) + 15) & ~(uintptr_t)15);
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    // [lab: upper bounds -- after n calls the Gram launch / the reduce launch is skipped and the consumers read an earlier pass's G;
-    //  only meaningful on a repeated batch]
-    static const int skip_pro = cvcl_lab_int("CVCL_SKIP_GRAM_PRO_AFTER", 0), skip_red = cvcl_lab_int("CVCL_SKIP_GRAM_REDUCE_AFTER", 0);
-    static long calls = 0;
-    ++calls;
-    if (!(skip_pro > 0 && calls > skip_pro)) {
+    {
         CvclProfScope prof(stream, CVCL_K_GEMM_PRO);
-        rc = NT == 8 ? gram_launch<8>(d, grid, st) : NT == 4 ? gram_launch<4>(d, grid, st) : gram_launch<2>(d, grid, st);
+        const int rc = NT == 8 ? gram_launch<8>(d, grid, st) : NT == 4 ? gram_launch<4>(d, grid, st) : gram_launch<2>(d, grid, st);
         if (rc) return rc;
         CVCL_LAUNCH_CHECK();
     }
-    if (!(skip_red > 0 && calls > skip_red)) {
+    {
         CvclProfScope prof(stream, CVCL_K_BN_FINALIZE);
         const int n = T * 1024 + K;
         hipLaunchKernelGGL(gram_reduce_kernel, dim3(cvcl_div_up(n, 64)), dim3(256), 0, st, d.P, d.CS, grid, NT, out);
@@ -504,9 +489,6 @@ extern "C" int cvcl_bn_from_gram(const double* gram, int K, long count, const vo
                                  float* scale, float* shift, float* moments, int moments_ld, const float* centre, void* stream) {
     CVCL_CHECK_ARG(gram && W && gamma && beta && scale && shift && count > 0 && N > 0 && (K == 64 || K == 128 || K == 256) && ldw >= K,
                    "cvcl_bn_from_gram: bad args");
-    static const int skip_fg = cvcl_lab_int("CVCL_SKIP_FROM_GRAM_AFTER", 0);       // [lab: as above, the bn_from_gram launch]
-    static long fg_calls = 0;
-    if (skip_fg > 0 && ++fg_calls > skip_fg) return CVCL_OK;
     CvclProfScope prof(stream, CVCL_K_BN_FINALIZE);
 #define CVCL_FROM_GRAM(KK)                                                                                                                  \
     hipLaunchKernelGGL(bn_from_gram_kernel<KK>, dim3(cvcl_div_up(N, GF_CH)), dim3(1024), 0, (hipStream_t)stream, gram, 1.0 / (double)count, \

@@ -18,13 +18,10 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // thread-local last error text (cvcl_last_error)
 void cvcl_set_error(const char* fmt, ...);
 
-// Run-time switches (api.cpp holds the only getenv calls of the library).  The PRODUCT reads four environment variables -- the
-// table "Run-time switches" in include/cvcl_hip.h: cvcl_env_on(name) is false when $name starts with '0'.  Everything else that
-// earlier rounds could toggle is a LAB switch: cvcl_lab_int(name, default) reads $name only in a library built with -DCVCL_LAB
-// (tools/README.md) and is the constant `default` in the product build.
+// Run-time switches (api.cpp holds the only getenv call of the library): the four environment variables of the table
+// "Run-time switches" in include/cvcl_hip.h.  cvcl_env_on(name) is false when $name starts with '0'.
 int cvcl_gemm_cu_share();                                   // the value set by cvcl_set_gemm_cu_share (0 = all CUs)
 bool cvcl_env_on(const char* name);
-int cvcl_lab_int(const char* name, int dflt);
 
 // optional HIP-event timing of a launch (see cvcl_prof_enable in include/cvcl_hip.h)
 bool cvcl_prof_on();
@@ -159,15 +156,8 @@ __device__ __forceinline__ unsigned relu2(unsigned pair) {
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, pair), s16x2{0, 0}));
 }
 
-// streamed-out results: nontemporal by default (the L2 keeps the operands); -DCVCL_PLAIN_STORES builds the same kernels with
-// ordinary stores (experiment: does the consumer find the tensor in the Infinity Cache?)
-template <typename V> __device__ __forceinline__ void stream_store(V v, V* dst) {
-#ifdef CVCL_PLAIN_STORES
-    *dst = v;
-#else
-    __builtin_nontemporal_store(v, dst);
-#endif
-}
+// streamed-out results: nontemporal (the L2 keeps the operands)
+template <typename V> __device__ __forceinline__ void stream_store(V v, V* dst) { __builtin_nontemporal_store(v, dst); }
 
 // ---- wave / block reductions ---------------------------------------------------------------
 __device__ inline float wave_sum(float v) {

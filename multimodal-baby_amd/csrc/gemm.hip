@@ -122,8 +122,8 @@ __device__ __forceinline__ void split_hi_lo(float x, bf16_t& hi, bf16_t& lo) {
     lo = (bf16_t)(xfin ? x - (float)h : 0.f);
 }
 
-template <typename T, int PRO, bool LEAN, int MINW, int TR = 0>
-__global__ __launch_bounds__(256, MINW) void gemm_kernel(GemmDev p) {
+template <typename T, int PRO, bool LEAN, int TR = 0>
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void gemm_kernel(GemmDev p) {
     static_assert(TR == 0 || (sizeof(T) == 4 && PRO == 0 && !LEAN), "K-major operands / split arithmetic: fp32, no prologue");
     constexpr bool SPLIT = (TR & 4) != 0;
     constexpr int EPC = ElemTraits<T>::kPerChunk;   // elements per 16-B chunk
@@ -834,32 +834,18 @@ __global__ __launch_bounds__(1024) void colsum_f32_kernel(const float* __restric
 
 // Resident workgroups per CU of each kernel variant (queried once); the persistent grid never exceeds what is
 // co-resident, so there is no second "wave" of workgroups and no tail.
-// bf16: the register allocator is asked for 2 or 3 workgroups per CU ($CVCL_GEMM_MINW, default 2: at 3 the
-// 168-VGPR budget spills ~25 registers to scratch); fp32 (parity mode) runs one workgroup per CU.
-template <typename T> int min_waves() {
-    if (sizeof(T) != 2) return 1;
-    static int v = 0;
-    if (!v) v = cvcl_lab_int("CVCL_GEMM_MINW", 2) == 3 ? 3 : 2;
-    return v;
-}
-
-template <typename T, int PRO, bool LEAN, int MINW>
-int resident_per_cu_v() {
+// bf16: the register allocator is asked for 2 workgroups per CU (at 3 the 168-VGPR budget spills ~25 registers to
+// scratch); fp32 (parity mode) runs one workgroup per CU.
+template <typename T, int PRO, bool LEAN>
+int resident_per_cu() {
     static int cached = 0;
     if (cached) return cached;
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)gemm_kernel<T, PRO, LEAN, MINW>, 256,
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)gemm_kernel<T, PRO, LEAN>, 256,
                                                      gemm_lds_bytes<T>()) != hipSuccess || n < 1)
         n = 1;
     cached = n > 4 ? 4 : n;
     return cached;
-}
-template <typename T, int PRO, bool LEAN>
-int resident_per_cu() {
-    if constexpr (sizeof(T) == 2)
-        return min_waves<T>() == 3 ? resident_per_cu_v<T, PRO, LEAN, 3>() : resident_per_cu_v<T, PRO, LEAN, 2>();
-    else
-        return resident_per_cu_v<T, PRO, LEAN, 1>();
 }
 
 int num_cus() {
@@ -890,14 +876,14 @@ int grid_m_for(int M, int N, int capacity) {
 
 template <typename T> int grid_m_query(int M, int N);
 
-template <typename T, int PRO, bool LEAN, int MINW, int TR = 0>
-int launch_gemm_w(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
+template <typename T, int PRO, bool LEAN, int TR = 0>
+int launch_gemm_v(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
     const int gm = grid_m_query<T>(a->M, a->N);      // same capacity for every variant (see grid_m_query)
     if (a->stats) CVCL_CHECK_ARG(a->stats_rows == CVCL_STATS_ACCUMULATE || a->stats_rows >= gm, "cvcl_gemm: stats_rows %d < grid_m %d", a->stats_rows, gm);
     static CvclLdsAttr attr_set;
     constexpr int lds = gemm_lds_bytes<T>();
     if (!attr_set.ready()) {
-        if (hipFuncSetAttribute((const void*)gemm_kernel<T, PRO, LEAN, MINW, TR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+        if (hipFuncSetAttribute((const void*)gemm_kernel<T, PRO, LEAN, TR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
             cvcl_set_error("cvcl_gemm: cannot raise dynamic LDS limit to %d", lds);
             return CVCL_ELAUNCH;
         }
@@ -905,17 +891,9 @@ int launch_gemm_w(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
     }
     dim3 grid(gm, cvcl_div_up(a->N, BN));
     CvclProfScope prof(stream, sizeof(T) == 2 ? CVCL_K_GEMM : CVCL_K_GEMM_F32);
-    hipLaunchKernelGGL((gemm_kernel<T, PRO, LEAN, MINW, TR>), grid, dim3(256), lds, stream, d);
+    hipLaunchKernelGGL((gemm_kernel<T, PRO, LEAN, TR>), grid, dim3(256), lds, stream, d);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
-}
-
-template <typename T, int PRO, bool LEAN>
-int launch_gemm_v(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
-    if constexpr (sizeof(T) == 2)
-        return min_waves<T>() == 3 ? launch_gemm_w<T, PRO, LEAN, 3>(a, d, stream) : launch_gemm_w<T, PRO, LEAN, 2>(a, d, stream);
-    else
-        return launch_gemm_w<T, PRO, LEAN, 1>(a, d, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1190,8 +1168,7 @@ inline int pick_gemm8w(int dtype, const cvcl_gemm_args* a) {
     if ((long)cvcl_div_up(a->M, 256) * (a->N / 256) < 96) return -1;
     // bandwidth-bound shapes stay with the 128 x 128 kernel (two workgroups per CU keep more bytes in flight): layer-2 block-0
     // conv1, M 802816 x N 256 x K 256, measured 176 us there vs 191-197 us here; N K / (N + K) = flop per byte of A + C traffic
-    static const long min_intensity = cvcl_lab_int("CVCL_G8_MIN_INTENSITY", 170);
-    if ((long)a->N * a->K < min_intensity * (a->N + a->K)) return -1;
+    if ((long)a->N * a->K < 170L * (a->N + a->K)) return -1;
     const bool plain = !a->bias && !a->R && a->act == CVCL_ACT_NONE;
     if (a->stats) {
         if (!plain || (a->stats_rows != CVCL_STATS_ACCUMULATE && a->stats_rows < cvcl_gemm8w_stats_rows(a->M, a->N))) return -1;
@@ -1270,17 +1247,16 @@ int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
         if (pick_gemm_pro(CVCL_BF16, a)) return cvcl_gemm_pro(a, stream);
         const int e8 = pick_gemm8w(CVCL_BF16, a);
         if (e8 >= 0) return cvcl_gemm8w(e8, a, stream);
-        static const bool use_glds = cvcl_lab_int("CVCL_GEMM_GLDS", 1) != 0;
-        if (use_glds && a->c_scale) {                // Bottleneck tail epilogue: only the direct-to-LDS kernel implements it
+        if (a->c_scale) {                // Bottleneck tail epilogue: only the direct-to-LDS kernel implements it
             CVCL_CHECK_ARG(d.vec_in && d.vec_out && pro_kind(a) == 0 && a->K % 64 == 0 && a->N % BN == 0 && a->R && a->c_shift &&
                                !a->bias && !a->exp_scale && !a->stats && (a->r_scale == nullptr) == (a->r_shift == nullptr),
                            "cvcl_gemm: the c_scale epilogue needs bf16, K %% 64 == 0, N %% 128 == 0, a residual and no bias/stats");
             return launch_gemm_glds<2>(a, d, stream);
         }
-        if (use_glds && lean && pro_kind(a) == 0 && a->K % 64 == 0) return launch_gemm_glds<0>(a, d, stream);
+        if (lean && pro_kind(a) == 0 && a->K % 64 == 0) return launch_gemm_glds<0>(a, d, stream);
         // ViT / nn.Linear shapes: bias, activation, residual, no statistics
         const bool al = ((uintptr_t)a->bias & 15) == 0;
-        const bool lin_ok = use_glds && d.vec_in && d.vec_out && pro_kind(a) == 0 && a->K % 64 == 0 && a->N % BN == 0 && !a->exp_scale &&
+        const bool lin_ok = d.vec_in && d.vec_out && pro_kind(a) == 0 && a->K % 64 == 0 && a->N % BN == 0 && !a->exp_scale &&
                             !a->stats && al && !(a->gather_stride > 1);
         if (a->C_pre || a->G) {                          // training epilogues: only this kernel implements them
             CVCL_CHECK_ARG(lin_ok, "cvcl_gemm: the C_pre / G epilogues need bf16, K %% 64 == 0, N %% 128 == 0 and 16-byte aligned rows");
@@ -1306,8 +1282,7 @@ int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
         // fp32 MFMA kernel needs ~4.6 us per 64-deep K step per round of <= 256 tiles, whatever M and N are (4.2 with split
         // arithmetic: its K step is bound by the serial load -> LDS -> multiply structure at one wave per SIMD, not by the matrix
         // pipe); the 64 x 64 split kernel ~1 us per (tile, 32-deep K step) with ~4 workgroups per CU overlapping
-        static const bool split64_on = cvcl_lab_int("CVCL_SPLIT64", 1) != 0;
-        const bool split64_ok = split64_on && split && pro_kind(a) == 0 && !(a->gather_stride > 1) && !a->stats && !a->R && !a->centre && !a->exp_scale &&
+        const bool split64_ok = split && pro_kind(a) == 0 && !(a->gather_stride > 1) && !a->stats && !a->R && !a->centre && !a->exp_scale &&
                                 (a->act == CVCL_ACT_NONE || a->act == CVCL_ACT_RELU);
         const double t_small = (double)a->M * a->N * a->K / 13.4e6 + 5.0;
         const double t_mfma128 = 12.0 + (a->K / 64.0) * (split ? 4.2 : 4.6) * cvcl_div_up((long)cvcl_div_up(a->M, BM) * cvcl_div_up(a->N, BN), 256);
@@ -1339,13 +1314,13 @@ int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
         if (tr || split) {
             CVCL_CHECK_ARG(pro_kind(a) == 0, "cvcl_gemm: K-major operands take no prologue");
             switch (tr | (split ? 4 : 0)) {
-                case 1: return launch_gemm_w<float, 0, false, 1, 1>(a, d, stream);
-                case 2: return launch_gemm_w<float, 0, false, 1, 2>(a, d, stream);
-                case 3: return launch_gemm_w<float, 0, false, 1, 3>(a, d, stream);
-                case 4: return launch_gemm_w<float, 0, false, 1, 4>(a, d, stream);
-                case 5: return launch_gemm_w<float, 0, false, 1, 5>(a, d, stream);
-                case 6: return launch_gemm_w<float, 0, false, 1, 6>(a, d, stream);
-                default: return launch_gemm_w<float, 0, false, 1, 7>(a, d, stream);
+                case 1: return launch_gemm_v<float, 0, false, 1>(a, d, stream);
+                case 2: return launch_gemm_v<float, 0, false, 2>(a, d, stream);
+                case 3: return launch_gemm_v<float, 0, false, 3>(a, d, stream);
+                case 4: return launch_gemm_v<float, 0, false, 4>(a, d, stream);
+                case 5: return launch_gemm_v<float, 0, false, 5>(a, d, stream);
+                case 6: return launch_gemm_v<float, 0, false, 6>(a, d, stream);
+                default: return launch_gemm_v<float, 0, false, 7>(a, d, stream);
             }
         }
     }

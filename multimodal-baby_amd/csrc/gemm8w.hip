@@ -15,8 +15,6 @@ int g8_num_cus() {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
             n = 256;
-        const int cap = cvcl_lab_int("CVCL_G8_CUS", 0);      // (lab: run the 8-wave kernels on part of the chip)
-        if (cap > 0 && cap < n) n = cap;
     }
     const int share = cvcl_gemm_cu_share();                  // cvcl_set_gemm_cu_share: the host's co-scheduling hint
     return share > 0 && share < n ? share : n;
@@ -32,10 +30,9 @@ int g8_grid_m(int tiles_m, int ncol) {
     if (gm < 8) gm = 8;
     const int need = (tiles_m + 7) & ~7;
     if (gm > need) gm = need;
-    static const bool lean_on = cvcl_lab_int("CVCL_LEAN_GRID", 1) != 0;
     const int rounds = cvcl_div_up(tiles_m, gm);
     const int lean = (cvcl_div_up(tiles_m, rounds) + 7) & ~7;      // the smallest multiple of 8 with the same number of rounds
-    return lean_on && lean < gm ? lean : gm;
+    return lean < gm ? lean : gm;
 }
 
 template <int MI, int EPI, bool LNF = false, int ACT = CVCL_ACT_NONE>
@@ -63,10 +60,9 @@ int g8_launch(const g8w::Dev& d, int grid, hipStream_t stream) {
 struct G8Plan { int bm, grid; };
 
 int g8_lean(long total, int grid) {                          // the smallest grid (multiple of 8) with the same number of rounds
-    static const bool lean_on = cvcl_lab_int("CVCL_LEAN_GRID", 1) != 0;
     const long rounds = (total + grid - 1) / grid;
     const int lean = (int)(((total + rounds - 1) / rounds + 7) & ~7L);
-    return lean_on && lean < grid ? lean : grid;
+    return lean < grid ? lean : grid;
 }
 
 G8Plan g8_plan(int M, int ncol) {
@@ -88,8 +84,7 @@ int g8_superrow(int grid, int ncol) {
     const int cpx = grid >> 3;
     int sr = 8;
     if (ncol * sr < cpx) sr = cvcl_div_up(cpx, ncol);
-    static const int sr_lab = cvcl_lab_int("CVCL_G8_SUPERROW", 0);   // (lab: 0 = the rule above; 1 = the column-fastest list of rounds 2-4)
-    return sr_lab > 0 ? sr_lab : sr;
+    return sr;
 }
 
 int g8_linear(g8w::Dev d, const cvcl_gemm_args* a, hipStream_t st) {

@@ -281,11 +281,7 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(F8Dev p) {
                 mb = max(mb, (unsigned)__builtin_amdgcn_update_dpp(0, (int)mb, 0x4E, 0xf, 0xf, true));
                 const unsigned sb = mx_scale_byte(__uint_as_float(mb << 16));
                 if (m < p.M) {
-#ifdef CVCL_CVT_SCALE_MUL                                                    // (probe build: the instruction multiplies instead of dividing)
-                    const u32x2 w = bf16x8_to_fp8_scaled(vw, mx_inv_scale(sb));
-#else
                     const u32x2 w = bf16x8_to_fp8_scaled(vw, __uint_as_float(sb << 23));
-#endif
                     __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(p.C8 + (long)m * p.ldc8 + n));
                     if ((chunk & 3) == 0) p.c_bs[((long)(n >> 7) * p.M + m) * 4 + ((n >> 5) & 3)] = (unsigned char)sb;
                 }
@@ -565,7 +561,6 @@ extern "C" int cvcl_gemm_fp8_ex(const cvcl_gemm_fp8_args* x, void* stream) {
             const long cost = ((total + gg - 1) / gg) * hgt * (hgt == 192 ? 107 : 100);
             if (best < 0 || cost < best) { best = cost; bm = hgt; }
         }
-        { static const int force_bm = cvcl_lab_int("CVCL_F8_BM", 0); if (force_bm == 256 || force_bm == 192) bm = force_bm; }
         g.tiles_m = cvcl_div_up(M, bm);
         const long total = (long)g.tiles_m * g.ncol;
         const int grid8 = total < cus ? (int)((total + 7) & ~7L) : (cus & ~7);

@@ -492,20 +492,16 @@ extern "C" int cvcl_gemm_pro(const cvcl_gemm_args* a, void* stream) {
     const int mode = a->c_scale ? (a->A2 ? PRO_TAIL_DS : PRO_TAIL) : (a->C ? PRO_STORE : PRO_STATS);
     CvclProfScope prof(stream, CVCL_K_GEMM_PRO);
     hipStream_t st = (hipStream_t)stream;
-    // tiles of A in flight: 3 (K = 128) / 2 (K = 256: the register budget); $CVCL_PRO_DEPTH overrides (measured on C2: depth 1
-    // 1.502 ms per step over the 14 launches, default 1.471)
-    static const int depth = cvcl_lab_int("CVCL_PRO_DEPTH", 0);
-    if (mode == PRO_TAIL_DS) {                               // K = 128 only; two tiles of A and X in flight (the register budget)
+    // tiles of A in flight: 3 (K = 128) / 2 (K = 256: the register budget) (measured on C2: depth 1 1.502 ms per step over the
+    // 14 launches, depth 3 1.471)
+    if (mode == PRO_TAIL_DS)                                 // K = 128 only; two tiles of A and X in flight (the register budget)
         return pro_launch<4, PRO_TAIL_DS, 2>(d, grid, st);
-    }
     if (a->K == 128) {
-        const int dd = depth ? depth : 3;
-        if (mode == PRO_TAIL) return dd >= 3 ? pro_launch<4, PRO_TAIL, 3>(d, grid, st) : dd == 2 ? pro_launch<4, PRO_TAIL, 2>(d, grid, st) : pro_launch<4, PRO_TAIL, 1>(d, grid, st);
-        if (mode == PRO_STORE) return dd >= 3 ? pro_launch<4, PRO_STORE, 3>(d, grid, st) : dd == 2 ? pro_launch<4, PRO_STORE, 2>(d, grid, st) : pro_launch<4, PRO_STORE, 1>(d, grid, st);
-        return dd >= 3 ? pro_launch<4, PRO_STATS, 3>(d, grid, st) : dd == 2 ? pro_launch<4, PRO_STATS, 2>(d, grid, st) : pro_launch<4, PRO_STATS, 1>(d, grid, st);
+        if (mode == PRO_TAIL) return pro_launch<4, PRO_TAIL, 3>(d, grid, st);
+        if (mode == PRO_STORE) return pro_launch<4, PRO_STORE, 3>(d, grid, st);
+        return pro_launch<4, PRO_STATS, 3>(d, grid, st);
     }
-    const int dd = depth ? depth : 2;
-    if (mode == PRO_TAIL) return dd >= 2 ? pro_launch<8, PRO_TAIL, 2>(d, grid, st) : pro_launch<8, PRO_TAIL, 1>(d, grid, st);
-    if (mode == PRO_STORE) return dd >= 2 ? pro_launch<8, PRO_STORE, 2>(d, grid, st) : pro_launch<8, PRO_STORE, 1>(d, grid, st);
-    return dd >= 2 ? pro_launch<8, PRO_STATS, 2>(d, grid, st) : pro_launch<8, PRO_STATS, 1>(d, grid, st);
+    if (mode == PRO_TAIL) return pro_launch<8, PRO_TAIL, 2>(d, grid, st);
+    if (mode == PRO_STORE) return pro_launch<8, PRO_STORE, 2>(d, grid, st);
+    return pro_launch<8, PRO_STATS, 2>(d, grid, st);
 }

@@ -633,14 +633,12 @@ __global__ __launch_bounds__(256) void stem_tiled_f32_kernel(const float* __rest
 // output rows per thread (round 5): R vertically adjacent outputs share input rows -- 3 (2 R + 1) taps for R outputs instead of 9 R, and
 // (2 R + 1) / R instead of 3 input rows fetched per output row across the L2s (the counters had FETCH_SIZE at 1.5 x the input:
 // consecutive output rows belong to workgroups on different XCDs)
-#ifndef CVCL_POOL_ROWS
-#define CVCL_POOL_ROWS 2
-#endif
+constexpr int POOL_ROWS = 2;
 template <typename T>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const T* __restrict__ x, const float* __restrict__ scale,
                                                               const float* __restrict__ shift, T* __restrict__ y,
                                                               int B, int H, int W, int C) {
-    constexpr int R = CVCL_POOL_ROWS, NR = 2 * R + 1, NTAP = 3 * NR;
+    constexpr int R = POOL_ROWS, NR = 2 * R + 1, NTAP = 3 * NR;
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1, CC = C / 8;
     const int Hq = (Ho + R - 1) / R;
     const long total = (long)B * Hq * Wo * CC;
@@ -707,10 +705,7 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const T* __restric
 // grouped 3x3 convolution, pad 1, stride 1|2, NHWC raw in (BN+ReLU applied on load) -> NHWC raw out
 // ------------------------------------------------------------------------------------------------
 constexpr int GC_CS = 64;                  // channels per workgroup slab
-#ifndef CVCL_GC_PIXB
-#define CVCL_GC_PIXB 144
-#endif
-constexpr int GC_PIXB = CVCL_GC_PIXB;      // LDS bytes per staged pixel (128 B of channels + pad; an odd number of 16-byte slots)
+constexpr int GC_PIXB = 144;               // LDS bytes per staged pixel (128 B of channels + pad; an odd number of 16-byte slots)
 
 struct GconvDev {
     const void* x; const float* a_scale; const float* a_shift; const void* w; void* y; float* stats;
@@ -720,12 +715,6 @@ struct GconvDev {
     BnSrc src;       // src.acc != NULL: the input's BatchNorm affine is formed here from its producer's accumulators (finalize-on-load)
     int stats_acc;   // stats is an int64 accumulator [8][2][C] (cvcl_common.h), not partial rows
 };
-// Phase ablation for timing studies is a BUILD option (no run-time flag in the loop: the per-slot tests it needed cost branches in
-// every work item): -DCVCL_GCONV_ABLATE=<bits>, 1 skip the BN math, 2 skip the MFMA loop (and the stores), 4 skip the stores,
-// 8 skip the LDS staging writes -- e.g. CVCL_EXTRA_FLAGS=-DCVCL_GCONV_ABLATE=2 CVCL_LIB_SUFFIX=_abl2 python build.py.
-#ifndef CVCL_GCONV_ABLATE
-#define CVCL_GCONV_ABLATE 0
-#endif
 
 template <bool WIDE, int NPF, int NMT>
 __global__ __launch_bounds__(256, WIDE ? 2 : 3) void gconv_mfma_kernel(GconvDev p) {
@@ -737,7 +726,6 @@ __global__ __launch_bounds__(256, WIDE ? 2 : 3) void gconv_mfma_kernel(GconvDev 
     const int slab = blockIdx.y, c0 = slab * GC_CS;
     const int Wp = p.W + 2;                                       // staged row width incl. halo columns
     constexpr bool wide = WIDE;                                   // 32 channels per group (layer4) vs 4/8/16
-    constexpr int ABL = CVCL_GCONV_ABLATE;
     constexpr int KS = WIDE ? 9 : 5;
     // this wave's unit: 16 output channels [c0 + 16*wave, +16); for cg == 32 the unit's inputs are the
     // 32 channels of its group, else the same 16 channels (block-diagonal weights)
@@ -867,18 +855,17 @@ __global__ __launch_bounds__(256, WIDE ? 2 : 3) void gconv_mfma_kernel(GconvDev 
                 u32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    unsigned y = (ABL & 1) ? pf[i][e] : round2(__builtin_elementwise_fma(widen2(pf[i][e]), sc[e], sh[e]));
+                    unsigned y = round2(__builtin_elementwise_fma(widen2(pf[i][e]), sc[e], sh[e]));
                     if constexpr (decltype(RELU)::value) y = relu2(y);
                     v[e] = y & keep;
                 }
-                if (!(ABL & 8) && pi < npix_in) *reinterpret_cast<u32x4*>(smem + pi * GC_PIXB + s_chunk * 16) = v;
+                if (pi < npix_in) *reinterpret_cast<u32x4*>(smem + pi * GC_PIXB + s_chunk * 16) = v;
             }
         };
         if (relu_in) stage(std::true_type{});
         else stage(std::false_type{});
         __syncthreads();
         if (item + (int)gridDim.x < n_items) prefetch(item + gridDim.x);
-        if (ABL & 2) continue;
         // two independent m-tiles in flight per wave: their LDS reads and MFMA chains interleave
         const int rows_left = p.Ho - oy0;                            // (a last band may be partial)
 #pragma unroll
@@ -913,18 +900,16 @@ __global__ __launch_bounds__(256, WIDE ? 2 : 3) void gconv_mfma_kernel(GconvDev 
         // (16 B per lane).  Scattered 8-byte stores straight from the MFMA layout cost more than the whole
         // load + compute phases together (ablation in DESIGN.md).
         __syncthreads();
-        if (!(ABL & 4)) {
-            const int valid_rows = min(p.TH, p.Ho - oy0);
-            const int n_chunks = valid_rows * p.Wo * 8;
-            // chunk tid + 256 k of the band (pixel (tid >> 3) + 32 k, channels 8 (tid & 7) ..): the element offset inside the band's
-            // output rows is item-invariant up to the stride 32 C per k; only the band's base pointer changes per item
-            bf16_t* yb = y + ((long)b * p.Ho + oy0) * p.Wo * p.C + c0 + st_off;
-            const char* so = s_out + (tid >> 3) * GC_PIXB + (tid & 7) * 16;
+        const int valid_rows = min(p.TH, p.Ho - oy0);
+        const int n_chunks = valid_rows * p.Wo * 8;
+        // chunk tid + 256 k of the band (pixel (tid >> 3) + 32 k, channels 8 (tid & 7) ..): the element offset inside the band's
+        // output rows is item-invariant up to the stride 32 C per k; only the band's base pointer changes per item
+        bf16_t* yb = y + ((long)b * p.Ho + oy0) * p.Wo * p.C + c0 + st_off;
+        const char* so = s_out + (tid >> 3) * GC_PIXB + (tid & 7) * 16;
 #pragma unroll
-            for (int k = 0; k < NMT / 2; ++k) {                   // NMT * 16 pixels * 8 chunks / 256 threads
-                if (tid + 256 * k < n_chunks)
-                    *reinterpret_cast<bf16x8*>(yb + (long)k * 32 * p.C) = *reinterpret_cast<const bf16x8*>(so + k * 32 * GC_PIXB);
-            }
+        for (int k = 0; k < NMT / 2; ++k) {                   // NMT * 16 pixels * 8 chunks / 256 threads
+            if (tid + 256 * k < n_chunks)
+                *reinterpret_cast<bf16x8*>(yb + (long)k * 32 * p.C) = *reinterpret_cast<const bf16x8*>(so + k * 32 * GC_PIXB);
         }
     }
     // per-channel partial sums: reduce over the 16 pixel lanes; channel = c0 + wave*16 + kb*4 + e
@@ -1470,8 +1455,7 @@ extern "C" int cvcl_stem_conv7x7(int dtype, const float* x_nchw, const void* w_p
         auto lds_of = [&](int th) { return (size_t)(147 * 64 + 64 + 3 * (2 * th + 5) * (W + 6)) * 4; };
         int TH = Ho < 8 ? Ho : 8;
         while (TH > 1 && lds_of(TH) > 150 * 1024) --TH;
-        static const bool tiled_on = cvcl_env_on("CVCL_F32_TILED");
-        if (tiled_on && lds_of(TH) <= 150 * 1024) {
+        if (lds_of(TH) <= 150 * 1024) {
             static CvclLdsAttr attr;
             if (!attr.ready()) {
                 if (hipFuncSetAttribute((const void*)stem_tiled_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
@@ -1533,7 +1517,7 @@ extern "C" int cvcl_bn_relu_maxpool(int dtype, const void* x, const float* scale
     CVCL_CHECK_ARG(x && scale && shift && y && C % 8 == 0, "cvcl_bn_relu_maxpool: bad args");
     CvclProfScope prof(stream, CVCL_K_MAXPOOL);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const long total = (long)B * ((Ho + CVCL_POOL_ROWS - 1) / CVCL_POOL_ROWS) * Wo * (C / 8);          // a thread owns CVCL_POOL_ROWS output rows
+    const long total = (long)B * ((Ho + POOL_ROWS - 1) / POOL_ROWS) * Wo * (C / 8);          // a thread owns POOL_ROWS output rows
     const int grid = grid_for(total, 256, 8192);
     if (dtype == CVCL_F32)
         hipLaunchKernelGGL(bn_relu_maxpool_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
@@ -1553,9 +1537,8 @@ GconvPlan gconv_plan(int B, int H, int W, int C, int stride) {
     // output rows per work item: staged input band + output band within ~52 KiB (3 workgroups per CU) and the
     // input pixel count within the 10 x 32 register-prefetch slots of the kernel
     auto bytes = [&](int th) { return (size_t)(((th - 1) * stride + 3) * Wp + th * Wo) * GC_PIXB; };
-    static const int lds_kb = cvcl_lab_int("CVCL_GCONV_LDS_KB", 52);
     int TH = Ho;
-    while (TH > 1 && (bytes(TH) > (size_t)lds_kb * 1024 || ((TH - 1) * stride + 3) * Wp > 10 * 32 || TH * Wo > 128)) TH = (TH + 1) / 2;
+    while (TH > 1 && (bytes(TH) > (size_t)52 * 1024 || ((TH - 1) * stride + 3) * Wp > 10 * 32 || TH * Wo > 128)) TH = (TH + 1) / 2;
     g.TH = TH;
     g.bands = cvcl_div_up(Ho, TH);
     g.rows_in = (TH - 1) * stride + 3;
@@ -1658,8 +1641,7 @@ static int gconv3x3_impl(int dtype, const void* x, const float* a_scale, const f
         auto lds_of = [&](int th) { return (size_t)(64 * 9 * cg + 64 + 64 * plane_p_of(th)) * 4; };
         int TH = Ho;
         while (TH > 1 && lds_of(TH) > 150 * 1024) --TH;
-        static const bool tiled_on = cvcl_env_on("CVCL_F32_TILED");
-        const bool tiled = tiled_on && C % 64 == 0 && (cg == 4 || cg == 8 || cg == 16 || cg == 32) && lds_of(TH) <= 150 * 1024 &&
+        const bool tiled = C % 64 == 0 && (cg == 4 || cg == 8 || cg == 16 || cg == 32) && lds_of(TH) <= 150 * 1024 &&
                            ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)a_scale & 15) == 0 && ((uintptr_t)a_shift & 15) == 0;
         if (tiled) {
             const int bands = cvcl_div_up(Ho, TH);
@@ -1819,13 +1801,8 @@ int bottleneck_fwd(const BlockCtx& c, int stage, bool first, int h, int wd, cons
     auto scale_of = [&](int l) { return aff + (size_t)l * 4096; };
     auto shift_of = [&](int l) { return aff + (size_t)l * 4096 + 2048; };
     auto centre_of = [&](int l) -> const float* { return cen ? cen + (size_t)l * 2048 : nullptr; };
-    // [lab: CVCL_SKIP_FINALIZE_AFTER=n -- upper bound on what removing the finalize chain could buy: after n finalize calls the
-    //  launches are skipped and the consumers read the (scale, shift) of an earlier pass; only meaningful on a repeated batch]
-    static const int skip_after = cvcl_lab_int("CVCL_SKIP_FINALIZE_AFTER", 0);
-    static long finalize_calls = 0;
     const int stats_cap = kMaxStatsRows;
     auto finalize = [&](int l, int rows, long count, int C) -> int {
-        if (skip_after > 0 && ++finalize_calls > skip_after) return CVCL_OK;
         if (training)
             return bn_finalize_launch(stats, rows, count, L[l].gamma, L[l].beta, L[l].running_mean, L[l].running_var,
                                       L[l].num_batches_tracked, c.momentum, c.eps, scale_of(l), shift_of(l), C,
@@ -1846,17 +1823,16 @@ int bottleneck_fwd(const BlockCtx& c, int stage, bool first, int h, int wd, cons
         return b;
     };
     static const bool fol_on = cvcl_env_on("CVCL_FINALIZE_ON_LOAD");               // (0: partial rows + a bn_finalize launch per layer)
-    const bool use_acc = fol_on && c.acc && training && dtype == CVCL_BF16 && skip_after == 0;
-    // (which forms this block takes -- the explanations sit at the launches below)
-    static const int pro_stages = cvcl_lab_int("CVCL_CONV3_PRO_STAGES", 2);
-    const bool pro = dtype == CVCL_BF16 && stage < pro_stages && (width == 128 || width == 256);
-    static const int fused_stages = cvcl_lab_int("CVCL_FUSED_TAIL_STAGES", 2);
-    const bool fused_tail = dtype == CVCL_BF16 && (stage < fused_stages || !training);
-    static const bool ds_recompute_on = cvcl_lab_int("CVCL_DS_RECOMPUTE", 1) != 0 && cvcl_env_on("CVCL_GEMM_PRO");
-    const bool ds_recompute = ds_recompute_on && first && stride == 1 && inplanes == 64 && fused_tail && pro && width == 128;
-    static const bool gram_on = cvcl_lab_int("CVCL_BN_GRAM", 1) != 0;
+    const bool use_acc = fol_on && c.acc && training && dtype == CVCL_BF16;
+    // Which forms this block takes (the explanations sit at the launches below):
+    //  pro         conv3 applies BN2 + ReLU on its operand load: layers 1-2 in bf16 (width 128 | 256, the K of gemm_pro.hip)
+    //  fused_tail  conv3's epilogue writes the block output: layers 1-2 in bf16, and every bf16 stage in eval mode
+    // so in train mode fused_tail == pro, and in eval mode pro implies fused_tail.
+    const bool pro = dtype == CVCL_BF16 && stage < 2;
+    const bool fused_tail = dtype == CVCL_BF16 && (stage < 2 || !training);
+    static const bool gemm_pro_on = cvcl_env_on("CVCL_GEMM_PRO");
+    const bool ds_recompute = gemm_pro_on && pro && first && stage == 0;      // layer1.0: stride 1, a K = 64 block input
     auto gram_stats = [&](int l, const void* A, int K, const float* a_scale, const float* a_shift, int a_relu, const BnSrc* src = nullptr) -> int {
-        if (skip_after > 0 && ++finalize_calls > skip_after) return CVCL_OK;          // [lab: the Gram launches go as well]
         const double* g = nullptr;
         int r = cvcl_conv1x1_gram_src(A, K, m_out, K, src ? nullptr : a_scale, src ? nullptr : a_shift, src, a_relu, c.gram_ws,
                                       cvcl_conv1x1_gram_workspace_bytes(256), &g, stream);
@@ -1869,33 +1845,30 @@ int bottleneck_fwd(const BlockCtx& c, int stage, bool first, int h, int wd, cons
     // sits in the Infinity Cache (after conv1 / conv2 / conv3 it no longer does).
     // layer1.0 (bf16, fused tail, BN-prologue kernel): the branch is a K = 64 product of the block input, recomputed inside the tail
     // pass (gemm_pro.hip PRO_TAIL_DS) instead of being written to HBM (411 MB at B = 256) and read back; its own launch shrinks to a
-    // Gram launch for its BN statistics (train mode) or disappears (eval mode).  $CVCL_DS_RECOMPUTE=0: the stored form.
-    const bool ds_gram = ds_recompute && training && gram_on;
+    // Gram launch for its BN statistics (train mode) or disappears (eval mode).
     // BN2 of layers 1-2: formed by the Gram launch (the first reader of relu(bn2(.)); it publishes the affine for the tail pass behind
     // it).  (Layers 3-4 keep partial rows + cvcl_bn_finalize for BN2 / BN3 / the downsample BatchNorm: their consumers are elementwise
     // passes whose workgroups touch every channel.  Re-blocked into channel-sliced 1024-thread workgroups that finalize on load they
     // cost 2-3 us more per launch than the launch they save once two passes overlap: profiles/r06_fol_ab.txt.)
-    static const int fol_gram_lab = cvcl_lab_int("CVCL_FOL_GRAM", 1);                // [lab: 0 = BN2 of layers 1-2 keeps its finalize launch]
-    const bool fol2 = use_acc && fused_tail && pro && gram_on && fol_gram_lab != 0;
+    const bool fol2 = use_acc && pro;
     if (first) {
-        if (ds_gram) {
-            if ((rc = gram_stats(ld, X, inplanes, nullptr, nullptr, 0))) return rc;
+        if (ds_recompute) {
+            if (training && (rc = gram_stats(ld, X, inplanes, nullptr, nullptr, 0))) return rc;
         } else {
             // downsample 1x1 stride s: X -> RD [m_out, outc]
             cvcl_gemm_args a = {};
-            a.A = X; a.W = L[ld].w; a.C = ds_recompute ? nullptr : RD;
+            a.A = X; a.W = L[ld].w; a.C = RD;
             a.M = (int)m_out; a.N = outc; a.K = inplanes; a.lda = inplanes; a.ldw = inplanes; a.ldc = outc;
             if (stride > 1) { a.gather_ho = ho; a.gather_wo = wo; a.gather_hi = h; a.gather_wi = wd; a.gather_stride = stride; }
             a.stats = training ? stats : nullptr; a.stats_rows = stats_cap;
             a.centre = centre_of(ld);
-            if (a.C || a.stats) { if ((rc = cvcl_gemm(dtype, &a, stream))) return rc; }
+            if ((rc = cvcl_gemm(dtype, &a, stream))) return rc;
             if ((rc = finalize(ld, a.stats ? cvcl_gemm_stats_rows(dtype, &a) : 0, m_out, outc))) return rc;
         }
     }
     // conv1 1x1: X [m_in, inplanes] -> R1 [m_in, width]
     int rows1 = 0;
-    static const int fol1_lab = cvcl_lab_int("CVCL_FOL_CONV1", 1);                   // [lab: 0 = BN1 keeps its finalize launch]
-    const bool fol1 = use_acc && fol1_lab != 0;
+    const bool fol1 = use_acc;
     {
         cvcl_gemm_args a = {};
         a.A = X; a.W = L[l1].w; a.C = R1;
@@ -1924,12 +1897,12 @@ int bottleneck_fwd(const BlockCtx& c, int stage, bool first, int h, int wd, cons
     if (!pro) {
         if ((rc = cvcl_bn_relu_apply(dtype, R2, scale_of(l2), shift_of(l2), R2, m_out, width, stream))) return rc;
     }
-    // Layers 1-2 in bf16 ($CVCL_FUSED_TAIL_STAGES leading stages, default 2): conv3 is HBM-bound and cheap there, so it runs
-    // twice -- a statistics-only pass (reads only the narrow operand), then a pass whose epilogue applies BN3 + identity /
-    // normalised downsample + ReLU and writes the block output -- instead of materialising raw3 and re-reading it in
-    // bn_add_relu (saves one write and one read of the wide tensor; results are bit-identical).  Both passes apply BN2 + ReLU
-    // on the operand load (gemm_pro.hip).  Measured per step at B = 256 (round 2, with gemm_pro): 1 stage 5.47 ms, 2 stages
-    // 5.46 ms and 1.2 GB less HBM traffic; layers 3-4 are MFMA-bound and keep the materialised form.
+    // Layers 1-2 in bf16: conv3 is HBM-bound and cheap there, so it runs twice -- a statistics-only pass (reads only the narrow
+    // operand), then a pass whose epilogue applies BN3 + identity / normalised downsample + ReLU and writes the block output --
+    // instead of materialising raw3 and re-reading it in bn_add_relu (saves one write and one read of the wide tensor; results are
+    // bit-identical).  Both passes apply BN2 + ReLU on the operand load (gemm_pro.hip).  Measured per step at B = 256 (round 2,
+    // with gemm_pro): 1 stage 5.47 ms, 2 stages 5.46 ms and 1.2 GB less HBM traffic; layers 3-4 are MFMA-bound and keep the
+    // materialised form.
     // In eval mode there is no statistics pass at all, so the fused tail is used in every stage.
     auto conv3_args = [&]() {
         cvcl_gemm_args a = {};
@@ -1941,18 +1914,17 @@ int bottleneck_fwd(const BlockCtx& c, int stage, bool first, int h, int wd, cons
     };
     // Train mode with the fused tail: BN3's batch statistics are needed before the product exists.  They come from the Gram matrix
     // of the operand (bn_gram.hip: sum y = w.s, sum y^2 = w^T G w -- one read of the narrow tensor, K <= 256 <= N / 2) instead of
-    // a statistics-only run of the whole GEMM.  [lab: CVCL_BN_GRAM=0 the statistics-only pass]
-    if (fused_tail && training && pro && gram_on) {
+    // a statistics-only run of the whole GEMM.  Without the fused tail, conv3 is materialised (with its statistics in train mode);
+    // eval mode with the fused tail launches nothing here (the affine came from the running stats up front).
+    if (fused_tail && training) {
         const BnSrc s2 = fol2 ? bn_src(l2, m_out, width) : BnSrc{};
         if ((rc = gram_stats(l3, R2, width, scale_of(l2), shift_of(l2), 1, fol2 ? &s2 : nullptr))) return rc;
-    } else if (!fused_tail || training) {
+    } else if (!fused_tail) {
         cvcl_gemm_args a = conv3_args();
-        a.C = fused_tail ? nullptr : R3;
+        a.C = R3;
         a.stats = training ? stats : nullptr; a.stats_rows = stats_cap;
-        if (a.C || a.stats) { if ((rc = cvcl_gemm(dtype, &a, stream))) return rc; }
+        if ((rc = cvcl_gemm(dtype, &a, stream))) return rc;
         if ((rc = finalize(l3, a.stats ? cvcl_gemm_stats_rows(dtype, &a) : 0, m_out, outc))) return rc;
-    } else {
-        if ((rc = finalize(l3, 0, m_out, outc))) return rc;              // eval mode: affine from the running stats
     }
     if (fused_tail) {
         cvcl_gemm_args a = conv3_args();
@@ -2100,20 +2072,13 @@ static int resnext50_fwd_impl(int dtype, int B, int H, int W, int training, cons
     const int srows = cvcl_stem_conv_stats_rows(dtype, B, H, W);
     char* X = buf[0];
     char* OUT = buf[1];
-    // [lab: CVCL_STEM_POOL=1] the fused stem (cvcl_stem_pool: statistics-only pass, then convolution + bn1 + relu + maxpool in one
-    // kernel; bit-identical, -1.0 GB of traffic per step at B = 256) -- measured and NOT the default (profiles/r05_ab_stem.txt, same
-    // box: C2 5.13 -> 5.22 ms): the stem convolution itself runs at 116 us for 30 GFLOP (LDS-gather-bound), so recomputing it costs
-    // more than the 411 MB it stops writing; the API and its bit-identity test stay for when the convolution gets faster.
-    static const bool stem_pool_on = cvcl_lab_int("CVCL_STEM_POOL", 0) != 0;
-    if (stem_pool_on && cvcl_stem_pool_supported(dtype, H, W)) {
-        if (training && (rc = cvcl_stem_conv7x7(dtype, x_nchw, layers[0].w, nullptr, stats, kMaxStatsRows, centres, B, H, W, stream))) return rc;
-        if ((rc = finalize(0, srows, (long)B * h * wd, 64))) return rc;
-        if ((rc = cvcl_stem_pool(dtype, x_nchw, layers[0].w, scale_of(0), shift_of(0), centres, X, B, H, W, stream))) return rc;
-    } else {
-        if ((rc = cvcl_stem_conv7x7(dtype, x_nchw, layers[0].w, RAW, stats, kMaxStatsRows, centres, B, H, W, stream))) return rc;
-        if ((rc = finalize(0, srows, (long)B * h * wd, 64))) return rc;
-        if ((rc = cvcl_bn_relu_maxpool(dtype, RAW, scale_of(0), shift_of(0), X, B, h, wd, 64, stream))) return rc;
-    }
+    // (The fused stem, cvcl_stem_pool -- a statistics-only pass, then convolution + bn1 + relu + maxpool in one kernel; bit-identical,
+    // -1.0 GB of traffic per step at B = 256 -- measured slower here: profiles/r05_ab_stem.txt, same box, C2 5.13 -> 5.22 ms.  The stem
+    // convolution itself runs at 116 us for 30 GFLOP (LDS-gather-bound), so recomputing it costs more than the 411 MB it stops
+    // writing; the API and its bit-identity test stay for when the convolution gets faster.)
+    if ((rc = cvcl_stem_conv7x7(dtype, x_nchw, layers[0].w, RAW, stats, kMaxStatsRows, centres, B, H, W, stream))) return rc;
+    if ((rc = finalize(0, srows, (long)B * h * wd, 64))) return rc;
+    if ((rc = cvcl_bn_relu_maxpool(dtype, RAW, scale_of(0), shift_of(0), X, B, h, wd, 64, stream))) return rc;
     h /= 2; wd /= 2;
     li = 1;
     BlockCtx ctx = {dtype, B, training, momentum, eps, stats, gram_ws, stream, nullptr};

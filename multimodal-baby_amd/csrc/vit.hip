@@ -351,10 +351,6 @@ __global__ __launch_bounds__(256) void attention_valu_kernel(const T* __restrict
 // (The first version ran one workgroup per 64 queries: V^T was rebuilt 4x per head with 2-byte LDS scatters, 4-way
 //  bank conflicted, and K was re-read from L2 by every wave: 440 us per ViT-B/16 layer at B = 256.)
 // ------------------------------------------------------------------------------------------------
-// phase ablation for timing studies (build option): 1 no query-tile loop (stage K / V only), 2 no K / V staging
-#ifndef CVCL_ATT_ABLATE
-#define CVCL_ATT_ABLATE 0
-#endif
 constexpr int ATT_TPAD_MAX = 288;      // keys padded to a multiple of 32 (T <= 288 covers ViT-B/14 at 224: 257)
 constexpr int ATT_THREADS = 512;       // 8 waves: the 7 query tiles of a 197-token ViT-B/16 head run in ONE round (4 waves needed two, the
                                        // second half empty), two workgroups per CU = 4 waves per SIMD
@@ -406,24 +402,22 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_mfma_kernel(const bf
     // K and V rows -> LDS, 8 chunks of 16 B per row, zeros beyond Tn.  All of a thread's loads (<= ATT_STAGE_IT pairs) are issued
     // before the first LDS write: the plain loop waited for each pair (a dependent L2 round trip per iteration, ~half of the
     // workgroup's lifetime at 197 tokens)
-    if (!(CVCL_ATT_ABLATE & 2)) {
-        u32x4 kv[ATT_STAGE_IT], vv[ATT_STAGE_IT];
+    u32x4 kv[ATT_STAGE_IT], vv[ATT_STAGE_IT];
 #pragma unroll
-        for (int it = 0; it < ATT_STAGE_IT; ++it) {
-            const int i = tid + it * ATT_THREADS;
-            const int jc = min(i >> 3, Tn - 1), c = i & 7;                       // clamped row: always a valid address, no branch
-            kv[it] = *reinterpret_cast<const u32x4*>(base + (long)jc * 3 * D + D + hh * 64 + c * 8);
-            vv[it] = *reinterpret_cast<const u32x4*>(base + (long)jc * 3 * D + 2 * D + hh * 64 + c * 8);
-        }
+    for (int it = 0; it < ATT_STAGE_IT; ++it) {
+        const int i = tid + it * ATT_THREADS;
+        const int jc = min(i >> 3, Tn - 1), c = i & 7;                       // clamped row: always a valid address, no branch
+        kv[it] = *reinterpret_cast<const u32x4*>(base + (long)jc * 3 * D + D + hh * 64 + c * 8);
+        vv[it] = *reinterpret_cast<const u32x4*>(base + (long)jc * 3 * D + 2 * D + hh * 64 + c * 8);
+    }
 #pragma unroll
-        for (int it = 0; it < ATT_STAGE_IT; ++it) {
-            const int i = tid + it * ATT_THREADS;
-            const int j = i >> 3, c = i & 7;
-            if (i < Tpad * 8) {
-                const u32x4 z = {0u, 0u, 0u, 0u};
-                *reinterpret_cast<u32x4*>(sK + j * ATT_KP + c * 16) = j < Tn ? kv[it] : z;
-                *reinterpret_cast<u32x4*>(sV + j * ATT_VP + c * 16) = j < Tn ? vv[it] : z;
-            }
+    for (int it = 0; it < ATT_STAGE_IT; ++it) {
+        const int i = tid + it * ATT_THREADS;
+        const int j = i >> 3, c = i & 7;
+        if (i < Tpad * 8) {
+            const u32x4 z = {0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4*>(sK + j * ATT_KP + c * 16) = j < Tn ? kv[it] : z;
+            *reinterpret_cast<u32x4*>(sV + j * ATT_VP + c * 16) = j < Tn ? vv[it] : z;
         }
     }
     __syncthreads();
@@ -434,7 +428,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_mfma_kernel(const bf
     const int l15 = lane & 15;
     const int v_lane_off = (4 * h + (l15 >> 2)) * ATT_VP + (((lane >> 4) & 1) * 16 + (l15 & 3) * 4) * 2;
 
-    for (int qt = wave; qt < ((CVCL_ATT_ABLATE & 1) ? 0 : nqt); qt += ATT_THREADS / 64) {
+    for (int qt = wave; qt < nqt; qt += ATT_THREADS / 64) {
         const int q0 = qt * 32;
         const int qrow = min(q0 + l31, Tn - 1);
         bf16x8 qf[4];
@@ -810,8 +804,6 @@ template <bool MX>
 int launch_attention_mfma(const void* qkv, void* out, void* out8, void* out_bs, float* lse, int B, int T, int heads, float scale,
                           hipStream_t s) {
     const int nt = (T + 31) / 32;                            // the two-pass form for the token counts of ViT patch 16 / 14 at 224 x 224
-    static const bool two_pass = cvcl_lab_int("CVCL_ATT_TWOPASS", 1) != 0;
-    if (!two_pass) return launch_attention_mfma_n<MX, 0>(qkv, out, out8, out_bs, lse, B, T, heads, scale, s);
     // Measured (same box, B = 256, 12 layers): 257 tokens (one workgroup per CU: 97 KB of K / V, nobody to overlap with) 2.47 -> 2.13 ms;
     // 197 tokens (two workgroups per CU overlap each other's VALU and MFMA phases) 1.23 -> 1.44 ms: the online loop stays there
     if (nt == 9) return launch_attention_mfma_n<MX, 9>(qkv, out, out8, out_bs, lse, B, T, heads, scale, s);
@@ -850,11 +842,6 @@ extern "C" int cvcl_attention(int dtype, const void* qkv, const int64_t* key_tok
                               int head_dim, float scale, void* stream) {
     CVCL_CHECK_DTYPE(dtype, "cvcl_attention");
     CVCL_CHECK_ARG(qkv && out && B > 0 && T > 0 && heads > 0 && head_dim > 0 && head_dim <= 128, "cvcl_attention: bad args");
-    // [lab: CVCL_SKIP_ATTENTION_AFTER=n -- what the image encoder's attention launches cost the STEP: after n calls they are skipped
-    //  (timing only: the blocks then multiply whatever the output buffer holds)]
-    static const int skip_after = cvcl_lab_int("CVCL_SKIP_ATTENTION_AFTER", 0);
-    static long calls = 0;
-    if (skip_after > 0 && T > 32 && ++calls > skip_after) return CVCL_OK;
     CvclProfScope prof(stream, CVCL_K_ATTENTION);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == CVCL_BF16 && head_dim == 64 && !key_tok && T > 32 && T <= ATT_TPAD_MAX) {   // T <= 32: generic kernel below

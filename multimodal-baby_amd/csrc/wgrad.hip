@@ -695,10 +695,9 @@ extern "C" int cvcl_gconv3x3_wgrad(const void* x, const void* dy, float* dw, int
     // both forms read 16-byte chunks of x and dy (rows of C % 128 == 0 channels are whole chunks): as cvcl_gemm_tn, refused up front
     CVCL_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0, "cvcl_gconv3x3_wgrad: bf16 operands x and dy need 16-byte alignment");
     hipStream_t st = (hipStream_t)stream;
-    // one pass over the operands with all nine taps (band kernel) when a band fits the LDS; $CVCL_GCONV_WGRAD_BAND=0: the tap-at-a-time form
-    static const bool band_on = cvcl_lab_int("CVCL_GCONV_WGRAD_BAND", 1) != 0;
+    // one pass over the operands with all nine taps (band kernel) when a band fits the LDS; otherwise the tap-at-a-time form
     const GwPlan gw = gw_plan(B, H, W, C, stride);
-    if (band_on && gw.ok && cg <= 32 && 32 % cg == 0) {
+    if (gw.ok && cg <= 32 && 32 % cg == 0) {
         if (workspace_bytes < gw.ws) {
             cvcl_set_error("cvcl_gconv3x3_wgrad: workspace too small");
             return CVCL_EWORKSPACE;

@@ -1,5 +1,4 @@
-"""Timing of cvcl_attention alone at the C4 shapes (B = 256, 12 heads x 64; 197 and 257 tokens), for phase-ablation builds of the library
-(-DCVCL_ATT_ABLATE=<bits>, csrc/vit.hip) selected with CVCL_HIP_LIB."""
+"""Timing of cvcl_attention alone at the C4 shapes (B = 256, 12 heads x 64; 197 and 257 tokens); CVCL_HIP_LIB selects the library."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "multimodal-baby_amd"))
 from multimodal import _hip as H

@@ -1,7 +1,4 @@
-"""Timing of the grouped-conv kernel on the trunk's shapes.  Phase ablation is a build option of the library
-(-DCVCL_GCONV_ABLATE=<bits>, see csrc/resnext.hip): build a variant with
-    CVCL_EXTRA_FLAGS=-DCVCL_GCONV_ABLATE=2 CVCL_LIB_SUFFIX=_abl2 python multimodal-baby_amd/build.py
-and run this script with CVCL_HIP_LIB=multimodal-baby_amd/lib/libcvcl_hip_abl2.so."""
+"""Timing of the grouped-conv kernel on the trunk's shapes; CVCL_HIP_LIB selects the library."""
 import os, sys, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "multimodal-baby_amd"))
 from multimodal import _hip as H

@@ -1,4 +1,4 @@
-"""cvcl_gconv3x3_wgrad on the trunk's shapes at B = 256 (bf16): time per call; CVCL_GCONV_WGRAD_BAND=0 runs the tap-at-a-time form."""
+"""cvcl_gconv3x3_wgrad on the trunk's shapes at B = 256 (bf16): time per call."""
 import os, sys, torch
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))

@@ -1,10 +1,10 @@
 """Per-layer table of the conv GEMM launches of the last profiled C2 step from a rocprofv3 --kernel-trace CSV
 (tools/prof_layers.sh): per block conv1, conv3 (layers 1-2: the Gram kernel that stands in for its statistics, csrc/bn_gram.hip),
 [downsample (layer1.0: Gram kernel, the product is recomputed inside the tail)], [layers 1-2: fused tail pass]."""
-import csv, os, sys
+import csv, sys
 trace = sys.argv[1]
 out = sys.argv[2] if len(sys.argv) > 2 else None
-fused = int(os.environ.get("CVCL_FUSED_TAIL_STAGES", "2"))
+fused = 2  # stages with the fused tail in train mode (csrc/resnext.hip)
 rows = list(csv.DictReader(open(trace)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 def is_conv_gemm(n):
