@@ -425,6 +425,27 @@ int cvcl_gelu_bf16(const void* u, const void* d_y, void* y, long n, void* stream
 /* backward of cvcl_vit_assemble_tokens: d_tok [B][T-1][D] bf16 = the patch rows of dh [B][T][D]; d_pos [T][D] fp32 = sum over
  * the batch (its row 0 is also d_cls)                                                                                     */
 int cvcl_vit_tokens_bwd(const void* dh, void* d_tok, float* d_pos, int B, int T, int D, void* stream);
+/* fp32 fine-tuning of the ViT (csrc/vit_f32_train.hip; Lightning's default precision "32" under autograd of
+ * vision_transformer_dino_mugs.py:87-149).  Every product on v_mfma_f32_32x32x2_f32 (exact fp32), no atomics, fixed-order
+ * reductions: deterministic.  Each entry returns CVCL_EINVAL before it enqueues anything on a null pointer, a bad shape or a
+ * limit it does not support.
+ * Attention forward for training (vit:106-130 softmax(q k^T scale) v): qkv [B][T][3][heads][64] fp32 -> out [B][T][heads*64]
+ * fp32 and lse [B][heads][T] fp32 in the log2 units of cvcl_attention_train.  head_dim 64, 32 < T <= 288, 16-byte aligned.   */
+int cvcl_attention_train_f32(const float* qkv, float* out, float* lse, int B, int T, int heads, int head_dim, float scale, void* stream);
+/* its backward (autograd of vit:106-130): d_qkv [B][T][3][heads][64] fp32, fully written; probabilities rebuilt from lse,
+ * D_i = sum dO O in fp32; a dQ kernel that owns queries and a dK / dV kernel that owns keys.  Limits as the forward.           */
+int cvcl_attention_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse, float* d_qkv, int B, int T, int heads,
+                           int head_dim, float scale, void* stream);
+/* LayerNorm backward on fp32 rows (autograd of nn.LayerNorm, vit:140/147): x, dy, add (nullable, dx's layout), dx fp32; partial
+ * [cvcl_layernorm_bwd_rows_partials(rows)][2][D] as cvcl_layernorm_bwd_rows (reduce with cvcl_colsum_f32).  D % 4 == 0, D <= 1024. */
+int cvcl_layernorm_bwd_rows_f32(const float* x, long x_row_stride, const float* gamma, const float* dy, long dy_row_stride, float eps,
+                                const float* add, float* dx, long dx_row_stride, float* partial, long rows, int D, void* stream);
+/* GELU (erf form, vit:99 nn.GELU) on fp32, the expression of cvcl_gemm's fp32 GELU epilogue: d_y == NULL -> y = gelu(u); else
+ * y = d_y * gelu'(u).  n % 4 == 0, 16-byte aligned.                                                                         */
+int cvcl_gelu_f32(const float* u, const float* d_y, float* y, long n, void* stream);
+/* cvcl_vit_tokens_bwd on fp32 (autograd of prepare_tokens, vit:232-243): d_tok [B][T-1][D] fp32, d_pos [T][D] fp32 (batch sum,
+ * row 0 = d_cls).  D % 4 == 0.                                                                                                */
+int cvcl_vit_tokens_bwd_f32(const float* dh, float* d_tok, float* d_pos, int B, int T, int D, void* stream);
 /* x[b,l,:] = table[tok[b,l]] (+ pos[l]) (multimodal.py:496, 561-563) */
 int cvcl_embed_gather_pos(const float* table, const int64_t* tok, const float* pos, float* x, int B, int L, int E, int V,
                           void* stream);
@@ -509,6 +530,11 @@ int cvcl_gemm_tn(int dtype, const void* A, int lda, const void* B, int ldb, long
 size_t cvcl_gemm_tn_colsum_workspace_bytes(long M, int N, int K);
 int cvcl_gemm_tn_colsum(const void* A, int lda, const void* B, int ldb, long M, int N, int K, float* C, int k_keep, float* colsum,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* nn.Linear backward in one pass over dY, fp32 (autograd of the ViT linears, vit:92-94 / 113-115): C [N][k_keep] = (A^T B)[:, :k_keep],
+ * colsum [N] = column sums of A, on v_mfma_f32_32x32x2_f32; partial tiles over row chunks reduced in a fixed order (deterministic) */
+size_t cvcl_gemm_tn_colsum_f32_workspace_bytes(long M, int N, int K);
+int cvcl_gemm_tn_colsum_f32(const float* A, int lda, const float* B, int ldb, long M, int N, int K, float* C, int k_keep, float* colsum,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* grouped 3x3 (pad 1, stride 1|2) weight gradient, bf16 activations: dW [C][C/groups][3][3] f32 (reference OIHW); x and dy 16-byte aligned */
 size_t cvcl_gconv3x3_wgrad_workspace_bytes(int B, int H, int W, int C, int stride);
 int cvcl_gconv3x3_wgrad(const void* x, const void* dy, float* dw, int B, int H, int W, int C, int groups, int stride,

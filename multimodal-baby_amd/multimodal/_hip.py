@@ -175,6 +175,14 @@ SIGNATURES = {
     "cvcl_vit_tokens_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "cvcl_gemm_tn_colsum_workspace_bytes": (C.c_size_t, [C.c_long, _I, _I]),
     "cvcl_gemm_tn_colsum": (_I, [_P, _I, _P, _I, C.c_long, _I, _I, _P, _I, _P, _P, C.c_size_t, _P]),
+    # fp32 ViT fine-tuning (csrc/vit_f32_train.hip)
+    "cvcl_attention_train_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "cvcl_attention_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "cvcl_layernorm_bwd_rows_f32": (_I, [_P, C.c_long, _P, _P, C.c_long, _F, _P, _P, C.c_long, _P, C.c_long, _I, _P]),
+    "cvcl_gelu_f32": (_I, [_P, _P, _P, C.c_long, _P]),
+    "cvcl_vit_tokens_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "cvcl_gemm_tn_colsum_f32_workspace_bytes": (C.c_size_t, [C.c_long, _I, _I]),
+    "cvcl_gemm_tn_colsum_f32": (_I, [_P, _I, _P, _I, C.c_long, _I, _I, _P, _I, _P, _P, C.c_size_t, _P]),
     "cvcl_attention_mx": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "cvcl_gemm_fp8_mx": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     "cvcl_gemm_fp8_ex": (_I, [C.POINTER(GemmFp8Args), _P]),

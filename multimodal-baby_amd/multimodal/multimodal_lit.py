@@ -87,7 +87,8 @@ class MultiModalLitModel(LightningModule):
         parser.add_argument("--length_penalty_alpha", type=float, default=LENGTH_PENALTY_ALPHA)
 
     def set_precision(self, precision):
-        """Trainer ``--precision``: 'bf16' / '16' -> bf16 storage + bf16 MFMA trunk; '32' -> exact-fp32 parity mode;
+        """Trainer ``--precision``: 'bf16' / '16' -> bf16 storage + bf16 MFMA trunk; '32' -> exact-fp32 parity mode (also for
+        fine-tuning the ViT with --finetune_cnn: fp32 storage, fp32 MFMA products, vit_train.py);
         '32-split' -> fp32 storage with split-bf16 products in the ResNeXt trunk's convolutions and in the text linears
         (~fp32 numerics; refused for the ViT and with --finetune_cnn);
         'fp8' -> bf16 storage with e4m3 weights / activations in the ViT linears (BASELINE configs[4]; the ResNeXt trunk
