@@ -707,6 +707,38 @@ int cvcl_lstm_cell_tok(const float* gates, const float* G, const int64_t* tok, i
 int cvcl_lstm_cell_bwd_first(const float* gates_act, const float* c_save, const float* c0, const int64_t* len, const float* dh,
                              float* dc, float* d_gates, float* dh_carry, int B, int L, int Hd, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Nearest-neighbour searches between two frame sets (csrc/neighbors.hip).  Replace the torch compositions of the reference's
+ * leakage check analysis_cvcl/duplicates.py; neither writes a queries x base matrix.  Both validate everything before they enqueue
+ * anything (null pointers, Nq / Nb / D / C / HW out of range, strides below D, a workspace that is too small or not 16-byte aligned,
+ * one group array without the other: CVCL_EINVAL, cvcl_last_error names the argument), enqueue on the caller's stream only, use no
+ * atomics (partials per workgroup in the caller's workspace, merged in a fixed order: reproducible), and send ties to the LOWER index.
+ * NaN inputs are not supported.  Chunked base sets: call once per chunk with idx_offset = the chunk's first row and accumulate = 1
+ * from the second chunk on; the outputs then hold the running best (chunks in ascending order give the one-shot result bit for bit).
+ *
+ * cvcl_nn_cosine: F.cosine_similarity(a[:, None, :], b[None, :, :], dim=-1) + max / argmax over the base rows (duplicates.py:805-809
+ *   over all training frames, :576-577 + :604-605 per category).  q [Nq, D] f32 (row stride ldq >= D), base [Nb, D] f32 (row stride
+ *   ldb >= D); cos(i, j) = q_i . b_j / (max(|q_i|, eps) max(|b_j|, eps)) (torch: eps = 1e-8) -> best_cos [Nq] f32 = max_j,
+ *   best_idx [Nq] int64 = idx_offset + argmax_j.  q_group / base_group (int32 per row, both or neither): only pairs of equal group
+ *   are eligible -- the per-category search in one launch; a query without an eligible base row gets index -1 and -inf (or keeps
+ *   what it had, with accumulate).  Products are exact fp32 (v_mfma_f32_32x32x2_f32), summed in chains of 128 k that are then added
+ *   in fp32; norms and the final division in double, one rounding to fp32.  Zero rows give cosine 0.  CVCL_K_HEAD.
+ * cvcl_nn_l1_u8: torch.sum(torch.abs(eval_img - train_images), dim=(1, 2, 3)) + min / argmin (duplicates.py:993-1002) on 8-bit frames.
+ *   q [Nq, C, HW] uint8 planar, base [Nb, C, HW] uint8 (both 4-byte aligned; 16-byte aligned with HW % 16 == 0 for the wide loads),
+ *   w [C] double HOST values (read during the call).  Per pair and channel S_c = sum_p |q[c, p] - b[c, p]| as an exact integer
+ *   (v_sad_u8), d = S_0 w_0 + S_1 w_1 + ... in double, left to right, products and sums rounded separately -> best_dist [Nq] double
+ *   = min_j, best_idx [Nq] int64 = idx_offset + argmin_j (-1 and +inf without an eligible base frame), best_sums [Nq, C] uint32 = the
+ *   winner's S_c (may be NULL).  With w_c = 1 / (255 std_c) d is the reference's distance between ToTensor + Normalize frames (the
+ *   mean cancels), without the rounding of its 150 528 fp32 terms.  Limits: 1 <= C <= 4, HW % 4 == 0, HW 255 < 2^32.  CVCL_K_OTHER. */
+size_t cvcl_nn_cosine_workspace_bytes(int Nq, int Nb, int D);
+int cvcl_nn_cosine(const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, float eps, const int32_t* q_group,
+                   const int32_t* base_group, int64_t idx_offset, int accumulate, float* best_cos, int64_t* best_idx, void* workspace,
+                   size_t workspace_bytes, void* stream);
+size_t cvcl_nn_l1_u8_workspace_bytes(int Nq, int Nb, int C);
+int cvcl_nn_l1_u8(const uint8_t* q, const uint8_t* base, int Nq, int Nb, int C, int HW, const double* w, const int32_t* q_group,
+                  const int32_t* base_group, int64_t idx_offset, int accumulate, double* best_dist, int64_t* best_idx,
+                  uint32_t* best_sums, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

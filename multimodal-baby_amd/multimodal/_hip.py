@@ -207,6 +207,11 @@ SIGNATURES = {
     "cvcl_beam_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cvcl_lstm_cell_tok": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P]),
     "cvcl_lstm_cell_bwd_first": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    # nearest-neighbour searches (csrc/neighbors.hip)
+    "cvcl_nn_cosine_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "cvcl_nn_cosine": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, C.c_int64, _I, _P, _P, _P, _SZ, _P]),
+    "cvcl_nn_l1_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "cvcl_nn_l1_u8": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_double), _P, _P, C.c_int64, _I, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None
