@@ -708,6 +708,31 @@ int cvcl_lstm_cell_bwd_first(const float* gates_act, const float* c_save, const 
                              float* dc, float* d_gates, float* dh_carry, int B, int L, int Hd, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-word Grad-CAM of the captioning LM (csrc/caption_cam.hip).  Replaces the loop of the reference's
+ * analysis_tools/multimodal_visualization.py:26-41 -- one loss[0, step - 1].backward(retain_graph=True) per word and image -- by
+ * one multi-seed BPTT sweep: every (caption b, position p) is a seed row whose chain d loss[b, p] / d (h0, c0) runs over the saved
+ * gate activations of caption b.  The seed state dh, dc is seed-major ([L][B][Hd]: block p = the chains that start at position p),
+ * so the chains alive at step s (p >= s) are the contiguous tail from block s, and a step is this entry on that tail + one cvcl_gemm
+ * (dh <- d_gates W_hh + dh_carry, M = rows).  Nothing keeps a d_gates history: no weight gradient is wanted.
+ *
+ * cvcl_lstm_cell_bwd_seeds: the cell backward of step s on rows = B n_active seed rows (dh, dc, d_gates [rows, 4 Hd], dh_carry
+ *   [rows, Hd] all start at the tail's first row); row r reads gates_act / c_save (the [B, L, .] buffers cvcl_lstm_cell_train saved)
+ *   at row b L + s, b = r % B, and len[b].  Per element the arithmetic of cvcl_lstm_cell_bwd (bit for bit), with c_{-1} = c0 [B, Hd]
+ *   at s = 0 when c0 != NULL (cvcl_lstm_cell_bwd_first) and zeros otherwise; rows with len[b] <= s give d_gates = 0, dh_carry = dh
+ *   and keep dc.  d_out [B, L, Hd] (nullable): the first B rows JOIN at this step -- their dh is d_out[b L + s] where len[b] > s and 0
+ *   elsewhere, their dc is 0, and neither dh nor dc is read for them (no separate copy / clear launch).  dc is updated in place.
+ *   fp32, four hidden units per lane (16-byte loads and stores): Hd % 4 == 0 and every buffer 16-byte aligned.  Refused with
+ *   CVCL_EINVAL before anything is enqueued: null pointers, Hd, s outside [0, L), rows not a multiple of B or more than (L - s) B,
+ *   c0 at s > 0.  CVCL_K_LSTM.
+ * cvcl_l2norm_bwd_seeds: cvcl_l2norm_bwd for gradient rows that share an image's (y, norm): dy [K B, E] seed-major (row p B + b)
+ *   -> dx [B K, E] image-major (row b K + p, the target order of CVCL_GRADCAM_BLOCK_IMAGE), y [B, E], norm [B]; y = norm = NULL:
+ *   the reordering alone.  One launch for all K seeds (K launches of cvcl_l2norm_bwd otherwise).  dx must not alias dy.  CVCL_K_HEAD. */
+int cvcl_lstm_cell_bwd_seeds(const float* gates_act, const float* c_save, const float* c0, const int64_t* len, int s,
+                             const float* d_out, float* dh, float* dc, float* d_gates, float* dh_carry, int B, int L, int Hd, long rows,
+                             void* stream);
+int cvcl_l2norm_bwd_seeds(const float* y, const float* norm, const float* dy, float* dx, int B, int K, int E, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Nearest-neighbour searches between two frame sets (csrc/neighbors.hip).  Replace the torch compositions of the reference's
  * leakage check analysis_cvcl/duplicates.py; neither writes a queries x base matrix.  Both validate everything before they enqueue
  * anything (null pointers, Nq / Nb / D / C / HW out of range, strides below D, a workspace that is too small or not 16-byte aligned,

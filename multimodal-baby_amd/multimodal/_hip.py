@@ -207,6 +207,9 @@ SIGNATURES = {
     "cvcl_beam_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cvcl_lstm_cell_tok": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P]),
     "cvcl_lstm_cell_bwd_first": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    # per-word Grad-CAM of the captioning LM (csrc/caption_cam.hip)
+    "cvcl_lstm_cell_bwd_seeds": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, C.c_long, _P]),
+    "cvcl_l2norm_bwd_seeds": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
     # nearest-neighbour searches (csrc/neighbors.hip)
     "cvcl_nn_cosine_workspace_bytes": (_SZ, [_I, _I, _I]),
     "cvcl_nn_cosine": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, C.c_int64, _I, _P, _P, _P, _SZ, _P]),

@@ -5,7 +5,10 @@ plotting helpers :15-80).  The bodies are this repository's own.
 Device work runs on libcvcl_hip (csrc/gradcam.hip): ``gradCAM`` is the reference's one forward + backward per call (the
 backward reaches the hooked layer-4 map through the trunk's avgpool bridge, ``resnext._PooledFromMap``), and
 ``gradCAM_pairs`` is the batched form for the flat ResNeXt encoder -- one trunk pass, then every requested (image, target)
-map as one exact-fp32 MFMA contraction over the layer-4 map (cvcl_hip.h, "Grad-CAM").  The plotting helpers are host-side
+map as one exact-fp32 MFMA contraction over the layer-4 map (cvcl_hip.h, "Grad-CAM").  ``gradCAM_captions`` /
+``gradCAM_for_captioning_lm`` (reference analysis_tools/multimodal_visualization.py:9-49) give one map per word of a caption for the
+captioning LM: the per-word gradients of all captions come from one multi-seed BPTT sweep (csrc/caption_cam.hip) and feed the same
+contraction.  The plotting helpers are host-side
 numpy / matplotlib; matplotlib and scipy are imported only when a helper needs them."""
 from __future__ import annotations
 
@@ -17,6 +20,7 @@ import torch.nn as nn
 
 from . import _hip as H
 from . import ops
+from .multimodal_data_module import PAD_TOKEN_ID
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -206,6 +210,190 @@ def gradCAM_pairs(vision_model, images, targets, normalize_features=False, pairs
         fmap = hook.activation
     size = tuple(images.shape[2:]) if resize is True else resize
     return gradcam_from_features(fmap, features, resnet.fc.weight, targets, normalize_features, pairs, size)
+
+
+# ---- per-word maps of the captioning language model ----------------------------------------------------------------------
+
+MAX_CAPTION_LEN = 32                                       # the LSTM path's limit (text_train.transformer_text_train, ops.lstm_text)
+
+
+def _captioning_lstm_of(language_model):
+    """The text encoder behind ``language_model`` when it is the captioning one-layer uni-directional LSTM; refusals otherwise."""
+    te = getattr(language_model, "text_encoder", None)
+    if te is None or not hasattr(language_model, "output_layer"):
+        raise TypeError("expected a LanguageModel (text_encoder + output_layer)")
+    if getattr(te, "has_attention", False):
+        raise NotImplementedError("attention language models are outside the implemented path")
+    if not getattr(te, "captioning", False):
+        raise NotImplementedError("per-word Grad-CAM needs a captioning text encoder (--captioning: the LSTM starts from the image)")
+    lstm = getattr(te, "lstm", None)
+    if te.text_encoder != "lstm" or lstm is None or lstm.num_layers != 1 or lstm.bidirectional:
+        raise NotImplementedError("per-word Grad-CAM is defined for the one-layer uni-directional LSTM text encoder only")
+    return te
+
+
+def caption_seed_targets(features, language_model, y, y_len, normalize_features=False, eps=1e-12):
+    """-> targets [B (L-1), E] fp32, row b (L-1) + p = -d loss[b, p] / d f[b]: minus the gradient of the token-wise captioning loss
+    (``LanguageModel.calculate_ce_loss(y, y_len, image_features=n, tokenwise=True)``, n = f or F.normalize(f)) wrt the fc output
+    ``features`` [B, E], for every caption and position at once and without an autograd graph.  Zero rows where the label is <pad>.
+
+    One LSTM forward that saves gate activations and cell states, unit seeds through the output layer (the seeds are -1, so every
+    later quantity is already the negated one), then L - 1 steps of a triangular sweep -- one cvcl_lstm_cell_bwd_seeds launch and
+    one recurrent GEMM over all chains alive at that step -- and the connector / normalisation backward on all rows.  Always the
+    eval arithmetic: no dropout_i mask is drawn, whatever the modules' ``training`` flags say."""
+    te = _captioning_lstm_of(language_model)
+    if y.dim() != 2 or y_len.shape != (y.shape[0],) or features.shape[0] != y.shape[0]:
+        raise H.CvclError(f"shapes: features {tuple(features.shape)}, y {tuple(y.shape)}, y_len {tuple(y_len.shape)}")
+    B, L = y.shape
+    if L > MAX_CAPTION_LEN:
+        raise NotImplementedError(f"captions are at most {MAX_CAPTION_LEN} tokens on the LSTM path; got L = {L}")
+    if L < 2:
+        raise ValueError("a caption needs at least two tokens: position p predicts token p + 1")
+    for t in (features, y, y_len):
+        if not t.is_cuda:
+            raise H.CvclError("per-word Grad-CAM needs device tensors (got a CPU tensor); there is no CPU fallback")
+    F32 = torch.float32
+    lib, s, dev = H.lib(), H.stream_ptr(), features.device
+    lstm, Hd, K = te.lstm, te.hidden_dim, L - 1
+    table = te.embedding.weight.detach().contiguous()
+    V, E = table.shape
+    if Hd % 4 != 0:
+        raise H.CvclError(f"hidden_dim {Hd} is not a multiple of 4")
+    y = y.to(torch.int64).contiguous()
+    length = y_len.to(torch.int64).contiguous()
+    f = features.detach().to(F32).contiguous()
+    n, norm = f, None
+    if normalize_features:                                                          # encode_image (reference multimodal.py:736)
+        n = torch.empty_like(f)
+        norm = torch.empty(B, dtype=F32, device=dev)
+        H.check(lib.cvcl_l2norm_fwd(H.ptr(f), H.ptr(n), H.ptr(norm), B, E, eps, s), "cvcl_l2norm_fwd")
+
+    # forward: connector -> (h0, c0), the LSTM over tokens 0 .. L-2 with everything BPTT needs saved, output layer, softmax
+    w_conn = te.connector.weight.detach().contiguous()                              # [2 H, E]
+    state = H.gemm(n, w_conn, bias=te.connector.bias.detach().contiguous())
+    h, c0 = state[:, :Hd].contiguous(), state[:, Hd:].contiguous()
+    c = c0.clone()
+    tok = y[:, :K].contiguous()
+    x = torch.empty(B * K, E, dtype=F32, device=dev)
+    H.check(lib.cvcl_embed_gather_pos(H.ptr(table, F32), H.ptr(tok), None, H.ptr(x), B, K, E, V, s), "cvcl_embed_gather_pos")
+    w_hh = lstm.weight_hh_l0.detach().contiguous()
+    gx = H.gemm(x, lstm.weight_ih_l0.detach().contiguous(), bias=(lstm.bias_ih_l0 + lstm.bias_hh_l0).detach().contiguous())
+    gates = torch.empty(B, 4 * Hd, dtype=F32, device=dev)
+    gact = torch.zeros(B * K, 4 * Hd, dtype=F32, device=dev)
+    csave = torch.empty(B * K, Hd, dtype=F32, device=dev)
+    hprev = torch.empty(B * K, Hd, dtype=F32, device=dev)
+    out = torch.empty(B * K, Hd, dtype=F32, device=dev)
+    for t in range(K):
+        a = H.GemmArgs()
+        a.A, a.W, a.C = H.ptr(h), H.ptr(w_hh), H.ptr(gates)
+        a.M, a.N, a.K, a.lda, a.ldw, a.ldc = B, 4 * Hd, Hd, Hd, Hd, 4 * Hd
+        a.R, a.ldr = gx.data_ptr() + t * 4 * Hd * 4, K * 4 * Hd
+        H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
+        H.check(lib.cvcl_lstm_cell_train(H.ptr(gates), H.ptr(length), t, H.ptr(h), H.ptr(c), H.ptr(out), H.ptr(gact), H.ptr(csave),
+                                         H.ptr(hprev), B, K, Hd, s), "cvcl_lstm_cell_train")
+    w_out = language_model.output_layer.weight.detach().contiguous()                # [V, H] (the tied table)
+    b_out = language_model.output_layer.bias
+    logits = H.gemm(out, w_out, bias=None if b_out is None else b_out.detach().contiguous())
+    labels = y[:, 1:].contiguous().view(-1)
+    R = B * K
+    loss = torch.empty(R, dtype=F32, device=dev)
+    lse = torch.empty(R, dtype=F32, device=dev)
+    H.check(lib.cvcl_token_ce_fwd(H.ptr(logits), H.ptr(labels), H.ptr(loss), H.ptr(lse), R, V, PAD_TOKEN_ID, s), "cvcl_token_ce_fwd")
+
+    # seeds: -(softmax - onehot) per token (unit upstream gradient, negated), through the output layer
+    minus_one = torch.full((R,), -1.0, dtype=F32, device=dev)
+    d_logits = torch.empty_like(logits)
+    H.check(lib.cvcl_token_ce_bwd(H.ptr(logits), H.ptr(labels), H.ptr(lse), H.ptr(minus_one), H.ptr(d_logits), R, V, PAD_TOKEN_ID, s),
+            "cvcl_token_ce_bwd")
+    d_out = H.gemm(d_logits, w_out, w_trans=True)                                   # [B K, H], row b K + p
+
+    # triangular sweep over the seed-major state [K][B][H]: at step t the chains of blocks t .. K-1 are alive
+    dh = torch.empty(K * B, Hd, dtype=F32, device=dev)
+    dc = torch.empty(K * B, Hd, dtype=F32, device=dev)
+    dG = torch.empty(K * B, 4 * Hd, dtype=F32, device=dev)
+    carry = torch.empty(K * B, Hd, dtype=F32, device=dev)
+    for t in range(K - 1, -1, -1):
+        rows, off = B * (K - t), t * B * Hd * 4
+        H.check(lib.cvcl_lstm_cell_bwd_seeds(H.ptr(gact), H.ptr(csave), H.ptr(c0) if t == 0 else None, H.ptr(length), t, H.ptr(d_out),
+                                             dh.data_ptr() + off, dc.data_ptr() + off, H.ptr(dG), H.ptr(carry), B, K, Hd, rows, s),
+                "cvcl_lstm_cell_bwd_seeds")
+        a = H.GemmArgs()                                                            # dh_{t-1} = dG_t . W_hh + carry
+        a.A, a.W, a.C = H.ptr(dG), H.ptr(w_hh), dh.data_ptr() + off
+        a.M, a.N, a.K, a.lda, a.ldw, a.ldc = rows, Hd, 4 * Hd, 4 * Hd, Hd, Hd
+        a.w_trans = 1
+        a.R, a.ldr = H.ptr(carry), Hd
+        H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
+
+    # connector backward on all rows: d n = dh0 W[:H] + dc0 W[H:], then F.normalize's backward with the image's (n, norm) and the
+    # reordering seed-major -> image-major in one launch
+    dn_h = torch.empty(K * B, E, dtype=F32, device=dev)
+    dn = torch.empty(K * B, E, dtype=F32, device=dev)
+    for A, W_off, C, Rr in ((dh, 0, dn_h, None), (dc, Hd * E * 4, dn, dn_h)):
+        a = H.GemmArgs()
+        a.A, a.W, a.C = H.ptr(A), w_conn.data_ptr() + W_off, H.ptr(C)
+        a.M, a.N, a.K, a.lda, a.ldw, a.ldc = K * B, E, Hd, Hd, E, E
+        a.w_trans = 1
+        if Rr is not None:
+            a.R, a.ldr = H.ptr(Rr), E
+        H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
+    targets = torch.empty(B * K, E, dtype=F32, device=dev)
+    H.check(lib.cvcl_l2norm_bwd_seeds(H.ptr(n) if normalize_features else None, H.ptr(norm), H.ptr(dn), H.ptr(targets), B, K, E, eps, s),
+            "cvcl_l2norm_bwd_seeds")
+    return targets
+
+
+def caption_gradcam_from_features(fmap, features, fc_weight, language_model, y, y_len, normalize_features=False, resize=False):
+    """Per-word Grad-CAM maps of a captioning LM from one trunk pass's outputs -> [B, L-1, h, w] fp32 (or [B, L-1, H', W'] with
+    ``resize=(H', W')``): map [b, p] is relu(sum_c alpha_c A[b, c]) with alpha = -mean_hw d loss[b, p] / d A[b], loss[b, p] the cross
+    entropy of predicting y[b, p + 1] from position p -- what the reference's gradCAM_for_captioning_lm returns for step p + 1
+    (analysis_tools/multimodal_visualization.py:9-49), for all captions and words without a backward pass per word.  ``fmap``,
+    ``features``, ``fc_weight`` as in gradcam_from_features; ``y`` [B, L] int64, ``y_len`` [B].  Maps of <pad> labels are exactly 0.
+    The map reaches the loss only through avgpool and fc, so the maps are the Grad-CAM contraction (cvcl_gradcam_pairs, image n with
+    its own L - 1 targets) of the targets caption_seed_targets computes; the normalisation is already inside them."""
+    for t in (fmap, features, fc_weight):
+        if not t.is_cuda:
+            raise H.CvclError("per-word Grad-CAM needs device tensors (got a CPU tensor); there is no CPU fallback")
+    targets = caption_seed_targets(features, language_model, y, y_len, normalize_features)
+    return gradcam_from_features(fmap, features, fc_weight, targets, False, ("block", y.shape[1] - 1, "image"), resize)
+
+
+@torch.no_grad()
+def gradCAM_captions(model, images, y, y_len, resize=False):
+    """Batched per-word Grad-CAM of a captioning ``MultiModalLitModel``: one eval-mode trunk pass over ``images`` [B, 3, H, W], then
+    caption_gradcam_from_features with the model's ``normalize_features`` -> [B, L-1, h, w] (``resize=True``: bicubic to H x W).
+    Flat ResNeXt encoder + captioning one-layer LSTM only.  No autograd graph is built; every ``requires_grad``, ``training`` flag and
+    parameter ``.grad`` is left as it was found (the trunk runs with its modules in eval mode for the length of the pass, as the
+    reference calls this on an eval() model; the language model's arithmetic is the eval one whatever its flags)."""
+    resnet = _resnet_of(model.vision_encoder)
+    _captioning_lstm_of(model.language_model)
+    for t in (images, y, y_len):
+        if not t.is_cuda:
+            raise H.CvclError("gradCAM_captions needs device tensors (got a CPU tensor); there is no CPU fallback")
+    flags = [(m, m.training) for m in resnet.modules()]
+    try:
+        for m, _ in flags:
+            m.training = False
+        with Hook(resnet.layer4, requires_grad=False) as hook:
+            features = resnet(images)
+            fmap = hook.activation
+    finally:
+        for m, was in flags:
+            m.training = was
+    size = tuple(images.shape[2:]) if resize is True else resize
+    return caption_gradcam_from_features(fmap, features, resnet.fc.weight, model.language_model, y, y_len,
+                                         bool(model.model.normalize_features), size)
+
+
+def gradCAM_for_captioning_lm(model, x, y, y_len, steps=None):
+    """The reference's call (analysis_tools/multimodal_visualization.py:9-49): one image ``x`` [3, H, W], one caption ``y`` [L] with
+    ``y_len`` (a one-element tensor) -> a list over ``steps`` (default 0 .. y_len - 1): None for step 0, otherwise the [h, w] numpy
+    map of predicting word ``step``.  A batch-of-one call of gradCAM_captions."""
+    if steps is None:
+        steps = list(range(int(y_len.item())))
+    dev = next(model.parameters()).device
+    cams = gradCAM_captions(model, x.unsqueeze(0).to(dev), y.unsqueeze(0).to(dev), y_len.reshape(1).to(dev))[0]
+    host = cams.cpu().numpy()
+    return [None if step == 0 else host[step - 1] for step in steps]
 
 
 # ---- host-side visualisation (numpy / matplotlib) ------------------------------------------------------------------------
