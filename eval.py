@@ -82,7 +82,9 @@ def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention
     """trials: list of collated batch-1 items (img, label, label_len, raw_label).  Returns per trial (soft-max list, pred).
     All trials of the list are encoded in one pass; trial t's logits are the t-th diagonal block.
     ``attention_maps``: returns (per-trial results, Grad-CAM maps [T, 4, h, w]) -- per trial the maps of its 4 images w.r.t. its
-    label (``image``) or of its image w.r.t. its 4 labels (``text``), from the same encoder pass as the logits."""
+    label (``image``) or of its image w.r.t. its 4 labels (``text``), from the same encoder pass as the logits.  A ViT encoder has
+    no Grad-CAM: its maps are the CLS token's last-block self-attention [T, 4, gh, gw], which do not depend on the label (``text``:
+    the one image's map repeated 4 times, so the array keeps its shape)."""
     T = len(trials)
     if eval_type == "image":
         imgs = torch.cat([t[0].squeeze(0) for t in trials], 0).to(device)                    # [4T, ...]
@@ -103,7 +105,13 @@ def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention
     if imgs.dtype == torch.uint8 and datamodule is not None:                                 # --device_frames: base transform on the GPU
         imgs = datamodule.on_after_batch_transfer((imgs,), 1, training=False)[0]
     maps = None
-    if attention_maps:                                    # label t with images 4t .. 4t + 3, or image t with labels 4t .. 4t + 3
+    if attention_maps and getattr(getattr(model, "vision_encoder", None), "vit_dino", False):
+        logits_per_image, logits_per_text, maps = model.self_attention_maps(imgs, labels.to(device), lens.to(device))
+        if eval_type == "image":                          # [4T, gh, gw] -> [T, 4, gh, gw]
+            maps = maps.view(T, n_per, *maps.shape[1:])
+        else:                                             # one image per trial: its map along the 4 axis
+            maps = maps[:, None].expand(T, n_per, *maps.shape[1:]).contiguous()
+    elif attention_maps:                                  # label t with images 4t .. 4t + 3, or image t with labels 4t .. 4t + 3
         pairs = ("block", n_per, "text" if eval_type == "image" else "image")
         logits_per_image, logits_per_text, maps = model.attention_maps(imgs, labels.to(device), lens.to(device), pairs=pairs)
     else:
@@ -119,7 +127,7 @@ def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention
 
 
 def plot_attention(path, image, cam):
-    """One overlay PNG (reference eval_shuffled.py:195-228): the frame with its Grad-CAM map blended in."""
+    """One overlay PNG (reference eval_shuffled.py:195-228): the frame with its Grad-CAM (ViT: self-attention) map blended in."""
     try:
         import matplotlib
         matplotlib.use("Agg")
@@ -256,7 +264,10 @@ def _parser():
     parser.add_argument("--n_trials", type=int, default=32, help="number of synthetic trials")
     parser.add_argument("--attention_maps", type=str, default=None, metavar="DIR",
                         help="write the Grad-CAM maps of every trial (layer 4, same pass as the logits) to DIR/cams.npy "
-                             "[n_trials, 4, h, w]: the trial's 4 images w.r.t. its label (image) or its image w.r.t. its 4 labels (text)")
+                             "[n_trials, 4, h, w]: the trial's 4 images w.r.t. its label (image) or its image w.r.t. its 4 labels (text). "
+                             "With a ViT checkpoint (--vit_dino) the maps are the CLS token's last-block self-attention over the patch "
+                             "grid, averaged over the heads, [n_trials, 4, gh, gw]: unlike Grad-CAM they do not depend on the label "
+                             "(--eval_type text: the trial's one map repeated 4 times)")
     parser.add_argument("--plot_attention", action="store_true",
                         help="save one overlay PNG per trial, {model}_{class}_{i %% 100}_attn_map.png, under the --attention_maps "
                              "directory (results/ without it); needs matplotlib")

@@ -670,6 +670,22 @@ int cvcl_gradcam_act_grad(int act_dtype, const void* act, int act_nhwc, int grad
                           int N, int C, int HW, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Self-attention maps of the DINO ViT (csrc/vit_maps.hip; vision_transformer_dino_mugs.py:252-259 get_last_selfattention).
+ * softmax(q k^T * scale) of vit:123-124, written out: qkv [B][T][3][heads][hd] (dtype f32 or bf16)
+ * -> probs [B][heads][q_rows][T] fp32 for queries 0 .. q_rows-1 (q_rows = T: the whole matrix; 1: the CLS row).
+ * hd = 64: MFMA route (fp32: v_mfma_f32_32x32x2_f32, exact; bf16: v_mfma_f32_32x32x16_bf16, fp32 accumulation), one workgroup per
+ * (image, head, 128 queries), key tiles of 64 streamed through LDS (any T), two passes (running max / sum, then the stores), no
+ * T x T scratch, no atomics, fixed reduction order: deterministic.  qkv 16-byte aligned; probs needs no alignment beyond 4 bytes.
+ * Other hd (hd % 4 == 0, hd <= 128): a plain fp32 VALU route.  CVCL_EINVAL before anything is enqueued on a null pointer, q_rows
+ * outside 1 .. T, a dtype other than CVCL_F32 / CVCL_BF16, non-positive sizes or another hd.  CVCL_K_ATTENTION.               */
+int cvcl_attention_probs(int dtype, const void* qkv, float* probs, int B, int T, int heads, int head_dim, float scale, int q_rows,
+                         void* stream);
+/* The CLS query's attention over the patch tokens: probs [B][heads][1][T] (cvcl_attention_probs with q_rows = 1) ->
+ * out [B][T-1] = the mean over the heads (mean != 0; summed h = 0 first, then / heads) or out [B][heads][T-1] = a copy without
+ * the CLS column (mean == 0).  T > 1; out must not alias probs.  CVCL_K_OTHER.                                                 */
+int cvcl_cls_attention_maps(const float* probs, float* out, int B, int heads, int T, int mean, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Beam-search decoding of the LSTM language model (csrc/textgen.hip).  Replaces the reference's LanguageModel.beam_search_decode
  * (multimodal/multimodal.py:893-960) over beam_search (multimodal/beam_search.py:232-703): per decode step the torch composition
  * of grow_topk / grow_alive / grow_finished (:418-611) plus the host `.item()` of the stop test (:613-667) becomes one launch.

@@ -202,6 +202,9 @@ SIGNATURES = {
     "cvcl_gradcam_pairs": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _F, _P, _P]),
     "cvcl_bicubic_resize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cvcl_gradcam_act_grad": (_I, [_I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P]),
+    # ViT self-attention maps (csrc/vit_maps.hip)
+    "cvcl_attention_probs": (_I, [_I, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
+    "cvcl_cls_attention_maps": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     # beam-search decoding (csrc/textgen.hip)
     "cvcl_beam_step": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "cvcl_beam_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -212,6 +212,38 @@ def gradCAM_pairs(vision_model, images, targets, normalize_features=False, pairs
     return gradcam_from_features(fmap, features, resnet.fc.weight, targets, normalize_features, pairs, size)
 
 
+# ---- self-attention maps of the DINO ViT encoder ---------------------------------------------------------------------------
+
+def _vit_of(vision_model):
+    """The VisionTransformer behind ``vision_model`` (a VisionEncoder or the ViT itself); a ResNeXt encoder is sent to Grad-CAM."""
+    from .vision_transformer_dino_mugs import VisionTransformer
+    model = getattr(vision_model, "model", vision_model)
+    if not isinstance(model, VisionTransformer):
+        raise NotImplementedError("self-attention maps are defined for the ViT encoder only; for the ResNeXt encoder use gradCAM_pairs "
+                                  f"(got {type(model).__name__})")
+    return model
+
+
+@torch.no_grad()
+def vit_cls_attention(vision_model, x, size=None, heads="mean"):
+    """The CLS query's attention over the patch tokens in the ViT's last block (the usual view of a DINO ViT; the CLS row of
+    reference vision_transformer_dino_mugs.py:252-259 without its CLS column): [B, gh, gw] fp32 averaged over the heads
+    (``heads="mean"``) or [B, heads, gh, gw] (``heads=None``).  One q_rows = 1 launch of cvcl_attention_probs: the T x T matrix is
+    never formed.  ``size=(H, W)``: resized bicubically (cvcl_bicubic_resize).  Unlike Grad-CAM the map does not depend on a target."""
+    from . import vit_maps
+    vit = _vit_of(vision_model)
+    if heads not in ("mean", None):
+        raise ValueError(f"heads = {heads!r}: 'mean' or None")
+    if not x.is_cuda:
+        raise H.CvclError("vit_cls_attention needs device tensors (got a CPU tensor); there is no CPU fallback")
+    probs, (gh, gw) = vit_maps.last_selfattention(vit, x, q_rows=1)
+    maps = vit_maps.cls_maps(probs, heads == "mean")
+    maps = maps.view(*maps.shape[:-1], gh, gw)
+    if size is not None:
+        maps = bicubic_resize(maps, size)
+    return maps
+
+
 # ---- per-word maps of the captioning language model ----------------------------------------------------------------------
 
 MAX_CAPTION_LEN = 32                                       # the LSTM path's limit (text_train.transformer_text_train, ops.lstm_text)

@@ -579,6 +579,15 @@ class MultiModalModel(nn.Module):
         maps = gradcam_from_features(feature_map, features, resnet.fc.weight, ft, self.normalize_features, pairs, size)
         return logits_per_image, logits_per_image.t(), maps
 
+    def self_attention_maps(self, image, text, text_length):
+        """ViT encoder: -> (logits_per_image, logits_per_text, maps [N, gh, gw]) -- the logits of forward() on the same inputs and
+        the CLS token's last-block self-attention over the patch grid, averaged over the heads (attention_maps.vit_cls_attention).
+        The maps depend on the image alone, not on the text (unlike Grad-CAM, which stays undefined for the ViT).  Evaluation use."""
+        from .attention_maps import vit_cls_attention
+        maps = vit_cls_attention(self.image_embed, image)      # (refuses a ResNeXt encoder before any encoder pass)
+        logits_per_image, logits_per_text = self(image, text, text_length)
+        return logits_per_image, logits_per_text, maps
+
     def calculate_contrastive_loss(self, x, y, y_len):
         logits_per_image, logits_per_text, image_features, image_feature_map, text_outputs = self(
             x, y, y_len, return_image_features=True, return_text_outputs=True)

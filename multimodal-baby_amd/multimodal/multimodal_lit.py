@@ -139,6 +139,10 @@ class MultiModalLitModel(LightningModule):
         """(logits_per_image, logits_per_text, Grad-CAM maps) of one encoder pass: MultiModalModel.attention_maps."""
         return self.model.attention_maps(x, y, y_len, pairs=pairs, resize=resize)
 
+    def self_attention_maps(self, x, y, y_len):
+        """(logits_per_image, logits_per_text, the ViT's CLS self-attention maps [N, gh, gw]): MultiModalModel.self_attention_maps."""
+        return self.model.self_attention_maps(x, y, y_len)
+
     @staticmethod
     def load_model(model_name="cvcl", checkpoint_path=None):
         """Reference :134-149 downloads ``wkvong/cvcl_s_dino_resnext50_embedding`` from the HF hub; without a

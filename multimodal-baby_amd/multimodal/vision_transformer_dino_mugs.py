@@ -140,6 +140,16 @@ class VisionTransformer(nn.Module):
         from . import vit_hip
         return vit_hip.vit_forward(self, x)
 
+    def get_last_selfattention(self, x):
+        """-> the last block's softmax(q k^T scale), [B, heads, T, T] fp32 (reference :252-259); see vit_maps."""
+        from . import vit_maps
+        return vit_maps.last_selfattention(self, x)[0]
+
+    def get_intermediate_layers(self, x, n=1):
+        """-> the final ``norm`` of the token matrix after each of the last ``n`` blocks: n tensors [B, T, D] fp32 (reference :261-269)."""
+        from . import vit_maps
+        return vit_maps.intermediate_layers(self, x, n)
+
 
 def vit_tiny(patch_size=16, **kw):
     return VisionTransformer(patch_size=patch_size, embed_dim=192, depth=12, num_heads=3, mlp_ratio=4, qkv_bias=True,

@@ -1,0 +1,116 @@
+"""ViT self-attention maps at B = 256, 224 x 224, ViT-B/16 and ViT-B/14, bf16 and fp32 (random-init weights):
+  get_last_selfattention, vit_cls_attention and get_intermediate_layers(n = 4) against the eager torch composition on the device
+  (the reference's lines, vision_transformer_dino_mugs.py:232-269, on torch's ROCm ops with the same weights; under
+  torch.autocast(bfloat16) for the bf16 rows), and cvcl_attention_probs alone (q_rows = T and 1): ms and GB/s of the bytes it must
+  write.  The parent of this entry cannot run these calls at all, so the eager composition is the only baseline.
+Warm-up, then ``--repeats`` device-event timings of ``--iters`` calls each; reported as median [min, max].  Prints one JSON line.
+
+    python tools/bench_vit_attention.py [--batch 256] [--iters 3] [--repeats 5] [--patches 16,14] [--dtypes bf16,f32] [--kernel-only]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
+
+from multimodal import vision_transformer_dino_mugs as vits          # noqa: E402
+from multimodal import vit_maps                                       # noqa: E402
+from multimodal.attention_maps import vit_cls_attention               # noqa: E402
+
+
+def timed(fn, iters, repeats):
+    out = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) / iters)
+    return {"ms": round(statistics.median(out), 3), "min": round(min(out), 3), "max": round(max(out), 3)}
+
+
+def eager(model, x, want, n=4):
+    """The reference's composition on torch ops: ``want`` = 'attn' (the last block's probabilities), 'cls' (their CLS row, head mean)
+    or 'layers' (norm of the last n blocks' outputs)."""
+    B = x.shape[0]
+    D, heads = model.embed_dim, model.num_heads
+    h = model.patch_embed.proj(x).flatten(2).transpose(1, 2)
+    h = torch.cat([model.cls_token.expand(B, -1, -1).to(h.dtype), h], dim=1) + model.pos_embed
+    T, out, depth = h.shape[1], [], len(model.blocks)
+    for i, blk in enumerate(model.blocks):
+        y = blk.norm1(h)
+        qkv = blk.attn.qkv(y).reshape(B, T, 3, heads, D // heads).permute(2, 0, 3, 1, 4)
+        attn = ((qkv[0] @ qkv[1].transpose(-2, -1)) * blk.attn.scale).softmax(dim=-1)
+        if i == depth - 1 and want != "layers":
+            return attn.float() if want == "attn" else attn[:, :, 0, 1:].float().mean(1)
+        h = h + blk.attn.proj((attn @ qkv[2]).transpose(1, 2).reshape(B, T, D))
+        h = h + blk.mlp.fc2(F.gelu(blk.mlp.fc1(blk.norm2(h))))
+        if depth - i <= n:
+            out.append(model.norm(h).float())
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--patches", type=str, default="16,14")
+    ap.add_argument("--dtypes", type=str, default="bf16,f32")
+    ap.add_argument("--kernel-only", action="store_true", help="time cvcl_attention_probs alone (the run to put under rocprofv3)")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B = args.batch
+    res = {"batch": B, "iters": args.iters, "repeats": args.repeats, "cases": []}
+    for patch in (int(p) for p in args.patches.split(",")):
+        torch.manual_seed(0)
+        model = vits.vit_base(patch_size=patch, num_classes=0).to(dev).eval()
+        for p in model.parameters():
+            p.requires_grad_(False)
+        x = torch.randn(B, 3, 224, 224, device=dev)
+        T, heads = (224 // patch) ** 2 + 1, model.num_heads
+        for name in args.dtypes.split(","):
+            dt = torch.bfloat16 if name == "bf16" else torch.float32
+            model.compute_dtype = dt
+            case = {"patch": patch, "dtype": name, "T": T}
+            cast = torch.autocast("cuda", dtype=torch.bfloat16, enabled=dt == torch.bfloat16)
+            calls = {"get_last_selfattention": (lambda: model.get_last_selfattention(x), "attn"),
+                     "vit_cls_attention": (lambda: vit_cls_attention(model, x), "cls"),
+                     "get_intermediate_layers_4": (lambda: model.get_intermediate_layers(x, 4), "layers")}
+            for key, (fn, want) in ({} if args.kernel_only else calls).items():
+                def ref(want=want):
+                    with torch.no_grad(), cast:
+                        return eager(model, x, want)
+                fn(), ref()                                            # warm-up: packing, allocator, library handles
+                torch.cuda.empty_cache()
+                case[key] = {"hip": timed(fn, args.iters, args.repeats), "eager_torch": timed(ref, args.iters, args.repeats)}
+                case[key]["speedup"] = round(case[key]["eager_torch"]["ms"] / case[key]["hip"]["ms"], 2)
+            # the kernel alone on one qkv matrix of the model's shape
+            qkv = torch.randn(B * T, 3 * model.embed_dim, device=dev).to(dt)
+            for q_rows in (T, 1):
+                def k(q_rows=q_rows):
+                    vit_maps.attention_probs(qkv, B, T, heads, 64, 0.125, q_rows)
+                k()
+                t = timed(k, max(args.iters, 10), args.repeats)
+                nbytes = B * heads * q_rows * T * 4
+                t["write_bytes"] = nbytes
+                t["write_gbs"] = round(nbytes / (t["ms"] * 1e-3) / 1e9, 1)
+                case[f"kernel_q_rows_{'T' if q_rows == T else 1}"] = t
+            del qkv
+            torch.cuda.empty_cache()
+            res["cases"].append(case)
+        del model, x
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
