@@ -780,6 +780,40 @@ int cvcl_nn_l1_u8(const uint8_t* q, const uint8_t* base, int Nq, int Nb, int C, 
                   const int32_t* base_group, int64_t idx_offset, int accumulate, double* best_dist, int64_t* best_idx,
                   uint32_t* best_sums, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Image-text alignment analysis (csrc/alignment.hip): the arithmetic of the reference's analysis_cvcl/alignment.py,
+ * analysis_cvcl/embeddings.py:106-118 and analysis_tools/representation_similarity.py.  fp32 in and out (the Pearson moments: double),
+ * contiguous rows.  Every entry validates everything before it enqueues anything (null pointers, sizes out of range, a workspace that
+ * is too small or not 16-byte aligned: CVCL_EINVAL, cvcl_last_error names the argument) and enqueues on the caller's stream only.  No
+ * floating-point atomics: the order of every sum is fixed by the shapes (and, for the class means, the labels), so two calls on the
+ * same inputs give the same bits whatever the addresses.
+ *
+ * cvcl_class_mean_f32: np.mean(all_image_features[idxs], axis=0) per category (alignment.py:106-110; embeddings.py:88-90).
+ *   x [N, D] f32, label [N] int32 in [0, C) (any order, classes of any size) -> mean [C, D] f32 and count [C] int32.  Sums in double
+ *   (one rounding to fp32 after the division).  A class without rows gets count 0 and a zero row; rows whose label lies outside
+ *   [0, C) are left out.  Limits: N < 2^24, D <= 2048, C <= 4096.  Workspace: cvcl_class_mean_workspace_bytes (0 = refused sizes)
+ *   -- the row indices sorted by class and the histograms that sort them.  CVCL_K_OTHER.
+ * cvcl_cosine_matrix_f32: out[i, j] = a_i . b_j / (max(|a_i|, eps) max(|b_j|, eps)), a [M, D], b [K, D] -> out [M, K]: the value of
+ *   F.cosine_similarity(F.normalize(a_i), F.normalize(b_j), dim=0) (alignment.py:148-161, :182-195) and of cosine_matrix
+ *   (representation_similarity.py:5-12).  Products are exact fp32 (v_mfma_f32_16x16x4_f32 / v_mfma_f32_32x32x2_f32), the four
+ *   partial sums of an element, the norms and the division are in double, one rounding to fp32.  a == b (the same pointer; then
+ *   M == K) is allowed and gives an exactly symmetric matrix: one triangle is computed and written twice.  Zero rows give 0.
+ *   Limits: M, K <= 4096, D <= 2048.  The grid follows M and K (16 x 16 outputs per workgroup below 256 tiles of 32 x 32).  CVCL_K_HEAD.
+ * cvcl_triu_pearson_f32: scipy.stats.pearsonr(A[np.triu_indices(C, k=1)], B[np.triu_indices(C, k=1)]) (alignment.py:230-232;
+ *   rsa_of_dissim_matrices, representation_similarity.py:30-39).  A, B [C, C] f32 -> out [6] doubles ON THE DEVICE: n = C (C - 1) / 2,
+ *   r, mean_a, mean_b, var_a, var_b (population variances).  Centred in double: per workgroup the means of its rows, then the
+ *   second moments about them; the partials are merged in a fixed tree.  A side whose values are all equal gives r = NaN (a value,
+ *   as scipy returns it).  Limits: 3 <= C <= 4096.  Workspace: cvcl_triu_pearson_workspace_bytes.  CVCL_K_OTHER.
+ * cvcl_paired_l2_f32: d_i = || x_i - y_i + eps ||_2 = F.pairwise_distance(x_i, y_i, p=2) (embeddings.py:106-111; torch: eps = 1e-6).
+ *   x, y [C, D] f32 -> d [C] f32; differences and sums in double.  Limits: C <= 4096, D <= 2048.  CVCL_K_OTHER. */
+size_t cvcl_class_mean_workspace_bytes(int N, int D, int C);
+int cvcl_class_mean_f32(const float* x, const int32_t* label, int N, int D, int C, float* mean, int32_t* count, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int cvcl_cosine_matrix_f32(const float* a, const float* b, int M, int K, int D, float eps, float* out, void* stream);
+size_t cvcl_triu_pearson_workspace_bytes(int C);
+int cvcl_triu_pearson_f32(const float* A, const float* B, int C, double* out6, void* workspace, size_t workspace_bytes, void* stream);
+int cvcl_paired_l2_f32(const float* x, const float* y, int C, int D, float eps, float* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

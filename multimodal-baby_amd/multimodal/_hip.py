@@ -218,6 +218,13 @@ SIGNATURES = {
     "cvcl_nn_cosine": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, C.c_int64, _I, _P, _P, _P, _SZ, _P]),
     "cvcl_nn_l1_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
     "cvcl_nn_l1_u8": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_double), _P, _P, C.c_int64, _I, _P, _P, _P, _P, _SZ, _P]),
+    # image-text alignment analysis (csrc/alignment.hip)
+    "cvcl_class_mean_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "cvcl_class_mean_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "cvcl_cosine_matrix_f32": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
+    "cvcl_triu_pearson_workspace_bytes": (_SZ, [_I]),
+    "cvcl_triu_pearson_f32": (_I, [_P, _P, _I, _P, _P, _SZ, _P]),
+    "cvcl_paired_l2_f32": (_I, [_P, _P, _I, _I, _F, _P, _P]),
 }
 
 _lib = None

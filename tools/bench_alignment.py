@@ -1,0 +1,111 @@
+"""The alignment chain (multimodal/alignment.py: class means, the three cosine matrices, the Pearson correlation of the two upper
+triangles) against the eager torch composition on the same device tensors, at the reference's shape (N = 4400 frames, D = 512,
+C = 22 categories) and at a vocabulary-scale one (N = 50 000, D = 512, C = 2350).
+
+    python tools/bench_alignment.py [--shapes 4400x512x22,50000x512x2350] [--repeats 7] [--window-ms 200]
+
+Yardstick: index_add_ + division for the means, F.normalize and ``@`` for the matrices, the triangle selection and centred double
+moments for r -- what a torch user would write in place of the reference's per-entry loops (which are not timed: they are minutes).
+Per shape and side: warm-up, then ``repeats`` windows of calls sized to ``window-ms`` between two device events; the median window
+per call is reported, the spread (min .. max) beside it, the two sides in alternation.  Also the kernels one by one, and the
+class-mean kernel's achieved GB/s over the bytes it has to move (N D 4 read + N 4 labels + C D 4 written).  Prints one JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="4400x512x22,50000x512x2350")
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--window-ms", type=float, default=200.0)
+    a = ap.parse_args()
+    import torch
+    import torch.nn.functional as F
+    from multimodal import alignment as A
+    if not torch.cuda.is_available():
+        sys.exit("bench_alignment: no GPU")
+    dev = torch.device("cuda:0")
+
+    def window(fn, calls):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(calls):
+            fn()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) * 1e3 / calls               # us per call
+
+    def measure(fns):
+        """{name: fn} -> {name: {"us", "min_us", "max_us", "calls"}}; the sides alternate window by window"""
+        calls = {}
+        for k, fn in fns.items():
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            one = window(fn, 5)
+            calls[k] = max(5, min(20000, int(a.window_ms * 1e3 / max(one, 1.0))))
+        samples = {k: [] for k in fns}
+        for _ in range(a.repeats):
+            for k, fn in fns.items():
+                samples[k].append(window(fn, calls[k]))
+        return {k: {"us": statistics.median(v), "min_us": min(v), "max_us": max(v), "calls": calls[k]} for k, v in samples.items()}
+
+    out = {"repeats": a.repeats, "window_ms": a.window_ms, "device": torch.cuda.get_device_name(0), "shapes": {}}
+    for shape in a.shapes.split(","):
+        N, D, Cn = (int(v) for v in shape.split("x"))
+        g = torch.Generator(device=dev).manual_seed(0)
+        proto = torch.randn(Cn, D, device=dev, generator=g)
+        lab = torch.randint(0, Cn, (N,), device=dev, generator=g)
+        lab[:Cn] = torch.arange(Cn, device=dev)                 # no empty class
+        x = (proto[lab] + 0.5 * torch.randn(N, D, device=dev, generator=g)).contiguous()
+        text = (proto + 0.5 * torch.randn(Cn, D, device=dev, generator=g)).contiguous()
+        lab32 = lab.int().contiguous()
+        iu = torch.triu_indices(Cn, Cn, offset=1, device=dev)
+
+        def hip_chain():
+            means, _ = A._class_means(x, lab32, Cn)
+            si, st = A.cosine_matrix(means), A.cosine_matrix(text)
+            sit = A.cosine_matrix(means, text)
+            return A._triu_pearson(si, st), sit
+
+        def torch_means():
+            s = torch.zeros(Cn, D, device=dev).index_add_(0, lab, x)
+            return s / torch.bincount(lab, minlength=Cn).clamp_min(1)[:, None]
+
+        def torch_pearson(si, st):
+            u, v = si[iu[0], iu[1]].double(), st[iu[0], iu[1]].double()
+            u, v = u - u.mean(), v - v.mean()
+            return (u @ v) / (u.norm() * v.norm())
+
+        def torch_chain():
+            means = torch_means()
+            mn, tn = F.normalize(means, dim=1), F.normalize(text, dim=1)
+            si, st, sit = mn @ mn.T, tn @ tn.T, mn @ tn.T
+            return torch_pearson(si, st), sit
+
+        means, _ = A._class_means(x, lab32, Cn)
+        si, st = A.cosine_matrix(means), A.cosine_matrix(text)
+        mn, tn = F.normalize(means, dim=1), F.normalize(text, dim=1)
+        r_hip, r_torch = float(hip_chain()[0][1]), float(torch_chain()[0])
+        res = measure({"hip_chain": hip_chain, "torch_chain": torch_chain})
+        res.update(measure({"hip_class_means": lambda: A._class_means(x, lab32, Cn), "torch_class_means": torch_means}))
+        res.update(measure({"hip_cosine_self": lambda: A.cosine_matrix(means), "torch_cosine_self": lambda: mn @ mn.T,
+                            "hip_cosine_pair": lambda: A.cosine_matrix(means, text)}))
+        res.update(measure({"hip_pearson": lambda: A._triu_pearson(si, st), "torch_pearson": lambda: torch_pearson(si, st)}))
+        moved = N * D * 4 + N * 4 + Cn * D * 4
+        res["class_means_GBps"] = moved / (res["hip_class_means"]["us"] * 1e-6) / 1e9
+        res["torch_class_means_GBps"] = moved / (res["torch_class_means"]["us"] * 1e-6) / 1e9
+        res["chain_speedup_over_torch"] = res["torch_chain"]["us"] / res["hip_chain"]["us"]
+        res["r_hip"], res["r_torch"] = r_hip, r_torch
+        out["shapes"][shape] = res
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
