@@ -686,7 +686,7 @@ int cvcl_attention_probs(int dtype, const void* qkv, float* probs, int B, int T,
 int cvcl_cls_attention_maps(const float* probs, float* out, int B, int heads, int T, int mean, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Beam-search decoding of the LSTM language model (csrc/textgen.hip).  Replaces the reference's LanguageModel.beam_search_decode
+ * Beam-search decoding of the LSTM language model (csrc/textgen.hip; its LSTM cells: csrc/lstm.hip).  Replaces the reference's LanguageModel.beam_search_decode
  * (multimodal/multimodal.py:893-960) over beam_search (multimodal/beam_search.py:232-703): per decode step the torch composition
  * of grow_topk / grow_alive / grow_finished (:418-611) plus the host `.item()` of the stop test (:613-667) becomes one launch.
  *
@@ -724,7 +724,7 @@ int cvcl_lstm_cell_bwd_first(const float* gates_act, const float* c_save, const 
                              float* dc, float* d_gates, float* dh_carry, int B, int L, int Hd, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Per-word Grad-CAM of the captioning LM (csrc/caption_cam.hip).  Replaces the loop of the reference's
+ * Per-word Grad-CAM of the captioning LM (csrc/lstm.hip, csrc/head.hip).  Replaces the loop of the reference's
  * analysis_tools/multimodal_visualization.py:26-41 -- one loss[0, step - 1].backward(retain_graph=True) per word and image -- by
  * one multi-seed BPTT sweep: every (caption b, position p) is a seed row whose chain d loss[b, p] / d (h0, c0) runs over the saved
  * gate activations of caption b.  The seed state dh, dc is seed-major ([L][B][Hd]: block p = the chains that start at position p),

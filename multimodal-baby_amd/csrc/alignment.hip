@@ -265,14 +265,9 @@ __device__ __forceinline__ Moments merge(const Moments& x, const Moments& y) {
     return r;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // sum over the 256 threads, the same value in every thread (xor tree per wave, then the four waves in order)
 __device__ __forceinline__ double block_sum_f64(double v, double* scratch) {
-    v = wave_sum_f64(v);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -380,7 +375,7 @@ __global__ __launch_bounds__(256) void paired_l2_kernel(const float* __restrict_
         const double t = ((double)xr[k] - (double)yr[k]) + (double)eps;
         s += t * t;
     }
-    s = wave_sum_f64(s);
+    s = wave_sum(s);
     if (lane == 0) d[row] = (float)sqrt(s);
 }
 

@@ -310,11 +310,6 @@ __device__ inline float gram_ema(float r, float x, float m) { return fmaf(m, x, 
 // fp64, where var = E[y^2] - mean^2 loses nothing that matters (2^-53 mean^2 / var).  The sums over k: butterflies inside a wave, the
 // sixteen waves in a fixed order.
 constexpr int GF_CH = 4;
-__device__ inline double gf_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 template <int K>
 __global__ __launch_bounds__(1024) void bn_from_gram_kernel(const double* __restrict__ Gd, double inv_count, double bessel,
                                                             const bf16_t* __restrict__ W,
@@ -380,7 +375,7 @@ __global__ __launch_bounds__(1024) void bn_from_gram_kernel(const double* __rest
             q += wsh[kk + 64 * i][c] * r[i][c];
             m += wsh[kk + 64 * i][c] * sk[i];
         }
-        q = gf_wave_sum(q); m = gf_wave_sum(m);
+        q = wave_sum(q); m = wave_sum(m);
         if (kk == 0) { red[wv][c] = q; red[wv][GF_CH + c] = m; }
     }
     __syncthreads();
@@ -418,13 +413,8 @@ int gram_grid(long tiles) {
 template <int NT>
 int gram_launch(const GramDev& d, int grid, hipStream_t st) {
     static CvclLdsAttr attr;
-    if (!attr.ready()) {
-        if (hipFuncSetAttribute((const void*)gram_pro_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, gp_lds_bytes<NT>()) != hipSuccess) {
-            cvcl_set_error("cvcl_conv1x1_gram: cannot raise the dynamic LDS limit");
-            return CVCL_ELAUNCH;
-        }
-        attr.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)gram_pro_kernel<NT>, gp_lds_bytes<NT>(), "cvcl_conv1x1_gram")) return rc;
+    attr.mark();
     hipLaunchKernelGGL(gram_pro_kernel<NT>, dim3(grid), dim3(256 + gp_producer_threads<NT>()), gp_lds_bytes<NT>(), st, d);
     return CVCL_OK;
 }

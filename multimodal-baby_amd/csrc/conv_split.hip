@@ -237,8 +237,7 @@ int cvcl_stem_split(const float* x, const void* w, float* y, float* stats, int s
 
 int cvcl_gconv_split(const float* x, const float* a_scale, const float* a_shift, float act_floor, const void* w, float* y, float* stats,
                      int stats_rows, const float* centre, int B, int H, int W, int C, int cg, int stride, void* stream) {
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    CVCL_CHECK_ARG(x && w && y && C % CS_CO == 0 && (cg == 4 || cg == 8 || cg == 16 || cg == 32) && al16(x),
+    CVCL_CHECK_ARG(x && w && y && C % CS_CO == 0 && (cg == 4 || cg == 8 || cg == 16 || cg == 32) && cvcl_aligned16(x),
                    "cvcl_gconv3x3(CVCL_F32X3): needs C %% 32 == 0, 4 / 8 / 16 / 32 channels per group and a 16-byte aligned input");
     ConvSplitDev d = {};
     d.x = x; d.a_scale = a_scale; d.a_shift = a_shift; d.act_floor = act_floor;

@@ -42,8 +42,18 @@ struct CvclLdsAttr {
     std::atomic<unsigned long long> devs{0};
     static int dev() { int d = 0; (void)hipGetDevice(&d); return d & 63; }
     bool ready() const { return (devs.load(std::memory_order_acquire) >> dev()) & 1ull; }
-    void mark() { devs.fetch_or(1ull << dev(), std::memory_order_release); }
+    void mark() { if (!ready()) devs.fetch_or(1ull << dev(), std::memory_order_release); }
 };
+// Raise the dynamic LDS limit of `kernel` to `bytes` unless `attr` says this device has it already.  The caller marks `attr` after
+// its last kernel under that flag (a site that launches two kernels calls this twice and marks once).
+static inline int cvcl_raise_lds_limit(CvclLdsAttr& attr, const void* kernel, int bytes, const char* entry) {
+    if (attr.ready()) return CVCL_OK;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+        cvcl_set_error("%s: cannot raise the dynamic LDS limit (%d bytes)", entry, bytes);
+        return CVCL_ELAUNCH;
+    }
+    return CVCL_OK;
+}
 #endif
 
 #define CVCL_CHECK_ARG(cond, ...)                \
@@ -65,6 +75,15 @@ struct CvclLdsAttr {
     } while (0)
 
 __host__ __device__ static inline int cvcl_div_up(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Host-side launch helpers.  cvcl_grid: workgroups of a grid-stride launch over `items` at `per_block` items each, at least 1 and at
+// most `cap`.  Several kernels write one partial per workgroup, so the cap is part of their result: every call site names its own.
+static inline int cvcl_grid(long items, int per_block, int cap) {
+    const long g = (items + per_block - 1) / per_block;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+// true for NULL: an optional operand that is absent does not stand in the way of the 16-byte paths
+static inline bool cvcl_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // dtype validation (ABI v7).  An entry that takes a dtype accepts CVCL_F32 and CVCL_BF16 and refuses everything else with CVCL_EINVAL
 // before it enqueues anything; the entries of the trunk forward (include/cvcl_hip.h "Conventions") accept CVCL_F32X3 as well, and the
@@ -161,6 +180,11 @@ template <typename V> __device__ __forceinline__ void stream_store(V v, V* dst) 
 
 // ---- wave / block reductions ---------------------------------------------------------------
 __device__ inline float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ inline double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;

@@ -882,13 +882,8 @@ int launch_gemm_v(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
     if (a->stats) CVCL_CHECK_ARG(a->stats_rows == CVCL_STATS_ACCUMULATE || a->stats_rows >= gm, "cvcl_gemm: stats_rows %d < grid_m %d", a->stats_rows, gm);
     static CvclLdsAttr attr_set;
     constexpr int lds = gemm_lds_bytes<T>();
-    if (!attr_set.ready()) {
-        if (hipFuncSetAttribute((const void*)gemm_kernel<T, PRO, LEAN, TR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            cvcl_set_error("cvcl_gemm: cannot raise dynamic LDS limit to %d", lds);
-            return CVCL_ELAUNCH;
-        }
-        attr_set.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr_set, (const void*)gemm_kernel<T, PRO, LEAN, TR>, lds, "cvcl_gemm")) return rc;
+    attr_set.mark();
     dim3 grid(gm, cvcl_div_up(a->N, BN));
     CvclProfScope prof(stream, sizeof(T) == 2 ? CVCL_K_GEMM : CVCL_K_GEMM_F32);
     hipLaunchKernelGGL((gemm_kernel<T, PRO, LEAN, TR>), grid, dim3(256), lds, stream, d);
@@ -1157,8 +1152,7 @@ inline int pick_gemm8w(int dtype, const cvcl_gemm_args* a) {
     if (a->a_scale || a->exp_scale || a->c_scale || a->C_pre || a->G) return -1;
     if (a->ln_stats && (a->R || !a->ln_colsum || !a->bias || a->row_part)) return -1;
     if (a->row_part && (!a->R || a->act != CVCL_ACT_NONE)) return -1;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (!al16(a->A) || !al16(a->W) || !al16(a->C) || !al16(a->R) || !al16(a->bias) || (a->R && a->ldr % 8)) return -1;
+    if (!cvcl_aligned16(a->A) || !cvcl_aligned16(a->W) || !cvcl_aligned16(a->C) || !cvcl_aligned16(a->R) || !cvcl_aligned16(a->bias) || (a->R && a->ldr % 8)) return -1;
     long a_rows = a->M;
     if (a->gather_stride > 1) {                              // strided 1x1 convolution (the downsample branch of blocks 2.0 / 3.0 / 4.0)
         if (a->gather_ho <= 0 || a->gather_wo <= 0 || a->M % (a->gather_ho * a->gather_wo)) return -1;
@@ -1200,13 +1194,8 @@ int launch_gemm_glds(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
     const int gm = grid_m_query<bf16_t>(a->M, a->N);
     if (a->stats) CVCL_CHECK_ARG(a->stats_rows == CVCL_STATS_ACCUMULATE || a->stats_rows >= gm, "cvcl_gemm: stats_rows %d < grid_m %d", a->stats_rows, gm);
     static CvclLdsAttr attr_set;
-    if (!attr_set.ready()) {
-        if (hipFuncSetAttribute((const void*)gemm_glds_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, GL_LDS) != hipSuccess) {
-            cvcl_set_error("cvcl_gemm: cannot raise dynamic LDS limit to %d", GL_LDS);
-            return CVCL_ELAUNCH;
-        }
-        attr_set.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr_set, (const void*)gemm_glds_kernel<EPI>, GL_LDS, "cvcl_gemm")) return rc;
+    attr_set.mark();
     dim3 grid(gm, a->N / BN);
     CvclProfScope prof(stream, CVCL_K_GEMM);
     hipLaunchKernelGGL(gemm_glds_kernel<EPI>, grid, dim3(256), GL_LDS, stream, d);
@@ -1227,9 +1216,8 @@ int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
     d.R = a->R; d.ldr = a->ldr; d.stats = a->stats; d.centre = a->centre;
     d.stats_acc = a->stats && a->stats_rows == CVCL_STATS_ACCUMULATE;
     d.c_scale = a->c_scale; d.c_shift = a->c_shift; d.r_scale = a->r_scale; d.r_shift = a->r_shift;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    d.vec_in = (a->K % EPC == 0) && (a->lda % EPC == 0) && (a->ldw % EPC == 0) && al16(a->A) && al16(a->W);
-    d.vec_out = (a->ldc % EPC == 0) && al16(a->C) && (!a->R || ((a->ldr % EPC == 0) && al16(a->R)));
+    d.vec_in = (a->K % EPC == 0) && (a->lda % EPC == 0) && (a->ldw % EPC == 0) && cvcl_aligned16(a->A) && cvcl_aligned16(a->W);
+    d.vec_out = (a->ldc % EPC == 0) && cvcl_aligned16(a->C) && (!a->R || ((a->ldr % EPC == 0) && cvcl_aligned16(a->R)));
     d.num_m_tiles = cvcl_div_up(a->M, BM);
     d.C2 = nullptr;
     d.a_rowsum = a->a_rowsum;
@@ -1277,7 +1265,6 @@ int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
     }
     CVCL_CHECK_ARG(a->C && !a->c_scale, "cvcl_gemm: statistics-only / BN-tail epilogues need the direct-to-LDS bf16 path");
     if constexpr (sizeof(T) == 4) {
-        auto al16p = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
         // measured cost models (us, MI355X): the split-K VALU kernel runs ~13.4 GMAC/s-per-us of work on any shape; the 128-tile
         // fp32 MFMA kernel needs ~4.6 us per 64-deep K step per round of <= 256 tiles, whatever M and N are (4.2 with split
         // arithmetic: its K step is bound by the serial load -> LDS -> multiply structure at one wave per SIMD, not by the matrix
@@ -1289,7 +1276,7 @@ int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
         const double t_split64 = split64_ok ? 6.0 + (double)cvcl_div_up(a->M, TS) * cvcl_div_up(a->N, TS) * cvcl_div_up(a->K, 32) / 1024.0 +
                                               0.25 * cvcl_div_up(a->K, 32) : 1e30;
         if (pro_kind(a) == 0 && !(a->gather_stride > 1) && !a->stats && !a->R && !a->centre && a->act == CVCL_ACT_NONE && a->K % 4 == 0 &&
-            a->lda % 4 == 0 && a->ldw % 4 == 0 && al16p(a->A) && al16p(a->W) && !a->a_rowsum && t_small < t_mfma128 && t_small < t_split64) {
+            a->lda % 4 == 0 && a->ldw % 4 == 0 && cvcl_aligned16(a->A) && cvcl_aligned16(a->W) && !a->a_rowsum && t_small < t_mfma128 && t_small < t_split64) {
             CvclProfScope prof(stream, CVCL_K_GEMM_F32);
             const dim3 grid(cvcl_div_up(a->N, 16), cvcl_div_up(a->M, 16));
 #define CVCL_SMALL(TR_) hipLaunchKernelGGL(gemm_f32_small_kernel<TR_>, grid, dim3(256), 0, stream, (const float*)a->A, (const float*)a->W, \
@@ -1301,7 +1288,7 @@ int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
         }
         if (split64_ok && t_split64 < t_mfma128) {
             // the tail's products: many 64 x 64 workgroups (gemm_f32_split_kernel)
-            const int vec = (a->lda % 4 == 0) && (a->ldw % 4 == 0) && al16p(a->A) && al16p(a->W) && al16p(a->C);
+            const int vec = (a->lda % 4 == 0) && (a->ldw % 4 == 0) && cvcl_aligned16(a->A) && cvcl_aligned16(a->W) && cvcl_aligned16(a->C);
             CvclProfScope prof(stream, CVCL_K_GEMM_F32);
             const dim3 grid(cvcl_div_up(a->M, TS), cvcl_div_up(a->N, TS));
 #define CVCL_SPLIT(TR_) hipLaunchKernelGGL(gemm_f32_split_kernel<TR_>, grid, dim3(256), 0, stream, (const float*)a->A, (const float*)a->W, \

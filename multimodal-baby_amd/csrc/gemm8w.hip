@@ -38,13 +38,10 @@ int g8_grid_m(int tiles_m, int ncol) {
 template <int MI, int EPI, bool LNF = false, int ACT = CVCL_ACT_NONE>
 int g8_launch(const g8w::Dev& d, int grid, hipStream_t stream) {
     static CvclLdsAttr attr;
-    if (!attr.ready()) {
-        if (hipFuncSetAttribute((const void*)g8w::gemm8w_kernel<MI, EPI, LNF, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, g8w::LDS_BYTES) != hipSuccess) {
-            cvcl_set_error("cvcl_gemm8w: cannot raise the dynamic LDS limit to %d", g8w::LDS_BYTES);
-            return CVCL_ELAUNCH;
-        }
-        attr.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)g8w::gemm8w_kernel<MI, EPI, LNF, ACT>, g8w::LDS_BYTES,
+                                            "cvcl_gemm8w"))
+        return rc;
+    attr.mark();
     hipLaunchKernelGGL((g8w::gemm8w_kernel<MI, EPI, LNF, ACT>), dim3(grid), dim3(512), g8w::LDS_BYTES, stream, d);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
@@ -153,9 +150,8 @@ extern "C" int cvcl_gemm8w(int epi, const cvcl_gemm_args* a, void* stream) {
                    "cvcl_gemm8w: ln_stats goes with the bias / activation epilogue and needs ln_colsum and the folded bias");
     CVCL_CHECK_ARG(!a->row_part || (epi == 1 && a->R), "cvcl_gemm8w: row_part goes with the bias + residual epilogue");
     CVCL_CHECK_ARG(!a->ln_colsum || a->ln_stats, "cvcl_gemm8w: ln_colsum without ln_stats");
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    CVCL_CHECK_ARG(al16(a->A) && al16(a->W) && al16(a->C) && al16(a->R) && al16(a->bias) && (!a->R || a->ldr % 8 == 0) &&
-                       al16(a->ln_stats) && al16(a->ln_colsum) && (((uintptr_t)a->row_part & 7) == 0),
+    CVCL_CHECK_ARG(cvcl_aligned16(a->A) && cvcl_aligned16(a->W) && cvcl_aligned16(a->C) && cvcl_aligned16(a->R) && cvcl_aligned16(a->bias) && (!a->R || a->ldr % 8 == 0) &&
+                       cvcl_aligned16(a->ln_stats) && cvcl_aligned16(a->ln_colsum) && (((uintptr_t)a->row_part & 7) == 0),
                    "cvcl_gemm8w: operands must be 16-byte aligned");
     const bool gather = a->gather_stride > 1;
     if (gather)

@@ -461,13 +461,10 @@ namespace {
 template <int MT, int KIND, int ACT>
 int launch_8f(const g8f::Dev& d, int grid, hipStream_t st) {
     static CvclLdsAttr attr;
-    if (!attr.ready()) {
-        if (hipFuncSetAttribute((const void*)g8f::gemm8f_kernel<MT, KIND, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, g8f::LDS_BYTES) != hipSuccess) {
-            cvcl_set_error("cvcl_gemm_fp8: cannot raise the dynamic LDS limit to %d", g8f::LDS_BYTES);
-            return CVCL_ELAUNCH;
-        }
-        attr.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)g8f::gemm8f_kernel<MT, KIND, ACT>, g8f::LDS_BYTES,
+                                            "cvcl_gemm_fp8"))
+        return rc;
+    attr.mark();
     hipLaunchKernelGGL((g8f::gemm8f_kernel<MT, KIND, ACT>), dim3(grid), dim3(512), g8f::LDS_BYTES, st, d);
     return CVCL_OK;
 }
@@ -484,13 +481,8 @@ int pick_8f(const float* a_scale, const void* a_bs, const void* C, const void* c
 template <int ACT, bool MXA, int MXOUT>
 int launch_fp8(const F8Dev& d, dim3 grid, hipStream_t st) {
     static CvclLdsAttr attr_set;
-    if (!attr_set.ready()) {
-        if (hipFuncSetAttribute((const void*)gemm_fp8_kernel<ACT, MXA, MXOUT>, hipFuncAttributeMaxDynamicSharedMemorySize, F8_LDS) != hipSuccess) {
-            cvcl_set_error("cvcl_gemm_fp8: cannot raise the dynamic LDS limit");
-            return CVCL_ELAUNCH;
-        }
-        attr_set.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr_set, (const void*)gemm_fp8_kernel<ACT, MXA, MXOUT>, F8_LDS, "cvcl_gemm_fp8")) return rc;
+    attr_set.mark();
     hipLaunchKernelGGL((gemm_fp8_kernel<ACT, MXA, MXOUT>), grid, dim3(256), F8_LDS, st, d);
     return CVCL_OK;
 }
@@ -531,8 +523,7 @@ extern "C" int cvcl_gemm_fp8_ex(const cvcl_gemm_fp8_args* x, void* stream) {
     CVCL_CHECK_ARG(K % 128 == 0 && N % 128 == 0 && lda % 16 == 0 && ldw % 16 == 0 && (!C || ldc % 8 == 0) && (!c8 || ldc8 % 8 == 0) &&
                        (!R || ldr % 8 == 0),
                    "cvcl_gemm_fp8: needs K %% 128 == 0, N %% 128 == 0 and 16-byte aligned rows (M %d N %d K %d)", M, N, K);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    CVCL_CHECK_ARG(al16(A8) && al16(W8) && al16(C) && al16(R) && al16(bias) && al16(w_scale) && (((uintptr_t)c8 & 7) == 0) &&
+    CVCL_CHECK_ARG(cvcl_aligned16(A8) && cvcl_aligned16(W8) && cvcl_aligned16(C) && cvcl_aligned16(R) && cvcl_aligned16(bias) && cvcl_aligned16(w_scale) && (((uintptr_t)c8 & 7) == 0) &&
                        (((uintptr_t)a_block_scales & 3) == 0), "cvcl_gemm_fp8: operands must be 16-byte aligned");
     CVCL_CHECK_ARG(act == CVCL_ACT_NONE || act == CVCL_ACT_RELU || act == CVCL_ACT_GELU, "cvcl_gemm_fp8: activation %d", act);
     CVCL_CHECK_ARG(!c8 || !R || producer, "cvcl_gemm_fp8: the MX output mode takes no residual");

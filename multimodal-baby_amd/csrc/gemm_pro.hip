@@ -434,13 +434,8 @@ template <int KT, int MODE, int D>
 int pro_launch(const ProDev& d, dim3 grid, hipStream_t stream) {
     static CvclLdsAttr attr;
     constexpr int lds = pro_lds_bytes<KT>();
-    if (!attr.ready()) {
-        if (hipFuncSetAttribute((const void*)gemm_pro_kernel<KT, MODE, D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            cvcl_set_error("cvcl_gemm_pro: cannot raise the dynamic LDS limit to %d", lds);
-            return CVCL_ELAUNCH;
-        }
-        attr.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)gemm_pro_kernel<KT, MODE, D>, lds, "cvcl_gemm_pro")) return rc;
+    attr.mark();
     hipLaunchKernelGGL((gemm_pro_kernel<KT, MODE, D>), grid, dim3(512), lds, stream, d);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
@@ -457,11 +452,10 @@ extern "C" int cvcl_gemm_pro_supported(const cvcl_gemm_args* a) {
     if (plain && (a->c_scale || a->A2 || a->W2)) return 0;
     if ((a->K != 128 && a->K != 256) || a->N % PN != 0 || a->M < 1) return 0;
     if (a->lda % 8 || a->ldw % 8 || (a->C && a->ldc % 8) || a->gather_stride > 1 || a->exp_scale || a->bias || a->C_pre || a->G) return 0;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (!al16(a->A) || !al16(a->W) || !al16(a->C) || !al16(a->R)) return 0;
+    if (!cvcl_aligned16(a->A) || !cvcl_aligned16(a->W) || !cvcl_aligned16(a->C) || !cvcl_aligned16(a->R)) return 0;
     if (a->c_scale && a->A2)                              // tail with the downsample branch recomputed from the block input
         return a->c_shift && !a->R && a->C && !a->stats && a->act == CVCL_ACT_RELU && a->W2 && a->K2 == K2 && a->K == 128 && a->r_scale &&
-               a->r_shift && a->lda2 % 8 == 0 && a->ldw2 % 8 == 0 && al16(a->A2) && al16(a->W2);
+               a->r_shift && a->lda2 % 8 == 0 && a->ldw2 % 8 == 0 && cvcl_aligned16(a->A2) && cvcl_aligned16(a->W2);
     if (a->A2 || a->W2) return 0;
     if (a->c_scale) return a->c_shift && a->R && a->C && !a->stats && a->ldr % 8 == 0 && a->act == CVCL_ACT_RELU &&
                            (a->r_scale == nullptr) == (a->r_shift == nullptr);

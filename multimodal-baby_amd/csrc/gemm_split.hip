@@ -239,13 +239,8 @@ int split_grid_m(int M, int N) {
 template <int NT>
 int launch_split(const SplitDev& d, int gm, hipStream_t stream) {
     static CvclLdsAttr attr;
-    if (!attr.ready()) {
-        if (hipFuncSetAttribute((const void*)gemm_split_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, split_lds_bytes<NT>()) != hipSuccess) {
-            cvcl_set_error("cvcl_gemm: cannot raise the dynamic LDS limit of the split kernel");
-            return CVCL_ELAUNCH;
-        }
-        attr.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)gemm_split_kernel<NT>, split_lds_bytes<NT>(), "cvcl_gemm")) return rc;
+    attr.mark();
     hipLaunchKernelGGL(gemm_split_kernel<NT>, dim3(gm, d.N / SP_BN), dim3(256), split_lds_bytes<NT>(), stream, d);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
@@ -268,13 +263,12 @@ int cvcl_pack_split_dense(const float* w, void* out, long elems, void* stream) {
 }
 
 int cvcl_gemm_split(const cvcl_gemm_args* a, void* stream) {
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     CVCL_CHECK_ARG(!a->a_scale && !a->bias && !a->exp_scale && !a->R && !a->c_scale && !a->centre && !a->C_pre && !a->G && !a->A2 &&
                        !a->a_trans && !a->w_trans && !a->a_rowsum && !a->f32_split && !a->ln_stats && !a->ln_colsum && !a->row_part &&
                        a->act == CVCL_ACT_NONE,
                    "cvcl_gemm(CVCL_F32X3): plain products (+ BN statistics, row gather) only");
     CVCL_CHECK_ARG(a->N % SP_BN == 0 && a->K % SP_BK == 0 && a->lda % 4 == 0 && a->ldw % 8 == 0 && a->ldw >= a->K && a->lda >= a->K &&
-                       (!a->C || a->ldc >= a->N) && al16(a->A) && al16(a->W),
+                       (!a->C || a->ldc >= a->N) && cvcl_aligned16(a->A) && cvcl_aligned16(a->W),
                    "cvcl_gemm(CVCL_F32X3): needs N %% 128 == 0, K %% 32 == 0, lda %% 4 == 0, ldw %% 8 == 0 and 16-byte aligned A / W "
                    "(M %d N %d K %d lda %d ldw %d)", a->M, a->N, a->K, a->lda, a->ldw);
     const int gm = split_grid_m(a->M, a->N);

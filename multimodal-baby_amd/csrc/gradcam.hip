@@ -254,8 +254,6 @@ __global__ __launch_bounds__(256) void act_grad_kernel(const TA* __restrict__ ac
     }
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int cvcl_gradcam_pairs(int dtype, const void* map, int N, int HW, int C, const float* P, int M, int mode, int k,
@@ -266,7 +264,7 @@ extern "C" int cvcl_gradcam_pairs(int dtype, const void* map, int N, int HW, int
     CVCL_CHECK_ARG(C % GC_K == 0, "cvcl_gradcam_pairs: C = %d is not a multiple of %d", C, GC_K);
     CVCL_CHECK_ARG((Q && S && norm) || (!Q && !S && !norm), "cvcl_gradcam_pairs: Q, s and norm go together (normalised features) or not at all");
     CVCL_CHECK_ARG(!norm || eps > 0.f, "cvcl_gradcam_pairs: eps must be positive");
-    CVCL_CHECK_ARG(al16(map) && al16(P) && (!Q || al16(Q)), "cvcl_gradcam_pairs: map / P / Q must be 16-byte aligned");
+    CVCL_CHECK_ARG(cvcl_aligned16(map) && cvcl_aligned16(P) && (!Q || cvcl_aligned16(Q)), "cvcl_gradcam_pairs: map / P / Q must be 16-byte aligned");
     if (mode == CVCL_GRADCAM_ALL) {
         CVCL_CHECK_ARG(k == 0, "cvcl_gradcam_pairs: all pairs takes k = 0 (got %d)", k);
     } else if (mode == CVCL_GRADCAM_BLOCK_IMAGE) {
@@ -297,7 +295,7 @@ extern "C" int cvcl_bicubic_resize(const float* x, float* y, int maps, int h, in
     CVCL_CHECK_ARG(maps > 0 && h > 0 && w > 0 && H > 0 && W > 0, "cvcl_bicubic_resize: sizes must be positive (maps %d %dx%d -> %dx%d)",
                    maps, h, w, H, W);
     CVCL_CHECK_ARG(w <= BIC_LDS, "cvcl_bicubic_resize: input width %d > %d", w, BIC_LDS);
-    CVCL_CHECK_ARG(al16(y), "cvcl_bicubic_resize: output must be 16-byte aligned");
+    CVCL_CHECK_ARG(cvcl_aligned16(y), "cvcl_bicubic_resize: output must be 16-byte aligned");
     const int rpw = max(1, min(16, BIC_LDS / w));
     const int tpm = cvcl_div_up(H, rpw);
     CVCL_CHECK_ARG((long)maps * tpm <= 0x7fffffffL, "cvcl_bicubic_resize: grid too large");

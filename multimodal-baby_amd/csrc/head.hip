@@ -153,21 +153,31 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* __restrict
     if (lane == 0) norm[row] = nrm;
 }
 
+// Backward of F.normalize on B K gradient rows, K per (y, norm) row.  dy is seed-major (row p B + b: the sweep of the per-word
+// Grad-CAM, include/cvcl_hip.h), dx image-major (row b K + p), each row through the backward with its image's own (y[b], norm[b]);
+// K = 1 is the plain row-by-row backward.  y == NULL: the reordering alone.  One wave per row, 4 rows per workgroup.
 __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict__ y, const float* __restrict__ norm,
-                                                         const float* __restrict__ dy, float* __restrict__ dx,
-                                                         int N, int E, float eps) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= N) return;
-    const float* yr = y + (long)row * E;
-    const float* gr = dy + (long)row * E;
+                                                         const float* __restrict__ dy, float* __restrict__ dx, int B, int K, int E,
+                                                         float eps) {
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= (long)B * K) return;
+    const int p = (int)(row / B), b = (int)(row % B);
+    const float* gr = dy + row * E;
+    float* out = dx + ((long)b * K + p) * E;
+    if (y == nullptr) {
+        for (int e = lane; e < E; e += 64) out[e] = gr[e];
+        return;
+    }
+    const float* yr = y + (long)b * E;
     float dot = 0.f;
     for (int e = lane; e < E; e += 64) dot = fmaf(yr[e], gr[e], dot);
     dot = wave_sum(dot);
-    const float nrm = norm[row];
+    const float nrm = norm[b];
     if (nrm < eps) {                 // clamp_min active: y = x / eps, no projection term
-        for (int e = lane; e < E; e += 64) dx[(long)row * E + e] = gr[e] / eps;
+        for (int e = lane; e < E; e += 64) out[e] = gr[e] / eps;
     } else {
-        for (int e = lane; e < E; e += 64) dx[(long)row * E + e] = (gr[e] - yr[e] * dot) / nrm;
+        for (int e = lane; e < E; e += 64) out[e] = (gr[e] - yr[e] * dot) / nrm;
     }
 }
 
@@ -419,7 +429,21 @@ extern "C" int cvcl_l2norm_bwd(const float* y, const float* norm, const float* d
                                void* stream) {
     CVCL_CHECK_ARG(y && norm && dy && dx && N > 0 && E > 0, "cvcl_l2norm_bwd: bad args");
     CvclProfScope prof(stream, CVCL_K_HEAD);
-    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(cvcl_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, y, norm, dy, dx, N, E, eps);
+    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(cvcl_div_up(N, 4)), dim3(256), 0, (hipStream_t)stream, y, norm, dy, dx, N, 1, E, eps);
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
+}
+
+// the gradient rows of the per-word Grad-CAM sweep, seed-major, -> image-major rows through the backward of F.normalize
+extern "C" int cvcl_l2norm_bwd_seeds(const float* y, const float* norm, const float* dy, float* dx, int B, int K, int E, float eps,
+                                     void* stream) {
+    CVCL_CHECK_ARG(dy && dx, "cvcl_l2norm_bwd_seeds: null pointer (dy / dx)");
+    CVCL_CHECK_ARG((y == nullptr) == (norm == nullptr), "cvcl_l2norm_bwd_seeds: y and norm go together");
+    CVCL_CHECK_ARG(dy != dx, "cvcl_l2norm_bwd_seeds: dx must not alias dy (the rows are reordered)");
+    CVCL_CHECK_ARG(B >= 1 && K >= 1 && E >= 1, "cvcl_l2norm_bwd_seeds: bad sizes (B %d, K %d, E %d)", B, K, E);
+    CvclProfScope prof(stream, CVCL_K_HEAD);
+    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(cvcl_div_up((long)B * K, 4)), dim3(256), 0, (hipStream_t)stream, y, norm, dy, dx, B, K, E,
+                       eps);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }

@@ -1152,12 +1152,6 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const T* __restrict__ x, f
     }
 }
 
-int grid_for(long total, int per_block = 256, int cap = 4096) {
-    long g = (total + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Grouped train-mode BatchNorm (linear-probe scoring, cvcl_resnext50_fwd_grouped): the batch is T consecutive groups of
 // rows_g rows, and each group is normalised on its own mean and biased variance.  fp32 storage only (CVCL_F32, CVCL_F32X3).
@@ -1394,9 +1388,9 @@ extern "C" int cvcl_pack_conv_weight(int dtype, int kind, const float* w_oihw, v
         return CVCL_EINVAL;
     }
     if (dtype == CVCL_F32) {                       // parity mode keeps the reference layout
-        hipLaunchKernelGGL(cast_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s, w_oihw, (float*)out, n);
+        hipLaunchKernelGGL(cast_kernel<float>, dim3(cvcl_grid(n, 256, 4096)), dim3(256), 0, s, w_oihw, (float*)out, n);
     } else if (kind == CVCL_PACK_DENSE) {
-        hipLaunchKernelGGL(cast_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, s, w_oihw, (bf16_t*)out, n);
+        hipLaunchKernelGGL(cast_kernel<bf16_t>, dim3(cvcl_grid(n, 256, 4096)), dim3(256), 0, s, w_oihw, (bf16_t*)out, n);
     } else if (kind == CVCL_PACK_STEM7) {
         CVCL_CHECK_ARG(cout == 64 && cin_per_group == 3 && k == 7, "cvcl_pack_conv_weight: stem must be 64x3x7x7");
         hipLaunchKernelGGL(pack_stem_kernel, dim3(cvcl_div_up(4 * 6 * 512, 256)), dim3(256), 0, s, w_oihw, (bf16_t*)out);
@@ -1458,19 +1452,14 @@ extern "C" int cvcl_stem_conv7x7(int dtype, const float* x_nchw, const void* w_p
         while (TH > 1 && lds_of(TH) > 150 * 1024) --TH;
         if (lds_of(TH) <= 150 * 1024) {
             static CvclLdsAttr attr;
-            if (!attr.ready()) {
-                if (hipFuncSetAttribute((const void*)stem_tiled_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                    cvcl_set_error("cvcl_stem_conv7x7: cannot raise the dynamic LDS limit");
-                    return CVCL_ELAUNCH;
-                }
-                attr.mark();
-            }
+            if (const int rc = cvcl_raise_lds_limit(attr, (const void*)stem_tiled_f32_kernel, 160 * 1024, "cvcl_stem_conv7x7")) return rc;
+            attr.mark();
             const int bands = cvcl_div_up(Ho, TH);
             const long items = (long)B * bands;
             hipLaunchKernelGGL(stem_tiled_f32_kernel, dim3((unsigned)(items < 1024 ? items : 1024)), dim3(256), lds_of(TH), s, x_nchw,
                                (const float*)w_packed, (float*)y_nhwc, centre, B, H, W, TH, bands);
         } else {
-            hipLaunchKernelGGL(stem_direct_f32_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, s, x_nchw,
+            hipLaunchKernelGGL(stem_direct_f32_kernel, dim3(cvcl_grid(total, 256, 8192)), dim3(256), 0, s, x_nchw,
                                (const float*)w_packed, (float*)y_nhwc, centre, B, H, W);
         }
     }
@@ -1492,13 +1481,8 @@ extern "C" int cvcl_stem_pool(int dtype, const float* x_nchw, const void* w_pack
                    2 * (STEMP_BW - 2), dtype, H, W);
     const size_t lds = (size_t)3 * STEMP_ROWS * STEM_PITCH * 4 + (size_t)STEMP_CR * STEMP_BW * 128 + 3 * 64 * 4;
     static CvclLdsAttr attr;
-    if (!attr.ready()) {
-        if (hipFuncSetAttribute((const void*)stem_pool_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            cvcl_set_error("cvcl_stem_pool: cannot raise the dynamic LDS limit");
-            return CVCL_ELAUNCH;
-        }
-        attr.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)stem_pool_mfma_kernel, (int)lds, "cvcl_stem_pool")) return rc;
+    attr.mark();
     const int Hp = (H / 2 - 1) / 2 + 1;
     const int items = B * cvcl_div_up(Hp, STEMP_TP);
     int dev = 0, cus = 256;
@@ -1519,7 +1503,7 @@ extern "C" int cvcl_bn_relu_maxpool(int dtype, const void* x, const float* scale
     CvclProfScope prof(stream, CVCL_K_MAXPOOL);
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long total = (long)B * ((Ho + POOL_ROWS - 1) / POOL_ROWS) * Wo * (C / 8);          // a thread owns POOL_ROWS output rows
-    const int grid = grid_for(total, 256, 8192);
+    const int grid = cvcl_grid(total, 256, 8192);
     if (dtype == CVCL_F32)
         hipLaunchKernelGGL(bn_relu_maxpool_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream,
                            (const float*)x, scale, shift, (float*)y, B, H, W, C);
@@ -1612,13 +1596,8 @@ static int gconv3x3_impl(int dtype, const void* x, const float* a_scale, const f
         static CvclLdsAttr attr_set[2][2][11];                 // per instantiation (wide, short m-tile table, slots)
         auto launch = [&](auto kern) -> int {
             CvclLdsAttr& done = attr_set[cg == 32][g.TH * Wo <= 64][slots <= 4 ? 4 : slots <= 6 ? 6 : slots <= 8 ? 8 : 10];
-            if (!done.ready()) {
-                if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                    cvcl_set_error("cvcl_gconv3x3: cannot raise the dynamic LDS limit");
-                    return CVCL_ELAUNCH;
-                }
-                done.mark();
-            }
+            if (const int rc = cvcl_raise_lds_limit(done, (const void*)kern, 160 * 1024, "cvcl_gconv3x3")) return rc;
+            done.mark();
             hipLaunchKernelGGL(kern, dim3(g.grid_x, C / GC_CS), dim3(256), g.lds, s, d);
             return CVCL_OK;
         };
@@ -1653,13 +1632,8 @@ static int gconv3x3_impl(int dtype, const void* x, const float* a_scale, const f
             if (gx > items) gx = items;
             static CvclLdsAttr attr[4];
             auto launch = [&](auto kern, int slot) -> int {
-                if (!attr[slot].ready()) {
-                    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                        cvcl_set_error("cvcl_gconv3x3: cannot raise the dynamic LDS limit");
-                        return CVCL_ELAUNCH;
-                    }
-                    attr[slot].mark();
-                }
+                if (const int rc = cvcl_raise_lds_limit(attr[slot], (const void*)kern, 160 * 1024, "cvcl_gconv3x3")) return rc;
+                attr[slot].mark();
                 hipLaunchKernelGGL(kern, dim3((unsigned)gx, slabs), dim3(256), lds_of(TH), s, (const float*)x, a_scale, a_shift,
                                    (const float*)w_packed, (float*)y, centre, B, H, W, C, stride, Ho, Wo, TH, bands, plane_p_of(TH), act_floor);
                 return CVCL_OK;
@@ -1668,7 +1642,7 @@ static int gconv3x3_impl(int dtype, const void* x, const float* a_scale, const f
                          : cg == 16 ? launch(gconv_tiled_f32_kernel<16>, 2) : launch(gconv_tiled_f32_kernel<32>, 3);
             if (rc) return rc;
         } else {
-            hipLaunchKernelGGL(gconv_direct_f32_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, s, (const float*)x, a_scale,
+            hipLaunchKernelGGL(gconv_direct_f32_kernel, dim3(cvcl_grid(total, 256, 8192)), dim3(256), 0, s, (const float*)x, a_scale,
                                a_shift, (const float*)w_packed, (float*)y, centre, B, H, W, C, cg, stride, Ho, Wo, act_floor);
         }
     }
@@ -1698,7 +1672,7 @@ extern "C" int cvcl_bn_add_relu(int dtype, const void* raw, const float* scale, 
     int g256 = cc, t256 = 256;
     while (t256) { const int r = g256 % t256; g256 = t256; t256 = r; }      // gcd(cc, 256)
     const int mult = cc / g256;
-    int grid = grid_for(rows * (long)cc, 256 * 4, 16384);
+    int grid = cvcl_grid(rows * (long)cc, 256 * 4, 16384);
     grid = (grid + mult - 1) / mult * mult;
     if (dtype == CVCL_F32)
         hipLaunchKernelGGL(bn_add_relu_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)raw,
@@ -1722,7 +1696,7 @@ extern "C" int cvcl_bn_relu_apply(int dtype, const void* x, const float* scale, 
     int g256 = cc, t256 = 256;
     while (t256) { const int r = g256 % t256; g256 = t256; t256 = r; }
     const int mult = cc / g256;
-    int grid = grid_for(rows * (long)cc, 256 * 4, 16384);
+    int grid = cvcl_grid(rows * (long)cc, 256 * 4, 16384);
     grid = (grid + mult - 1) / mult * mult;
     if (dtype == CVCL_F32)
         hipLaunchKernelGGL(bn_relu_apply_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)x, scale,
@@ -1740,9 +1714,9 @@ extern "C" int cvcl_avgpool(int dtype, const void* x, float* out, int B, int HW,
     CVCL_CHECK_ARG(x && out && B > 0 && HW > 0 && C > 0, "cvcl_avgpool: bad args");
     CvclProfScope prof(stream, CVCL_K_AVGPOOL);
     if (dtype == CVCL_F32)
-        hipLaunchKernelGGL(avgpool_kernel<float>, dim3(grid_for((long)B * C)), dim3(256), 0, (hipStream_t)stream, (const float*)x, out, B, HW, C);
+        hipLaunchKernelGGL(avgpool_kernel<float>, dim3(cvcl_grid((long)B * C, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const float*)x, out, B, HW, C);
     else
-        hipLaunchKernelGGL(avgpool_kernel<bf16_t>, dim3(grid_for((long)B * C)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, out, B, HW, C);
+        hipLaunchKernelGGL(avgpool_kernel<bf16_t>, dim3(cvcl_grid((long)B * C, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, out, B, HW, C);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }
@@ -2264,7 +2238,7 @@ extern "C" int cvcl_resnext50_fwd_grouped(int dtype, int B, int H, int W, int gr
     };
     auto group_relu = [&](float* x, const float* a, long rows, int C, long rows_g) -> int {
         CvclProfScope prof(stream, CVCL_K_BN_APPLY);
-        hipLaunchKernelGGL(bn_group_relu_kernel, dim3(grid_for(rows * (C / 4), 256, 16384)), dim3(256), 0, s, x, a, shift_of(a, C), x,
+        hipLaunchKernelGGL(bn_group_relu_kernel, dim3(cvcl_grid(rows * (C / 4), 256, 16384)), dim3(256), 0, s, x, a, shift_of(a, C), x,
                            rows, C, rows_g);
         CVCL_LAUNCH_CHECK();
         return CVCL_OK;
@@ -2277,7 +2251,7 @@ extern "C" int cvcl_resnext50_fwd_grouped(int dtype, int B, int H, int W, int gr
     {
         CvclProfScope prof(stream, CVCL_K_MAXPOOL);
         const long total = (long)B * ((h - 1) / 2 + 1) * ((wd - 1) / 2 + 1) * 16;
-        hipLaunchKernelGGL(bn_group_relu_maxpool_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, s, ws.buf[2], ws.aff[0],
+        hipLaunchKernelGGL(bn_group_relu_maxpool_kernel, dim3(cvcl_grid(total, 256, 16384)), dim3(256), 0, s, ws.buf[2], ws.aff[0],
                            shift_of(ws.aff[0], 64), ws.buf[0], B, h, wd, 64, group);
         CVCL_LAUNCH_CHECK();
     }
@@ -2309,7 +2283,7 @@ extern "C" int cvcl_resnext50_fwd_grouped(int dtype, int B, int H, int W, int gr
         if ((rc = group_bn(g.li + kConv3, io.R3, g_out, g.outc, ws.aff[kConv3]))) return rc;
         // bn3 + identity / bn(downsample) + relu -> dst
         CvclProfScope prof(stream, CVCL_K_BN_ADD_RELU);
-        hipLaunchKernelGGL(bn_group_add_relu_kernel, dim3(grid_for(g.m_out * (g.outc / 4), 256, 16384)), dim3(256), 0, s, io.R3,
+        hipLaunchKernelGGL(bn_group_add_relu_kernel, dim3(cvcl_grid(g.m_out * (g.outc / 4), 256, 16384)), dim3(256), 0, s, io.R3,
                            ws.aff[kConv3], shift_of(ws.aff[kConv3], g.outc), g.first ? io.RD : io.X,
                            g.first ? ws.aff[kDownsample] : nullptr, g.first ? shift_of(ws.aff[kDownsample], g.outc) : nullptr, io.dst,
                            g.m_out, g.outc, g_out);

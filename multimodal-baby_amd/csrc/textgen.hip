@@ -1,7 +1,7 @@
 // Beam-search text generation (include/cvcl_hip.h "Beam-search decoding"): one launch per decode step does one inner_loop of the
 // reference's beam search (multimodal/beam_search.py:418-611) for every batch item, with the stop test (:613-667) evaluated on the
-// device, so a decode runs without a host sync until its end.  A small cell kernel adds the gathered input-projection row of the
-// previous token and runs the LSTM cell on all B K beam rows.  All arithmetic is fp32.
+// device, so a decode runs without a host sync until its end.  The cell of a decode step (cvcl_lstm_cell_tok: the gathered input-
+// projection row of the previous token added, then the LSTM cell on all B K beam rows) is in csrc/lstm.hip.  All arithmetic is fp32.
 #include "cvcl_common.h"
 
 #include <math.h>
@@ -14,18 +14,6 @@ constexpr float kInf = 1e7f;                          // beam_search.py INF: the
 
 // (score desc, flat index asc): a total order on the candidates, so every selection is deterministic
 __device__ __forceinline__ bool better(float s, int i, float t, int j) { return s > t || (s == t && i < j); }
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // One workgroup per batch item b.  M: per-lane candidate list length (>= 2K).
 template <int M>
@@ -230,78 +218,8 @@ __global__ __launch_bounds__(kThreads) void beam_finalize_kernel(int K, int T, c
     if ((int)threadIdx.x < K) out_scores[bk + threadIdx.x] = sc[bk + threadIdx.x];
 }
 
-// LSTM cell of one decode step on N beam rows (gate order i,f,g,o): gates [N, 4H] = h W_hh^T, G [V, 4H] = table W_ih^T + b_ih + b_hh;
-// the row of each beam's input token is added before the cell.  h, c updated in place.
-__global__ __launch_bounds__(256) void lstm_cell_tok_kernel(const float* __restrict__ gates, const float* __restrict__ G,
-                                                            const int64_t* __restrict__ tok, int V, float* __restrict__ h,
-                                                            float* __restrict__ c, int N, int Hd) {
-    const long total = (long)N * Hd;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(i % Hd);
-        const long n = i / Hd;
-        const int64_t t = tok[n];
-        if (t < 0 || t >= V) continue;                // not a token of the vocabulary: the row keeps its state
-        const float* gp = gates + n * 4 * Hd;
-        const float* gr = G + t * 4 * Hd;
-        const float ig = 1.f / (1.f + expf(-(gp[j] + gr[j])));
-        const float fg = 1.f / (1.f + expf(-(gp[Hd + j] + gr[Hd + j])));
-        const float gg = tanhf(gp[2 * Hd + j] + gr[2 * Hd + j]);
-        const float og = 1.f / (1.f + expf(-(gp[3 * Hd + j] + gr[3 * Hd + j])));
-        const float cn = fg * c[i] + ig * gg;
-        c[i] = cn;
-        h[i] = og * tanhf(cn);
-    }
-}
-
-// BPTT step t = 0 of an LSTM that started from (h0, c0) (the captioning state): lstm_cell_bwd_kernel (csrc/vit.hip) with c_{-1} = c0
-// instead of zeros.  dc is updated in place to the gradient wrt c0; dh_carry as there.
-__global__ __launch_bounds__(256) void lstm_cell_bwd_first_kernel(const float* __restrict__ gates_act, const float* __restrict__ c_save,
-                                                                  const float* __restrict__ c0, const int64_t* __restrict__ len,
-                                                                  const float* __restrict__ dh, float* __restrict__ dc,
-                                                                  float* __restrict__ d_gates, float* __restrict__ dh_carry, int B,
-                                                                  int L, int Hd) {
-    const long total = (long)B * Hd;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(i % Hd);
-        const long b = i / Hd;
-        const long row = b * L;
-        float* dg = d_gates + row * 4 * Hd;
-        if (len[b] <= 0) {
-            dg[j] = 0.f; dg[Hd + j] = 0.f; dg[2 * Hd + j] = 0.f; dg[3 * Hd + j] = 0.f;
-            dh_carry[i] = dh[i];
-            continue;
-        }
-        dh_carry[i] = 0.f;
-        const float* ga = gates_act + row * 4 * Hd;
-        const float ig = ga[j], fg = ga[Hd + j], gg = ga[2 * Hd + j], og = ga[3 * Hd + j];
-        const float c_t = c_save[row * Hd + j];
-        const float c_prev = c0[i];
-        const float tc = tanhf(c_t);
-        const float dho = dh[i];
-        const float dct = dc[i] + dho * og * (1.f - tc * tc);
-        dg[j] = dct * gg * ig * (1.f - ig);
-        dg[Hd + j] = dct * c_prev * fg * (1.f - fg);
-        dg[2 * Hd + j] = dct * ig * (1.f - gg * gg);
-        dg[3 * Hd + j] = dho * tc * og * (1.f - og);
-        dc[i] = dct * fg;
-    }
-}
 
 }  // namespace
-
-extern "C" int cvcl_lstm_cell_bwd_first(const float* gates_act, const float* c_save, const float* c0, const int64_t* len,
-                                        const float* dh, float* dc, float* d_gates, float* dh_carry, int B, int L, int Hd,
-                                        void* stream) {
-    CVCL_CHECK_ARG(B >= 1 && L >= 1 && Hd >= 1, "cvcl_lstm_cell_bwd_first: bad sizes");
-    CVCL_CHECK_ARG(gates_act && c_save && c0 && len && dh && dc && d_gates && dh_carry, "cvcl_lstm_cell_bwd_first: null pointer");
-    CvclProfScope prof(stream, CVCL_K_LSTM);
-    const long total = (long)B * Hd;
-    const int grid = (int)(total / 256 + 1 < 8192 ? total / 256 + 1 : 8192);
-    hipLaunchKernelGGL(lstm_cell_bwd_first_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, gates_act, c_save, c0, len, dh, dc,
-                       d_gates, dh_carry, B, L, Hd);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
 
 extern "C" int cvcl_beam_step(const float* logits, int B, int K, int V, int T, int step, double alpha, int eos_id,
                               const float* alive_lp_in, float* alive_lp_out, const float* fin_scores_in, float* fin_scores_out,
@@ -340,18 +258,6 @@ extern "C" int cvcl_beam_finalize(int B, int K, int T, const int64_t* alive_seq,
     CvclProfScope prof(stream, CVCL_K_HEAD);
     hipLaunchKernelGGL(beam_finalize_kernel, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, K, T, alive_seq, alive_lp, fin_seq,
                        fin_scores, fin_flags, out_seq, out_scores);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_lstm_cell_tok(const float* gates, const float* G, const int64_t* tok, int V, float* h, float* c, int N, int Hd,
-                                  void* stream) {
-    CVCL_CHECK_ARG(N >= 1 && Hd >= 1 && V >= 1, "cvcl_lstm_cell_tok: bad sizes");
-    CVCL_CHECK_ARG(gates && G && tok && h && c, "cvcl_lstm_cell_tok: null pointer");
-    CvclProfScope prof(stream, CVCL_K_LSTM);
-    const long total = (long)N * Hd;
-    const int grid = (int)(total / 256 + 1 < 8192 ? total / 256 + 1 : 8192);
-    hipLaunchKernelGGL(lstm_cell_tok_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, gates, G, tok, V, h, c, N, Hd);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }

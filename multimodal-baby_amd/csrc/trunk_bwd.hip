@@ -8,12 +8,6 @@
 
 namespace {
 
-int grid_for(long total, int per_block = 256, int cap = 8192) {
-    long g = (total + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
-
 // All elementwise / reduction kernels below work on 16-byte chunks (8 bf16 / 4 fp32 channels) with the channel chunk
 // fixed per thread (grid * 256 is a multiple of the chunks per row), so per-channel vectors are loaded once per thread.
 
@@ -614,7 +608,7 @@ extern "C" int cvcl_bn_batch_moments(const float* stats, int stats_rows, long co
 extern "C" int cvcl_gconv_weight_dgrad(const float* w, float* out, int C, int cin_per_group, void* stream) {
     CVCL_CHECK_ARG(w && out && C > 0 && cin_per_group > 0 && C % cin_per_group == 0, "cvcl_gconv_weight_dgrad: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
-    hipLaunchKernelGGL(gconv_wflip_kernel, dim3(grid_for((long)C * cin_per_group * 9)), dim3(256), 0, (hipStream_t)stream, w, out, C,
+    hipLaunchKernelGGL(gconv_wflip_kernel, dim3(cvcl_grid((long)C * cin_per_group * 9, 256, 8192)), dim3(256), 0, (hipStream_t)stream, w, out, C,
                        cin_per_group);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
@@ -638,9 +632,9 @@ extern "C" int cvcl_add(int dtype, const void* a, const void* b, void* y, long n
     CVCL_CHECK_ARG(a && b && y && n > 0 && n % epc_of(dtype) == 0, "cvcl_add: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     if (dtype == CVCL_F32)
-        hipLaunchKernelGGL(add_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)y, n, relu);
+        hipLaunchKernelGGL(add_kernel<float>, dim3(cvcl_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)y, n, relu);
     else
-        hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, n, relu);
+        hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(cvcl_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, n, relu);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }
@@ -650,9 +644,9 @@ extern "C" int cvcl_relu_mask(int dtype, const void* y, const void* dy, void* dx
     CVCL_CHECK_ARG(y && dy && dx && n > 0 && n % epc_of(dtype) == 0, "cvcl_relu_mask: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     if (dtype == CVCL_F32)
-        hipLaunchKernelGGL(relu_mask_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)y, (const float*)dy, (float*)dx, n);
+        hipLaunchKernelGGL(relu_mask_kernel<float>, dim3(cvcl_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const float*)y, (const float*)dy, (float*)dx, n);
     else
-        hipLaunchKernelGGL(relu_mask_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y, (const bf16_t*)dy, (bf16_t*)dx, n);
+        hipLaunchKernelGGL(relu_mask_kernel<bf16_t>, dim3(cvcl_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y, (const bf16_t*)dy, (bf16_t*)dx, n);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }
@@ -664,11 +658,11 @@ extern "C" int cvcl_maxpool3x3s2(int dtype, const void* x, const void* dy, void*
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     hipStream_t s = (hipStream_t)stream;
     if (!dy) {       // forward: out = pooled [B,Ho,Wo,C]
-        if (dtype == CVCL_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid_for((long)B * Ho * Wo * C)), dim3(256), 0, s, (const float*)x, (float*)out, B, H, W, C);
-        else hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(grid_for((long)B * Ho * Wo * C)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, B, H, W, C);
+        if (dtype == CVCL_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(cvcl_grid((long)B * Ho * Wo * C, 256, 8192)), dim3(256), 0, s, (const float*)x, (float*)out, B, H, W, C);
+        else hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(cvcl_grid((long)B * Ho * Wo * C, 256, 8192)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, B, H, W, C);
     } else {         // backward: out = dx [B,H,W,C]
-        if (dtype == CVCL_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid_for((long)B * H * W * C / 4)), dim3(256), 0, s, (const float*)x, (const float*)dy, (float*)out, B, H, W, C);
-        else hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(grid_for((long)B * H * W * C / 8)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, B, H, W, C);
+        if (dtype == CVCL_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(cvcl_grid((long)B * H * W * C / 4, 256, 8192)), dim3(256), 0, s, (const float*)x, (const float*)dy, (float*)out, B, H, W, C);
+        else hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(cvcl_grid((long)B * H * W * C / 8, 256, 8192)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, B, H, W, C);
     }
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
@@ -683,11 +677,11 @@ extern "C" int cvcl_maxpool3x3s2_idx(int dtype, const void* x, const void* dy, v
     hipStream_t s = (hipStream_t)stream;
     const int epc = epc_of(dtype);
     if (!dy) {       // forward: out = pooled [B,Ho,Wo,C], idx = arg-max code 0..8 per output element
-        const int g = grid_for((long)B * Ho * Wo * C / epc);
+        const int g = cvcl_grid((long)B * Ho * Wo * C / epc, 256, 8192);
         if (dtype == CVCL_F32) hipLaunchKernelGGL(maxpool_fwd_idx_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)x, (float*)out, idx, B, H, W, C);
         else hipLaunchKernelGGL(maxpool_fwd_idx_kernel<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, idx, B, H, W, C);
     } else {         // backward: out = dx [B,H,W,C]
-        const int g = grid_for((long)B * H * W * C / epc);
+        const int g = cvcl_grid((long)B * H * W * C / epc, 256, 8192);
         if (dtype == CVCL_F32) hipLaunchKernelGGL(maxpool_bwd_idx_kernel<float>, dim3(g), dim3(256), 0, s, idx, (const float*)dy, (float*)out, B, H, W, C);
         else hipLaunchKernelGGL(maxpool_bwd_idx_kernel<bf16_t>, dim3(g), dim3(256), 0, s, idx, (const bf16_t*)dy, (bf16_t*)out, B, H, W, C);
     }
@@ -699,8 +693,8 @@ extern "C" int cvcl_avgpool_bwd(int dtype, const float* d_pooled, void* dx, int 
     CVCL_CHECK_DTYPE(dtype, "cvcl_avgpool_bwd");
     CVCL_CHECK_ARG(d_pooled && dx && B > 0 && HW > 0 && C > 0, "cvcl_avgpool_bwd: bad args");
     CvclProfScope prof(stream, CVCL_K_AVGPOOL);
-    if (dtype == CVCL_F32) hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(grid_for((long)B * HW * C)), dim3(256), 0, (hipStream_t)stream, d_pooled, (float*)dx, B, HW, C);
-    else hipLaunchKernelGGL(avgpool_bwd_kernel<bf16_t>, dim3(grid_for((long)B * HW * C)), dim3(256), 0, (hipStream_t)stream, d_pooled, (bf16_t*)dx, B, HW, C);
+    if (dtype == CVCL_F32) hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(cvcl_grid((long)B * HW * C, 256, 8192)), dim3(256), 0, (hipStream_t)stream, d_pooled, (float*)dx, B, HW, C);
+    else hipLaunchKernelGGL(avgpool_bwd_kernel<bf16_t>, dim3(cvcl_grid((long)B * HW * C, 256, 8192)), dim3(256), 0, (hipStream_t)stream, d_pooled, (bf16_t*)dx, B, HW, C);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }
@@ -710,8 +704,8 @@ extern "C" int cvcl_zero_stuff2(int dtype, const void* dy, void* z, int B, int H
     CVCL_CHECK_ARG(dy && z && B > 0 && Ho > 0 && Wo > 0 && C > 0 && C % epc_of(dtype) == 0, "cvcl_zero_stuff2: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     const long total = (long)B * 4 * Ho * Wo * C / epc_of(dtype);
-    if (dtype == CVCL_F32) hipLaunchKernelGGL(zero_stuff_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (float*)z, B, Ho, Wo, C);
-    else hipLaunchKernelGGL(zero_stuff_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)z, B, Ho, Wo, C);
+    if (dtype == CVCL_F32) hipLaunchKernelGGL(zero_stuff_kernel<float>, dim3(cvcl_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (float*)z, B, Ho, Wo, C);
+    else hipLaunchKernelGGL(zero_stuff_kernel<bf16_t>, dim3(cvcl_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (bf16_t*)z, B, Ho, Wo, C);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }
@@ -737,7 +731,7 @@ extern "C" int cvcl_conv_wgrad_direct(int dtype, const void* x, const void* dy, 
 extern "C" int cvcl_bf16_to_f32(const void* x, float* y, long n, void* stream) {
     CVCL_CHECK_ARG(x && y && n > 0 && n % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "cvcl_bf16_to_f32: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
-    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, y, n);
+    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(cvcl_grid(n / 8, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, y, n);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }
@@ -745,7 +739,7 @@ extern "C" int cvcl_bf16_to_f32(const void* x, float* y, long n, void* stream) {
 extern "C" int cvcl_f32_to_bf16(const float* x, void* y, long n, void* stream) {
     CVCL_CHECK_ARG(x && y && n > 0 && n % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "cvcl_f32_to_bf16: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
-    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
+    hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(cvcl_grid(n / 8, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }

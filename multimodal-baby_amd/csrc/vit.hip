@@ -1,8 +1,7 @@
-// Transformer-side kernels: DINO ViT image encoder (reference multimodal/vision_transformer_dino_mugs.py:87-250),
-// the one-layer text transformer (multimodal/multimodal.py:553-573, nn.TransformerEncoderLayer) and the LSTM text
-// encoder (multimodal/multimodal.py:513-552).  Every linear layer runs on the MFMA GEMM of gemm.hip; this file
-// holds what is not a GEMM: patch gather, token assembly, LayerNorm, attention, embedding(+pos) gather, sequence
-// pooling and the LSTM cell.
+// Transformer-side kernels of the DINO ViT image encoder (reference multimodal/vision_transformer_dino_mugs.py:87-250).  Every
+// linear layer runs on the MFMA GEMM of gemm.hip; this file holds what is not a GEMM: patch gather, token assembly, the LayerNorm
+// forwards, row statistics and the attention forwards (the generic one also serves the one-layer text transformer,
+// multimodal/multimodal.py:553-573).  The text encoders' own kernels are in text.hip and lstm.hip.
 #include "cvcl_common.h"
 
 namespace {
@@ -613,70 +612,6 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_mfma_kernel(const bf
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// text side
-// ------------------------------------------------------------------------------------------------
-// x[b][l][:] = table[tok[b][l]] (+ pos[l])                       (multimodal.py:496, 561-563)
-__global__ __launch_bounds__(256) void embed_gather_pos_kernel(const float* __restrict__ table, const int64_t* __restrict__ tok,
-                                                               const float* __restrict__ pos, float* __restrict__ x, int B,
-                                                               int L, int E, int V) {
-    const long total = (long)B * L * E;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int e = (int)(i % E);
-        const long r = i / E;
-        const int l = (int)(r % L);
-        const int64_t t = tok[r];
-        float v = (t >= 0 && t < V) ? table[t * E + e] : NAN;
-        if (pos) v += pos[(long)l * E + e];
-        x[i] = v;
-    }
-}
-
-// ret[b][:] = sum_l x[b][l][:] / len[b]   (all L positions, pads included: multimodal.py:573, Appendix C.1)
-__global__ __launch_bounds__(256) void seq_sum_div_kernel(const float* __restrict__ x, const int64_t* __restrict__ len,
-                                                          float* __restrict__ ret, int B, int L, int E) {
-    const long total = (long)B * E;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int e = (int)(i % E);
-        const long b = i / E;
-        float acc = 0.f;
-        for (int l = 0; l < L; ++l) acc += x[(b * L + l) * E + e];
-        ret[i] = acc / (float)len[b];
-    }
-}
-
-// LSTM cell for step t (gate order i,f,g,o; nn.LSTM): gates [B,4H] already = x_t W_ih^T + b_ih + b_hh + h W_hh^T.
-// Sequences shorter than t+1 keep their state (packed-sequence semantics) and emit zeros (pad_packed_sequence).
-__global__ __launch_bounds__(256) void lstm_cell_kernel(const float* __restrict__ gates, const int64_t* __restrict__ len, int t,
-                                                        float* __restrict__ h, float* __restrict__ c, float* __restrict__ out,
-                                                        int B, int L, int Hd) {
-    const long total = (long)B * Hd;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(i % Hd);
-        const long b = i / Hd;
-        const bool live = len[b] > t;
-        float ho = 0.f;
-        if (live) {
-            const float* gp = gates + b * 4 * Hd;
-            const float ig = 1.f / (1.f + expf(-gp[j]));
-            const float fg = 1.f / (1.f + expf(-gp[Hd + j]));
-            const float gg = tanhf(gp[2 * Hd + j]);
-            const float og = 1.f / (1.f + expf(-gp[3 * Hd + j]));
-            const float cn = fg * c[i] + ig * gg;
-            ho = og * tanhf(cn);
-            c[i] = cn;
-            h[i] = ho;
-        }
-        if (out) out[(b * L + t) * Hd + j] = ho;
-    }
-}
-
-int grid_for(long total, int per_block = 256, int cap = 8192) {
-    long g = (total + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
-
 }  // namespace
 
 // ================================================================================================
@@ -688,13 +623,13 @@ extern "C" int cvcl_im2col_patches(int dtype, const float* x_nchw, void* cols, i
     CvclProfScope prof(stream, CVCL_K_OTHER);
     const long total = (long)B * (H / patch) * (W / patch) * Kpad;
     if (dtype == CVCL_F32)
-        hipLaunchKernelGGL(im2col_patches_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x_nchw,
+        hipLaunchKernelGGL(im2col_patches_kernel<float>, dim3(cvcl_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x_nchw,
                            (float*)cols, B, H, W, patch, Kpad);
     else if (patch % 8 == 0 && Kpad % 8 == 0 && W % 4 == 0 && ((uintptr_t)x_nchw & 15) == 0 && ((uintptr_t)cols & 15) == 0)
-        hipLaunchKernelGGL(im2col_patches8_kernel, dim3(grid_for(total / 8)), dim3(256), 0, (hipStream_t)stream, x_nchw,
+        hipLaunchKernelGGL(im2col_patches8_kernel, dim3(cvcl_grid(total / 8, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x_nchw,
                            (bf16_t*)cols, B, H, W, patch, Kpad);
     else
-        hipLaunchKernelGGL(im2col_patches_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x_nchw,
+        hipLaunchKernelGGL(im2col_patches_kernel<bf16_t>, dim3(cvcl_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x_nchw,
                            (bf16_t*)cols, B, H, W, patch, Kpad);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
@@ -707,13 +642,13 @@ extern "C" int cvcl_vit_assemble_tokens(int dtype, const void* tok, const float*
     CvclProfScope prof(stream, CVCL_K_OTHER);
     const long total = (long)B * T * D;
     if (dtype == CVCL_F32)
-        hipLaunchKernelGGL(vit_assemble_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)tok,
+        hipLaunchKernelGGL(vit_assemble_kernel<float>, dim3(cvcl_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const float*)tok,
                            cls, pos, (float*)h, B, T, D);
     else if (D % 8 == 0 && ((uintptr_t)tok & 15) == 0 && ((uintptr_t)h & 15) == 0 && ((uintptr_t)pos & 15) == 0 && ((uintptr_t)cls & 15) == 0)
-        hipLaunchKernelGGL(vit_assemble8_kernel, dim3(grid_for(total / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)tok, cls,
+        hipLaunchKernelGGL(vit_assemble8_kernel, dim3(cvcl_grid(total / 8, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)tok, cls,
                            pos, (bf16_t*)h, B, T, D);
     else
-        hipLaunchKernelGGL(vit_assemble_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(vit_assemble_kernel<bf16_t>, dim3(cvcl_grid(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
                            (const bf16_t*)tok, cls, pos, (bf16_t*)h, B, T, D);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
@@ -789,13 +724,10 @@ int launch_attention_mfma_n(const void* qkv, void* out, void* out8, void* out_bs
     const int nt = (T + 31) / 32;
     const size_t lds = (size_t)nt * 32 * (ATT_KP + ATT_VP);
     static CvclLdsAttr attr_set;
-    if (!attr_set.ready()) {
-        if (hipFuncSetAttribute((const void*)attention_mfma_kernel<MX, NTC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            cvcl_set_error("cvcl_attention: cannot raise the dynamic LDS limit");
-            return CVCL_ELAUNCH;
-        }
-        attr_set.mark();
-    }
+    if (const int rc = cvcl_raise_lds_limit(attr_set, (const void*)attention_mfma_kernel<MX, NTC>, 160 * 1024,
+                                            "cvcl_attention"))
+        return rc;
+    attr_set.mark();
     hipLaunchKernelGGL((attention_mfma_kernel<MX, NTC>), dim3(B * heads), dim3(ATT_THREADS), lds, s, (const bf16_t*)qkv, (bf16_t*)out,
                        (unsigned char*)out8, (unsigned char*)out_bs, lse, B, T, heads, scale, nt);
     return CVCL_OK;
@@ -859,424 +791,6 @@ extern "C" int cvcl_attention(int dtype, const void* qkv, const int64_t* key_tok
     else
         hipLaunchKernelGGL(attention_valu_kernel<bf16_t>, dim3(cvcl_div_up(nwork, 4)), dim3(256), lds, s, (const bf16_t*)qkv,
                            key_tok, (bf16_t*)out, B, T, heads, head_dim, scale);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_embed_gather_pos(const float* table, const int64_t* tok, const float* pos, float* x, int B, int L, int E,
-                                     int V, void* stream) {
-    CVCL_CHECK_ARG(table && tok && x && B > 0 && L > 0 && E > 0 && V > 0, "cvcl_embed_gather_pos: bad args");
-    CvclProfScope prof(stream, CVCL_K_HEAD);
-    hipLaunchKernelGGL(embed_gather_pos_kernel, dim3(grid_for((long)B * L * E)), dim3(256), 0, (hipStream_t)stream, table, tok,
-                       pos, x, B, L, E, V);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_seq_sum_div(const float* x, const int64_t* len, float* ret, int B, int L, int E, void* stream) {
-    CVCL_CHECK_ARG(x && len && ret && B > 0 && L > 0 && E > 0, "cvcl_seq_sum_div: bad args");
-    CvclProfScope prof(stream, CVCL_K_HEAD);
-    hipLaunchKernelGGL(seq_sum_div_kernel, dim3(grid_for((long)B * E)), dim3(256), 0, (hipStream_t)stream, x, len, ret, B, L, E);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_lstm_cell(const float* gates, const int64_t* len, int t, float* h, float* c, float* out, int B, int L,
-                              int Hd, void* stream) {
-    CVCL_CHECK_ARG(gates && len && h && c && B > 0 && L > 0 && Hd > 0 && t >= 0 && t < L, "cvcl_lstm_cell: bad args");
-    CvclProfScope prof(stream, CVCL_K_LSTM);
-    hipLaunchKernelGGL(lstm_cell_kernel, dim3(grid_for((long)B * Hd)), dim3(256), 0, (hipStream_t)stream, gates, len, t, h, c, out,
-                       B, L, Hd);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-// ================================================================================================
-// Training side of the text encoders (reference multimodal/multimodal.py:513-573 run under Lightning's
-// .train()): backward kernels + dropout.  All fp32, deterministic (no atomics).
-// ================================================================================================
-namespace {
-
-// counter-based hash RNG (one draw per element): keep iff u >= p.  Same (seed, index) -> same mask in fwd and bwd.
-__device__ inline float hash_uniform(unsigned long long seed, unsigned long long idx) {
-    unsigned long long z = seed + idx * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(z >> 40) * (1.0f / 16777216.0f);          // 24 random bits -> [0, 1)
-}
-
-// y = x * keep / (1 - p); the same kernel is the backward (dx = dy * keep / (1 - p)).
-// period > 0: the mask index is (i / (period * inner)) * inner + i % inner, i.e. shared along one dimension
-// (LockedDropout, multimodal.py:46-53: mask shape [B,1,E] shared over time).
-__global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                      float* __restrict__ y, long n, float p, unsigned long long seed,
-                                                      long period, long inner) {
-    const float scale = 1.f / (1.f - p);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const long mi = period > 0 ? (i / (period * inner)) * inner + (i % inner) : i;
-        float v = (p <= 0.f || hash_uniform(seed, (unsigned long long)mi) >= p) ? x[i] * scale : 0.f;
-        if (res) v += res[i];
-        y[i] = v;
-    }
-}
-
-// LayerNorm backward, one wave per row: dx = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma.
-// Per-row partial products for dgamma / dbeta are written as dy*xhat and dy (reduced by cvcl_colsum_f32).
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                            const float* __restrict__ dy, float eps, float* __restrict__ dx,
-                                                            float* __restrict__ dyxhat, long rows, int D) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const float* xr = x + row * D;
-    const float* gr = dy + row * D;
-    float s = 0.f;
-    for (int d = lane; d < D; d += 64) s += xr[d];
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-    for (int d = lane; d < D; d += 64) { const float c = xr[d] - mean; q = fmaf(c, c, q); }
-    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)D + eps);
-    float sg = 0.f, sgx = 0.f;
-    for (int d = lane; d < D; d += 64) {
-        const float xh = (xr[d] - mean) * rstd, g = gr[d] * gamma[d];
-        sg += g;
-        sgx = fmaf(g, xh, sgx);
-    }
-    sg = wave_sum(sg) / (float)D;
-    sgx = wave_sum(sgx) / (float)D;
-    for (int d = lane; d < D; d += 64) {
-        const float xh = (xr[d] - mean) * rstd, g = gr[d] * gamma[d];
-        dx[row * D + d] = rstd * (g - sg - xh * sgx);
-        dyxhat[row * D + d] = gr[d] * xh;
-    }
-}
-
-// dx = dy where y > 0 (ReLU backward from the saved output)
-__global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy,
-                                                       float* __restrict__ dx, long n) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        dx[i] = y[i] > 0.f ? dy[i] : 0.f;
-}
-
-
-// dx[b,l,:] = d_ret[b,:] / len[b] for every l (backward of seq_sum_div: pads included, as in the forward)
-__global__ __launch_bounds__(256) void seq_sum_div_bwd_kernel(const float* __restrict__ d_ret, const int64_t* __restrict__ len,
-                                                              float* __restrict__ dx, int B, int L, int E) {
-    const long total = (long)B * L * E;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int e = (int)(i % E);
-        const long b = i / ((long)L * E);
-        dx[i] = d_ret[b * E + e] / (float)len[b];
-    }
-}
-
-// Small-sequence attention forward+backward with key padding mask and probability dropout (training).
-// One workgroup (64 threads = 1 wave) per (b, head); T <= 32, hd <= 128.  P is recomputed in the backward.
-//   S = q k^T * scale (+mask) ; P = softmax(S) ; Pd = dropout(P) ; O = Pd v
-//   dPd = dO v^T ; dP = dropout'(dPd) ; dS = P * (dP - sum_j dP P) ; dq = dS k * scale ; dk = dS^T q * scale ; dv = Pd^T dO
-constexpr int SA_T = 32;
-__global__ __launch_bounds__(64) void attn_small_kernel(const float* __restrict__ qkv, const int64_t* __restrict__ key_tok,
-                                                        const float* __restrict__ d_out, float* __restrict__ out,
-                                                        float* __restrict__ d_qkv, int B, int T, int heads, int hd,
-                                                        float scale, float p, unsigned long long seed) {
-    __shared__ float sP[SA_T][SA_T + 1], sPd[SA_T][SA_T + 1], sdS[SA_T][SA_T + 1];
-    const int lane = threadIdx.x;
-    const int hh = blockIdx.x % heads, b = blockIdx.x / heads;
-    const int D = heads * hd;
-    const float* base = qkv + (long)b * T * 3 * D;
-    const float keep_scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
-    // scores: lane handles pairs (i, j) = idx / T, idx % T
-    for (int idx = lane; idx < T * T; idx += 64) {
-        const int i = idx / T, j = idx - i * T;
-        const float* qp = base + (long)i * 3 * D + hh * hd;
-        const float* kp = base + (long)j * 3 * D + D + hh * hd;
-        float s = 0.f;
-        for (int d = 0; d < hd; ++d) s = fmaf(qp[d], kp[d], s);
-        s *= scale;
-        if (key_tok && key_tok[(long)b * T + j] == 0) s = -INFINITY;
-        sP[i][j] = s;
-    }
-    __syncthreads();
-    if (lane < T) {                                       // row softmax + dropout mask
-        const int i = lane;
-        float mx = -INFINITY;
-        for (int j = 0; j < T; ++j) mx = fmaxf(mx, sP[i][j]);
-        float sum = 0.f;
-        for (int j = 0; j < T; ++j) { const float e = expf(sP[i][j] - mx); sP[i][j] = e; sum += e; }
-        for (int j = 0; j < T; ++j) {
-            const float pr = sP[i][j] / sum;
-            sP[i][j] = pr;
-            float keep = 1.f;
-            if (p > 0.f) keep = hash_uniform(seed, (((unsigned long long)b * heads + hh) * T + i) * T + j) >= p ? keep_scale : 0.f;
-            sPd[i][j] = pr * keep;
-        }
-    }
-    __syncthreads();
-    if (out) {
-        for (int idx = lane; idx < T * hd; idx += 64) {
-            const int i = idx / hd, d = idx - i * hd;
-            float acc = 0.f;
-            for (int j = 0; j < T; ++j) acc = fmaf(sPd[i][j], base[(long)j * 3 * D + 2 * D + hh * hd + d], acc);
-            out[((long)b * T + i) * D + hh * hd + d] = acc;
-        }
-    }
-    if (!d_qkv) return;
-    const float* dO = d_out + (long)b * T * D;
-    float* dbase = d_qkv + (long)b * T * 3 * D;
-    // dPd[i][j] = dO[i] . v[j]; dP = dPd * keep
-    for (int idx = lane; idx < T * T; idx += 64) {
-        const int i = idx / T, j = idx - i * T;
-        float s = 0.f;
-        for (int d = 0; d < hd; ++d) s = fmaf(dO[(long)i * D + hh * hd + d], base[(long)j * 3 * D + 2 * D + hh * hd + d], s);
-        float keep = 1.f;
-        if (p > 0.f) keep = hash_uniform(seed, (((unsigned long long)b * heads + hh) * T + i) * T + j) >= p ? keep_scale : 0.f;
-        sdS[i][j] = s * keep;
-    }
-    __syncthreads();
-    if (lane < T) {
-        const int i = lane;
-        float dot = 0.f;
-        for (int j = 0; j < T; ++j) dot = fmaf(sdS[i][j], sP[i][j], dot);
-        for (int j = 0; j < T; ++j) sdS[i][j] = sP[i][j] * (sdS[i][j] - dot);
-    }
-    __syncthreads();
-    for (int idx = lane; idx < T * hd; idx += 64) {
-        const int i = idx / hd, d = idx - i * hd;
-        float dq = 0.f, dk = 0.f, dv = 0.f;
-        for (int j = 0; j < T; ++j) {
-            dq = fmaf(sdS[i][j], base[(long)j * 3 * D + D + hh * hd + d], dq);       // dS[i][j] * k[j]
-            dk = fmaf(sdS[j][i], base[(long)j * 3 * D + hh * hd + d], dk);           // dS[j][i] * q[j]
-            dv = fmaf(sPd[j][i], dO[(long)j * D + hh * hd + d], dv);                 // Pd[j][i] * dO[j]
-        }
-        dbase[(long)i * 3 * D + hh * hd + d] = dq * scale;
-        dbase[(long)i * 3 * D + D + hh * hd + d] = dk * scale;
-        dbase[(long)i * 3 * D + 2 * D + hh * hd + d] = dv;
-    }
-}
-
-// LSTM training step t (gate order i,f,g,o).  Saved for BPTT in [B, L, .] layout (row b*L + t, matching the rows of the
-// input-projection GEMM): gate activations, c_t, h_{t-1}.  Rows with len <= t keep their state (packed-sequence semantics).
-__global__ __launch_bounds__(256) void lstm_cell_train_kernel(const float* __restrict__ gates, const int64_t* __restrict__ len,
-                                                              int t, float* __restrict__ h, float* __restrict__ c,
-                                                              float* __restrict__ out, float* __restrict__ gates_act,
-                                                              float* __restrict__ c_save, float* __restrict__ h_prev_save,
-                                                              int B, int L, int Hd) {
-    const long total = (long)B * Hd;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(i % Hd);
-        const long b = i / Hd;
-        const long row = b * L + t;
-        h_prev_save[row * Hd + j] = h[i];
-        float* ga = gates_act + row * 4 * Hd;
-        float ho = 0.f;
-        if (len[b] > t) {
-            const float* gp = gates + b * 4 * Hd;
-            const float ig = 1.f / (1.f + expf(-gp[j]));
-            const float fg = 1.f / (1.f + expf(-gp[Hd + j]));
-            const float gg = tanhf(gp[2 * Hd + j]);
-            const float og = 1.f / (1.f + expf(-gp[3 * Hd + j]));
-            const float cn = fg * c[i] + ig * gg;
-            ga[j] = ig; ga[Hd + j] = fg; ga[2 * Hd + j] = gg; ga[3 * Hd + j] = og;
-            c[i] = cn;
-            ho = og * tanhf(cn);
-            h[i] = ho;
-        }
-        c_save[row * Hd + j] = c[i];
-        if (out) out[row * Hd + j] = ho;
-    }
-}
-
-// BPTT step t.  In: dh (gradient wrt h_t), dc (gradient wrt c_t, updated in place to the gradient wrt c_{t-1}).
-// Out: d_gates rows b*L + t of the [B, L, 4H] buffer (pre-activation gate gradients), dh_carry = dh for rows whose
-// step was not taken (their h_t = h_{t-1}), 0 otherwise.
-__global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restrict__ gates_act, const float* __restrict__ c_save,
-                                                            const int64_t* __restrict__ len, int t, const float* __restrict__ dh,
-                                                            float* __restrict__ dc, float* __restrict__ d_gates,
-                                                            float* __restrict__ dh_carry, int B, int L, int Hd) {
-    const long total = (long)B * Hd;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(i % Hd);
-        const long b = i / Hd;
-        const long row = b * L + t;
-        float* dg = d_gates + row * 4 * Hd;
-        if (len[b] <= t) {
-            dg[j] = 0.f; dg[Hd + j] = 0.f; dg[2 * Hd + j] = 0.f; dg[3 * Hd + j] = 0.f;
-            dh_carry[i] = dh[i];
-            continue;
-        }
-        dh_carry[i] = 0.f;
-        const float* ga = gates_act + row * 4 * Hd;
-        const float ig = ga[j], fg = ga[Hd + j], gg = ga[2 * Hd + j], og = ga[3 * Hd + j];
-        const float c_t = c_save[row * Hd + j];
-        const float c_prev = t > 0 ? c_save[(row - 1) * Hd + j] : 0.f;
-        const float tc = tanhf(c_t);
-        const float dho = dh[i];
-        const float dct = dc[i] + dho * og * (1.f - tc * tc);
-        dg[j] = dct * gg * ig * (1.f - ig);
-        dg[Hd + j] = dct * c_prev * fg * (1.f - fg);
-        dg[2 * Hd + j] = dct * ig * (1.f - gg * gg);
-        dg[3 * Hd + j] = dho * tc * og * (1.f - og);
-        dc[i] = dct * fg;
-    }
-}
-
-}  // namespace
-
-extern "C" int cvcl_dropout(const float* x, const float* residual, float* y, long n, float p, unsigned long long seed,
-                            long shared_period, long inner, void* stream) {
-    CVCL_CHECK_ARG(x && y && n > 0 && p >= 0.f && p < 1.f, "cvcl_dropout: bad args");
-    CvclProfScope prof(stream, CVCL_K_HEAD);
-    hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, residual, y, n, p, seed,
-                       shared_period, inner > 0 ? inner : 1);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_layernorm_bwd(const float* x, const float* gamma, const float* dy, float eps, float* dx, float* dy_xhat,
-                                  long rows, int D, void* stream) {
-    CVCL_CHECK_ARG(x && gamma && dy && dx && dy_xhat && rows > 0 && D > 0, "cvcl_layernorm_bwd: bad args");
-    CvclProfScope prof(stream, CVCL_K_LAYERNORM);
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(cvcl_div_up(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, dy, eps, dx,
-                       dy_xhat, rows, D);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_relu_bwd(const float* y, const float* dy, float* dx, long n, void* stream) {
-    CVCL_CHECK_ARG(y && dy && dx && n > 0, "cvcl_relu_bwd: bad args");
-    CvclProfScope prof(stream, CVCL_K_HEAD);
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, y, dy, dx, n);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-
-extern "C" int cvcl_seq_sum_div_bwd(const float* d_ret, const int64_t* len, float* dx, int B, int L, int E, void* stream) {
-    CVCL_CHECK_ARG(d_ret && len && dx && B > 0 && L > 0 && E > 0, "cvcl_seq_sum_div_bwd: bad args");
-    CvclProfScope prof(stream, CVCL_K_HEAD);
-    hipLaunchKernelGGL(seq_sum_div_bwd_kernel, dim3(grid_for((long)B * L * E)), dim3(256), 0, (hipStream_t)stream, d_ret, len, dx,
-                       B, L, E);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_attention_small(const float* qkv, const int64_t* key_tok, const float* d_out, float* out, float* d_qkv,
-                                    int B, int T, int heads, int head_dim, float scale, float dropout_p,
-                                    unsigned long long seed, void* stream) {
-    CVCL_CHECK_ARG(qkv && (out || d_qkv) && B > 0 && T > 0 && T <= SA_T && heads > 0 && head_dim > 0,
-                   "cvcl_attention_small: bad args (T <= %d)", SA_T);
-    CVCL_CHECK_ARG(!d_qkv || d_out, "cvcl_attention_small: d_out needed for the backward");
-    CvclProfScope prof(stream, CVCL_K_ATTENTION);
-    hipLaunchKernelGGL(attn_small_kernel, dim3(B * heads), dim3(64), 0, (hipStream_t)stream, qkv, key_tok, d_out, out, d_qkv, B, T,
-                       heads, head_dim, scale, dropout_p, seed);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_lstm_cell_train(const float* gates, const int64_t* len, int t, float* h, float* c, float* out,
-                                    float* gates_act, float* c_save, float* h_prev_save, int B, int L, int Hd, void* stream) {
-    CVCL_CHECK_ARG(gates && len && h && c && gates_act && c_save && h_prev_save && B > 0 && L > 0 && Hd > 0 && t >= 0 && t < L,
-                   "cvcl_lstm_cell_train: bad args");
-    CvclProfScope prof(stream, CVCL_K_LSTM);
-    hipLaunchKernelGGL(lstm_cell_train_kernel, dim3(grid_for((long)B * Hd)), dim3(256), 0, (hipStream_t)stream, gates, len, t, h, c,
-                       out, gates_act, c_save, h_prev_save, B, L, Hd);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_lstm_cell_bwd(const float* gates_act, const float* c_save, const int64_t* len, int t, const float* dh,
-                                  float* dc, float* d_gates, float* dh_carry, int B, int L, int Hd, void* stream) {
-    CVCL_CHECK_ARG(gates_act && c_save && len && dh && dc && d_gates && dh_carry && B > 0 && L > 0 && Hd > 0 && t >= 0 && t < L,
-                   "cvcl_lstm_cell_bwd: bad args");
-    CvclProfScope prof(stream, CVCL_K_LSTM);
-    hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(grid_for((long)B * Hd)), dim3(256), 0, (hipStream_t)stream, gates_act, c_save, len,
-                       t, dh, dc, d_gates, dh_carry, B, L, Hd);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-// dh[b][:] += d_out[b][t][:] for the sequences still running at step t (out[b][t] = h_t there, 0 beyond the length): lets
-// the per-step outputs of the LSTM (the language-model branch, multimodal.py:859) take part in the BPTT
-namespace {
-__global__ __launch_bounds__(256) void lstm_add_dout_kernel(float* __restrict__ dh, const float* __restrict__ d_out,
-                                                            const int64_t* __restrict__ len, int t, int B, int L, int Hd) {
-    const long total = (long)B * Hd;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const long b = i / Hd;
-        const int j = (int)(i % Hd);
-        if (len[b] > t) dh[i] += d_out[(b * L + t) * Hd + j];
-    }
-}
-}  // namespace
-
-extern "C" int cvcl_lstm_add_dout(float* dh, const float* d_out, const int64_t* len, int t, int B, int L, int Hd, void* stream) {
-    CVCL_CHECK_ARG(dh && d_out && len && B > 0 && L > 0 && Hd > 0 && t >= 0 && t < L, "cvcl_lstm_add_dout: bad args");
-    CvclProfScope prof(stream, CVCL_K_LSTM);
-    hipLaunchKernelGGL(lstm_add_dout_kernel, dim3(grid_for((long)B * Hd)), dim3(256), 0, (hipStream_t)stream, dh, d_out, len, t, B, L, Hd);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-// ---- remaining text encoders (reference multimodal/multimodal.py:505-552) -------------------------------------------
-namespace {
-// y[b][t] = x[b][len[b]-1-t] for t < len[b], 0 beyond: the backward direction of a packed bidirectional LSTM runs over each
-// sequence from its last valid token; the same permutation un-reverses its outputs (and is its own adjoint)
-__global__ __launch_bounds__(256) void seq_reverse_kernel(const float* __restrict__ x, const int64_t* __restrict__ len,
-                                                          float* __restrict__ y, int B, int L, int E) {
-    const long total = (long)B * L * E;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int e = (int)(i % E);
-        const long r = i / E;
-        const int t = (int)(r % L);
-        const long b = r / L;
-        const int n = (int)len[b];
-        y[i] = t < n ? x[(b * L + (n - 1 - t)) * E + e] : 0.f;
-    }
-}
-// y = alpha * (a + b)   (b may be NULL): mean of the two LSTM directions and its backward
-__global__ __launch_bounds__(256) void scale_add_kernel(const float* __restrict__ a, const float* __restrict__ b, float alpha,
-                                                        float* __restrict__ y, long n) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        y[i] = alpha * (a[i] + (b ? b[i] : 0.f));
-}
-// continuous bag of words: y[b][j] = (sum_{|k-j| <= c, k != j, 0 <= k < L} x[b][k]) / (2c); symmetric -> its own backward
-__global__ __launch_bounds__(256) void cbow_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int L, int E, int c) {
-    const long total = (long)B * L * E;
-    const float inv = 1.f / (float)(2 * c);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int e = (int)(i % E);
-        const long r = i / E;
-        const int j = (int)(r % L);
-        const long b = r / L;
-        float acc = 0.f;
-        for (int k = max(j - c, 0); k <= min(j + c, L - 1); ++k)
-            if (k != j) acc += x[(b * L + k) * E + e];
-        y[i] = acc * inv;
-    }
-}
-}  // namespace
-
-extern "C" int cvcl_seq_reverse(const float* x, const int64_t* len, float* y, int B, int L, int E, void* stream) {
-    CVCL_CHECK_ARG(x && len && y && x != y && B > 0 && L > 0 && E > 0, "cvcl_seq_reverse: bad args");
-    CvclProfScope prof(stream, CVCL_K_LSTM);
-    hipLaunchKernelGGL(seq_reverse_kernel, dim3(grid_for((long)B * L * E)), dim3(256), 0, (hipStream_t)stream, x, len, y, B, L, E);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_scale_add_f32(const float* a, const float* b, float alpha, float* y, long n, void* stream) {
-    CVCL_CHECK_ARG(a && y && n > 0, "cvcl_scale_add_f32: bad args");
-    CvclProfScope prof(stream, CVCL_K_OTHER);
-    hipLaunchKernelGGL(scale_add_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a, b, alpha, y, n);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_cbow(const float* x, float* y, int B, int L, int E, int crange, void* stream) {
-    CVCL_CHECK_ARG(x && y && x != y && B > 0 && L > 0 && E > 0 && crange > 0, "cvcl_cbow: bad args");
-    CvclProfScope prof(stream, CVCL_K_HEAD);
-    hipLaunchKernelGGL(cbow_kernel, dim3(grid_for((long)B * L * E)), dim3(256), 0, (hipStream_t)stream, x, y, B, L, E, crange);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }

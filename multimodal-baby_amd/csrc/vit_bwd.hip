@@ -170,11 +170,6 @@ __global__ __launch_bounds__(256) void batch_sum_bf16_kernel(const bf16_t* __res
     }
 }
 
-int grid_1d(long n, int cap = 4096) {
-    long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 }  // namespace
 
 // number of partial rows ([2][D] each) cvcl_layernorm_bwd_rows writes for `rows` rows
@@ -214,7 +209,7 @@ extern "C" int cvcl_layernorm_bwd_rows(const void* x, long x_row_stride, const f
 extern "C" int cvcl_gelu_bf16(const void* u, const void* d_y, void* y, long n, void* stream) {
     CVCL_CHECK_ARG(u && y && n > 0 && n % 8 == 0, "cvcl_gelu_bf16: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
-    hipLaunchKernelGGL(gelu_kernel, dim3(grid_1d(n / 8, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)u, (const bf16_t*)d_y,
+    hipLaunchKernelGGL(gelu_kernel, dim3(cvcl_grid(n / 8, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)u, (const bf16_t*)d_y,
                        (bf16_t*)y, n / 8);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
@@ -224,9 +219,9 @@ extern "C" int cvcl_gelu_bf16(const void* u, const void* d_y, void* y, long n, v
 extern "C" int cvcl_vit_tokens_bwd(const void* dh, void* d_tok, float* d_pos, int B, int T, int D, void* stream) {
     CVCL_CHECK_ARG(dh && d_tok && d_pos && B > 0 && T > 1 && D % 8 == 0, "cvcl_vit_tokens_bwd: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
-    hipLaunchKernelGGL(vit_tokens_bwd_kernel, dim3(grid_1d((long)B * (T - 1) * D / 8, 8192)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(vit_tokens_bwd_kernel, dim3(cvcl_grid((long)B * (T - 1) * D / 8, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)dh, (bf16_t*)d_tok, B, T, D);
-    hipLaunchKernelGGL(batch_sum_bf16_kernel, dim3(grid_1d((long)T * D / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dh, d_pos, B,
+    hipLaunchKernelGGL(batch_sum_bf16_kernel, dim3(cvcl_grid((long)T * D / 8, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dh, d_pos, B,
                        (long)T * D);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;

@@ -509,25 +509,6 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_reduce_kernel(const float* __
     }
 }
 
-int grid_1d(long n, int cap) {
-    const long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int set_lds(const void* k0, const void* k1, const void* k2, CvclLdsAttr& attr, const char* fn) {
-    if (attr.ready()) return CVCL_OK;
-    const void* ks[3] = {k0, k1, k2};
-    for (const void* k : ks)
-        if (k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            cvcl_set_error("%s: cannot raise the dynamic LDS limit", fn);
-            return CVCL_ELAUNCH;
-        }
-    attr.mark();
-    return CVCL_OK;
-}
-
 }  // namespace
 
 // qkv [B][T][3][heads][64] fp32 -> out [B][T][heads*64] fp32, lse [B][heads][T] fp32 (log2 units, as cvcl_attention_train).
@@ -537,10 +518,10 @@ extern "C" int cvcl_attention_train_f32(const float* qkv, float* out, float* lse
     CVCL_CHECK_ARG(qkv && out && lse && B > 0 && heads > 0, "cvcl_attention_train_f32: bad args");
     CVCL_CHECK_ARG(head_dim == 64 && T > 32 && T <= AF_TPAD_MAX, "cvcl_attention_train_f32: needs head_dim 64 and 32 < T <= %d (got hd %d, T %d)",
                    AF_TPAD_MAX, head_dim, T);
-    CVCL_CHECK_ARG(aligned16(qkv) && aligned16(out), "cvcl_attention_train_f32: qkv / out must be 16-byte aligned");
+    CVCL_CHECK_ARG(cvcl_aligned16(qkv) && cvcl_aligned16(out), "cvcl_attention_train_f32: qkv / out must be 16-byte aligned");
     static CvclLdsAttr attr;
-    const int rc = set_lds((const void*)attention_f32_fwd_kernel, nullptr, nullptr, attr, "cvcl_attention_train_f32");
-    if (rc) return rc;
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)attention_f32_fwd_kernel, 160 * 1024, "cvcl_attention_train_f32")) return rc;
+    attr.mark();
     const int nt = (T + 31) / 32;
     CvclProfScope prof(stream, CVCL_K_ATTENTION);
     hipLaunchKernelGGL(attention_f32_fwd_kernel, dim3(B * heads), dim3(AF_THREADS), (size_t)nt * 32 * AF_P * 4 * 2, (hipStream_t)stream, qkv,
@@ -555,11 +536,11 @@ extern "C" int cvcl_attention_bwd_f32(const float* qkv, const float* o, const fl
     CVCL_CHECK_ARG(qkv && o && d_o && lse && d_qkv && B > 0 && heads > 0, "cvcl_attention_bwd_f32: bad args");
     CVCL_CHECK_ARG(head_dim == 64 && T > 32 && T <= AF_TPAD_MAX, "cvcl_attention_bwd_f32: needs head_dim 64 and 32 < T <= %d (got hd %d, T %d)",
                    AF_TPAD_MAX, head_dim, T);
-    CVCL_CHECK_ARG(aligned16(qkv) && aligned16(o) && aligned16(d_o) && aligned16(d_qkv), "cvcl_attention_bwd_f32: operands must be 16-byte aligned");
+    CVCL_CHECK_ARG(cvcl_aligned16(qkv) && cvcl_aligned16(o) && cvcl_aligned16(d_o) && cvcl_aligned16(d_qkv), "cvcl_attention_bwd_f32: operands must be 16-byte aligned");
     static CvclLdsAttr attr;
-    const int rc = set_lds((const void*)attention_f32_bwd_dq_kernel, (const void*)attention_f32_bwd_dkv_kernel, nullptr, attr,
-                           "cvcl_attention_bwd_f32");
-    if (rc) return rc;
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)attention_f32_bwd_dq_kernel, 160 * 1024, "cvcl_attention_bwd_f32")) return rc;
+    if (const int rc = cvcl_raise_lds_limit(attr, (const void*)attention_f32_bwd_dkv_kernel, 160 * 1024, "cvcl_attention_bwd_f32")) return rc;
+    attr.mark();
     const int nt = (T + 31) / 32, Tpad = nt * 32;
     hipStream_t s = (hipStream_t)stream;
     CvclProfScope prof(stream, CVCL_K_ATTENTION);
@@ -575,8 +556,8 @@ extern "C" int cvcl_attention_bwd_f32(const float* qkv, const float* o, const fl
 extern "C" int cvcl_layernorm_bwd_rows_f32(const float* x, long x_row_stride, const float* gamma, const float* dy, long dy_row_stride, float eps,
                                            const float* add, float* dx, long dx_row_stride, float* partial, long rows, int D, void* stream) {
     CVCL_CHECK_ARG(x && gamma && dy && dx && partial && rows > 0 && D > 0, "cvcl_layernorm_bwd_rows_f32: bad args");
-    CVCL_CHECK_ARG(D % 4 == 0 && D <= 1024 && x_row_stride % 4 == 0 && dy_row_stride % 4 == 0 && dx_row_stride % 4 == 0 && aligned16(x) &&
-                       aligned16(dy) && aligned16(dx) && aligned16(gamma) && aligned16(add) && aligned16(partial),
+    CVCL_CHECK_ARG(D % 4 == 0 && D <= 1024 && x_row_stride % 4 == 0 && dy_row_stride % 4 == 0 && dx_row_stride % 4 == 0 && cvcl_aligned16(x) &&
+                       cvcl_aligned16(dy) && cvcl_aligned16(dx) && cvcl_aligned16(gamma) && cvcl_aligned16(add) && cvcl_aligned16(partial),
                    "cvcl_layernorm_bwd_rows_f32: needs D %% 4 == 0, D <= 1024 and 16-byte aligned rows (D %d)", D);
     const int wgs = cvcl_layernorm_bwd_rows_partials(rows) / 4;          // one partial row per wave: exactly that many rows written
     CvclProfScope prof(stream, CVCL_K_LAYERNORM);
@@ -593,20 +574,20 @@ extern "C" int cvcl_layernorm_bwd_rows_f32(const float* x, long x_row_stride, co
 }
 
 extern "C" int cvcl_gelu_f32(const float* u, const float* d_y, float* y, long n, void* stream) {
-    CVCL_CHECK_ARG(u && y && n > 0 && n % 4 == 0 && aligned16(u) && aligned16(d_y) && aligned16(y), "cvcl_gelu_f32: bad args");
+    CVCL_CHECK_ARG(u && y && n > 0 && n % 4 == 0 && cvcl_aligned16(u) && cvcl_aligned16(d_y) && cvcl_aligned16(y), "cvcl_gelu_f32: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
-    hipLaunchKernelGGL(gelu_f32_kernel, dim3(grid_1d(n / 4, 8192)), dim3(256), 0, (hipStream_t)stream, u, d_y, y, n / 4);
+    hipLaunchKernelGGL(gelu_f32_kernel, dim3(cvcl_grid(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, u, d_y, y, n / 4);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }
 
 extern "C" int cvcl_vit_tokens_bwd_f32(const float* dh, float* d_tok, float* d_pos, int B, int T, int D, void* stream) {
-    CVCL_CHECK_ARG(dh && d_tok && d_pos && B > 0 && T > 1 && D > 0 && D % 4 == 0 && aligned16(dh) && aligned16(d_tok) && aligned16(d_pos),
+    CVCL_CHECK_ARG(dh && d_tok && d_pos && B > 0 && T > 1 && D > 0 && D % 4 == 0 && cvcl_aligned16(dh) && cvcl_aligned16(d_tok) && cvcl_aligned16(d_pos),
                    "cvcl_vit_tokens_bwd_f32: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
-    hipLaunchKernelGGL(vit_tokens_bwd_f32_kernel, dim3(grid_1d((long)B * (T - 1) * D / 4, 8192)), dim3(256), 0, (hipStream_t)stream, dh, d_tok,
+    hipLaunchKernelGGL(vit_tokens_bwd_f32_kernel, dim3(cvcl_grid((long)B * (T - 1) * D / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, dh, d_tok,
                        B, T, D);
-    hipLaunchKernelGGL(batch_sum_f32_kernel, dim3(grid_1d((long)T * D / 4, 4096)), dim3(256), 0, (hipStream_t)stream, dh, d_pos, B, (long)T * D);
+    hipLaunchKernelGGL(batch_sum_f32_kernel, dim3(cvcl_grid((long)T * D / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, dh, d_pos, B, (long)T * D);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }
@@ -632,7 +613,7 @@ extern "C" int cvcl_gemm_tn_colsum_f32(const float* A, int lda, const float* B, 
     float* cpart = part + (size_t)p.S * N * K;
     CvclProfScope prof(stream, CVCL_K_WGRAD);
     hipLaunchKernelGGL(gemm_tn_f32_partial_kernel, dim3(p.tn, p.tk, p.S), dim3(256), 0, s, A, lda, B, ldb, M, N, K, p.chunk, part, cpart);
-    hipLaunchKernelGGL(gemm_tn_f32_reduce_kernel, dim3(grid_1d((long)N * k_keep + N, 8192)), dim3(256), 0, s, (const float*)part,
+    hipLaunchKernelGGL(gemm_tn_f32_reduce_kernel, dim3(cvcl_grid((long)N * k_keep + N, 256, 8192)), dim3(256), 0, s, (const float*)part,
                        (const float*)cpart, p.S, N, K, k_keep, C, colsum);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;

@@ -215,8 +215,6 @@ __global__ __launch_bounds__(256) void cls_maps_kernel(const float* __restrict__
     }
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int cvcl_attention_probs(int dtype, const void* qkv, float* probs, int B, int T, int heads, int head_dim, float scale,
@@ -232,7 +230,7 @@ extern "C" int cvcl_attention_probs(int dtype, const void* qkv, float* probs, in
     const int nqt = cvcl_div_up(q_rows, mfma ? AP_QT : 4);
     const long grid = (long)B * heads * nqt;
     CVCL_CHECK_ARG(grid <= 0x7fffffffL, "cvcl_attention_probs: grid of %ld workgroups is too large", grid);
-    CVCL_CHECK_ARG(!mfma || al16(qkv), "cvcl_attention_probs: qkv must be 16-byte aligned");
+    CVCL_CHECK_ARG(!mfma || cvcl_aligned16(qkv), "cvcl_attention_probs: qkv must be 16-byte aligned");
     const hipStream_t s = (hipStream_t)stream;
     CvclProfScope prof(stream, CVCL_K_ATTENTION);
     if (mfma) {

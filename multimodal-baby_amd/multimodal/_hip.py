@@ -205,12 +205,12 @@ SIGNATURES = {
     # ViT self-attention maps (csrc/vit_maps.hip)
     "cvcl_attention_probs": (_I, [_I, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     "cvcl_cls_attention_maps": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    # beam-search decoding (csrc/textgen.hip)
+    # beam-search decoding (csrc/textgen.hip; the decode cell and the first BPTT step of the captioning state: csrc/lstm.hip)
     "cvcl_beam_step": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "cvcl_beam_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cvcl_lstm_cell_tok": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P]),
     "cvcl_lstm_cell_bwd_first": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    # per-word Grad-CAM of the captioning LM (csrc/caption_cam.hip)
+    # per-word Grad-CAM of the captioning LM (the multi-seed BPTT step: csrc/lstm.hip; the seed-major F.normalize backward: csrc/head.hip)
     "cvcl_lstm_cell_bwd_seeds": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, C.c_long, _P]),
     "cvcl_l2norm_bwd_seeds": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
     # nearest-neighbour searches (csrc/neighbors.hip)

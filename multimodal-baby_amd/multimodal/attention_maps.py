@@ -7,7 +7,7 @@ backward reaches the hooked layer-4 map through the trunk's avgpool bridge, ``re
 ``gradCAM_pairs`` is the batched form for the flat ResNeXt encoder -- one trunk pass, then every requested (image, target)
 map as one exact-fp32 MFMA contraction over the layer-4 map (cvcl_hip.h, "Grad-CAM").  ``gradCAM_captions`` /
 ``gradCAM_for_captioning_lm`` (reference analysis_tools/multimodal_visualization.py:9-49) give one map per word of a caption for the
-captioning LM: the per-word gradients of all captions come from one multi-seed BPTT sweep (csrc/caption_cam.hip) and feed the same
+captioning LM: the per-word gradients of all captions come from one multi-seed BPTT sweep (csrc/lstm.hip) and feed the same
 contraction.  The plotting helpers are host-side
 numpy / matplotlib; matplotlib and scipy are imported only when a helper needs them."""
 from __future__ import annotations

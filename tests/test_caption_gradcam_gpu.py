@@ -1,4 +1,4 @@
-"""Per-word Grad-CAM of the captioning LM on the MI355X (csrc/caption_cam.hip, multimodal/attention_maps.py): against the reference's
+"""Per-word Grad-CAM of the captioning LM on the MI355X (csrc/lstm.hip, csrc/head.hip, multimodal/attention_maps.py): against the reference's
 own maps (tests/golden/caption_gradcam.npz), against the per-word loop through the autograd bridges on the device, against float64
 autograd on the CPU at configuration size, the seed kernel alone against cvcl_lstm_cell_bwd on replicated rows, and the interface.
 

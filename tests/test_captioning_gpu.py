@@ -1,4 +1,4 @@
-"""GPU: beam-search decoding of the LSTM language model (csrc/textgen.hip, ops.beam_search_lstm, LanguageModel.beam_search_decode).
+"""GPU: beam-search decoding of the LSTM language model (csrc/textgen.hip, csrc/lstm.hip, ops.beam_search_lstm, LanguageModel.beam_search_decode).
 
 - cvcl_beam_step alone at B = 256, V = 2350 against a float64 restatement of one step of the reference algorithm written here;
 - the whole decode against the reference's own beam_search_decode (tests/golden/captioning_beam.npz, tools/gen_golden_captioning.py);
