@@ -814,6 +814,34 @@ size_t cvcl_triu_pearson_workspace_bytes(int C);
 int cvcl_triu_pearson_f32(const float* A, const float* B, int C, double* out6, void* workspace, size_t workspace_bytes, void* stream);
 int cvcl_paired_l2_f32(const float* x, const float* y, int C, int D, float eps, float* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Word statistics (csrc/token_items.hip): the per-word language-model analysis of the reference's analysis_tools/processing.py.
+ * Both entries validate everything before they enqueue anything (CVCL_EINVAL, cvcl_last_error names the argument), enqueue on the
+ * caller's stream only and use no atomics: two calls on the same inputs give the same bits.
+ *
+ * cvcl_token_items_accumulate: `token_pos_items[key] += SumData(1, loss_.item(), outputs_, None)` for every token of a batch
+ *   (processing.py:326-331) as one in-order segmented sum.  outputs [N, H] f32 and loss [N] f32 are the batch's N = B L positions;
+ *   the positions that carry a key are listed by a CSR over the keys present in the batch: segment s covers rows[seg_ptr[s] ..
+ *   seg_ptr[s + 1]) (int32 row indices in [0, N), ascending = the reference's visiting order; n_valid = seg_ptr[S]) and adds into
+ *   entry slot[s] of the running tables vector [K, H] f32, loss_sum [K] double, cnt [K] int64.  One workgroup owns a (slot, column
+ *   range): it loads the running value and adds the rows one by one, ((acc + v1) + v2) + ..., in fp32 for the vector and in double
+ *   for the loss -- the reference's sums bit for bit, whatever H (no alignment requirement).  The slots of a call must be distinct.
+ *   A segment whose slot lies outside [0, K) or whose bounds are not 0 <= begin < end <= n_valid is left out, and so is a row
+ *   index outside [0, N): nothing is read or written out of bounds.  S = 0 is allowed (nothing happens).  CVCL_K_OTHER.
+ * cvcl_token_topk: `logits.softmax(-1)` (processing.py:352) and `values.topk(top_k, -1)` (analysis_tools/utils.py:142) in one
+ *   pass.  logits [R, V] f32, labels [R] int64, 1 <= k <= CVCL_TOKEN_TOPK_MAX_K, k <= V <= 12288 (a row is held in LDS and read
+ *   from memory once) -> top_prob [R, k] f32 and top_idx [R, k] int64 ordered by (probability desc, index asc): ties go to the
+ *   lower index; label_prob [R] f32 = the probability of labels[r], 0 where the label is pad_id or outside [0, V); probs [R, V]
+ *   f32 = the whole softmax when the pointer is not NULL (nothing is written otherwise; it must not alias logits).  The logits
+ *   must be finite, or -inf in some but not all entries of a row: a row of -inf only, or one holding +inf or NaN, has NaN
+ *   probabilities and no order, and its top_idx entries are written as INT32_MAX (never used as an address).  CVCL_K_HEAD. */
+enum { CVCL_TOKEN_TOPK_MAX_K = 16 };
+int cvcl_token_items_accumulate(const float* outputs, const float* loss, int N, int H, const int32_t* seg_ptr, const int32_t* rows,
+                                const int32_t* slot, int S, int n_valid, float* vector, double* loss_sum, int64_t* cnt, int K,
+                                void* stream);
+int cvcl_token_topk(const float* logits, const int64_t* labels, long R, int V, int k, int pad_id, float* top_prob, int64_t* top_idx,
+                    float* label_prob, float* probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,9 @@ __device__ inline float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// (score desc, index asc): a total order on the candidates of a selection over the vocabulary, so every selection is deterministic
+// and ties go to the lower index (the beam step, csrc/textgen.hip; the top-k of csrc/token_items.hip)
+__device__ __forceinline__ bool cvcl_better(float s, int i, float t, int j) { return s > t || (s == t && i < j); }
 // block-wide sum through LDS scratch of >= (blockDim/64) floats; result broadcast to all threads
 __device__ inline float block_sum(float v, float* scratch) {
     v = wave_sum(v);

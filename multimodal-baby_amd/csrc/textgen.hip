@@ -12,9 +12,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / CVCL_WAVE;
 constexpr float kInf = 1e7f;                          // beam_search.py INF: the penalty added to unfinished / finished scores
 
-// (score desc, flat index asc): a total order on the candidates, so every selection is deterministic
-__device__ __forceinline__ bool better(float s, int i, float t, int j) { return s > t || (s == t && i < j); }
-
 // One workgroup per batch item b.  M: per-lane candidate list length (>= 2K).
 template <int M>
 __global__ __launch_bounds__(kThreads) void beam_step_kernel(
@@ -89,12 +86,12 @@ __global__ __launch_bounds__(kThreads) void beam_step_kernel(
     for (int f = tid; f < KV; f += kThreads) {
         const int k = f / V;
         const float s = ((lg[f] - s_lse[k]) + s_alp[k]) / lp;
-        if (better(s, f, ls[M - 1], li[M - 1])) {
+        if (cvcl_better(s, f, ls[M - 1], li[M - 1])) {
             ls[M - 1] = s;
             li[M - 1] = f;
 #pragma unroll
             for (int j = M - 1; j > 0; --j) {
-                if (better(ls[j], li[j], ls[j - 1], li[j - 1])) {
+                if (cvcl_better(ls[j], li[j], ls[j - 1], li[j - 1])) {
                     const float ts = ls[j]; ls[j] = ls[j - 1]; ls[j - 1] = ts;
                     const int ti = li[j]; li[j] = li[j - 1]; li[j - 1] = ti;
                 }
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(kThreads) void beam_step_kernel(
         for (int o = 32; o > 0; o >>= 1) {
             const float os = __shfl_xor(bs, o, 64);
             const int oi = __shfl_xor(bi, o, 64);
-            if (better(os, oi, bs, bi)) { bs = os; bi = oi; }
+            if (cvcl_better(os, oi, bs, bi)) { bs = os; bi = oi; }
         }
         if (lane == 0) { s_red_s[r & 1][w] = bs; s_red_i[r & 1][w] = bi; }
         __syncthreads();
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void beam_step_kernel(
         bi = s_red_i[r & 1][0];
 #pragma unroll
         for (int q = 1; q < kWaves; ++q)
-            if (better(s_red_s[r & 1][q], s_red_i[r & 1][q], bs, bi)) { bs = s_red_s[r & 1][q]; bi = s_red_i[r & 1][q]; }
+            if (cvcl_better(s_red_s[r & 1][q], s_red_i[r & 1][q], bs, bi)) { bs = s_red_s[r & 1][q]; bi = s_red_i[r & 1][q]; }
         if (tid == 0) { s_cs[r] = bs; s_ci[r] = bi; }
         if (li[0] == bi) {                            // flat indices are unique: exactly one lane owned the winner
 #pragma unroll
@@ -140,7 +137,7 @@ __global__ __launch_bounds__(kThreads) void beam_step_kernel(
                 if (taken[r]) continue;
                 const bool fin = s_ci[r] % V == eos_id;
                 const float v = s_cs[r] + (fin ? -kInf : -0.f);
-                if (bj < 0 || better(v, r, bv, bj)) { bj = r; bv = v; }
+                if (bj < 0 || cvcl_better(v, r, bv, bj)) { bj = r; bv = v; }
             }
             taken[bj] = true;
             s_apar[k] = s_ci[bj] / V;
@@ -163,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void beam_step_kernel(
                     const bool fin = s_ci[j - K] % V == eos_id;
                     v = s_cs[j - K] + (fin ? -0.f : -kInf);
                 }
-                if (bj < 0 || better(v, j, bv, bj)) { bj = j; bv = v; }
+                if (bj < 0 || cvcl_better(v, j, bv, bj)) { bj = j; bv = v; }
             }
             taken[bj] = true;
             fin_out[bk + k] = bv;

@@ -21,6 +21,7 @@ ABI_VERSION = 7
 PACK_DENSE, PACK_STEM7, PACK_GCONV3 = 0, 1, 2
 GRADCAM_ALL, GRADCAM_BLOCK_IMAGE, GRADCAM_BLOCK_TEXT = 0, 1, 2      # cvcl_hip.h CVCL_GRADCAM_*
 BEAM_MAX_K, BEAM_MAX_T = 16, 128                                 # cvcl_hip.h CVCL_BEAM_MAX_*
+TOKEN_TOPK_MAX_K = 16                                            # cvcl_hip.h CVCL_TOKEN_TOPK_MAX_K
 KERNEL_CLASSES = ("gemm", "gconv3x3", "stem7x7", "bn_finalize", "bn_add_relu", "bn_relu_maxpool", "avgpool", "head",
                   "other", "attention", "layernorm", "lstm", "gemm_f32", "bn_relu_apply", "bn_bwd", "wgrad", "gemm8w", "gemm_pro")
 
@@ -225,6 +226,9 @@ SIGNATURES = {
     "cvcl_triu_pearson_workspace_bytes": (_SZ, [_I]),
     "cvcl_triu_pearson_f32": (_I, [_P, _P, _I, _P, _P, _SZ, _P]),
     "cvcl_paired_l2_f32": (_I, [_P, _P, _I, _I, _F, _P, _P]),
+    # word statistics (csrc/token_items.hip)
+    "cvcl_token_items_accumulate": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
+    "cvcl_token_topk": (_I, [_P, _P, C.c_long, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -439,3 +439,40 @@ def transformer_text(table, layer, pos_embed, tok, length):
         ret = torch.empty(B, E, dtype=_F, device=x.device)
         H.check(lib.cvcl_seq_sum_div(H.ptr(h2), H.ptr(length, torch.int64), H.ptr(ret), B, L, E, s), "cvcl_seq_sum_div")
     return ret, h2.view(B, L, E)
+
+
+def token_items_accumulate(outputs, loss, seg_ptr, rows, slot, vector, loss_sum, cnt):
+    """The per-key sums of one batch (reference analysis_tools/processing.py:326-331) added in place to the running tables
+    ``vector`` [K, H] f32, ``loss_sum`` [K] f64, ``cnt`` [K] int64.  ``outputs`` [N, H] f32 and ``loss`` [N] f32 are the batch's
+    positions; ``seg_ptr`` [S + 1], ``rows`` [seg_ptr[-1]], ``slot`` [S] (int32, on the device) the CSR over the keys present:
+    cvcl_token_items_accumulate adds every segment's rows one by one in ``rows`` order.  The caller guarantees that the entries
+    of ``slot`` are distinct (processing.build_batch_csr does): nothing checks it, and two segments of one slot would race on
+    the key's table row."""
+    N, Hd = outputs.shape
+    S = slot.numel()
+    if seg_ptr.numel() != S + 1 or loss.numel() != N or vector.dim() != 2 or vector.shape[1] != Hd or \
+            loss_sum.numel() != vector.shape[0] or cnt.numel() != vector.shape[0]:
+        raise ValueError("token_items_accumulate: shapes do not fit together")
+    i32 = torch.int32
+    H.check(H.lib().cvcl_token_items_accumulate(
+        H.ptr(outputs, _F), H.ptr(loss, _F), N, Hd, H.ptr(seg_ptr, i32), H.ptr(rows, i32), H.ptr(slot, i32), S, rows.numel(),
+        H.ptr(vector, _F), H.ptr(loss_sum, torch.float64), H.ptr(cnt, torch.int64), vector.shape[0], H.stream_ptr()),
+        "cvcl_token_items_accumulate")
+
+
+def token_topk(logits, labels, k, pad_id=0, want_probs=False):
+    """Softmax over the vocabulary and its ``k`` best entries in one pass (reference processing.py:352, utils.py:142) ->
+    (top_prob [R, k] f32, top_idx [R, k] int64, label_prob [R] f32, probs [R, V] f32 or None).  Ordered by (probability desc,
+    index asc); ``label_prob`` is 0 where the label is ``pad_id``."""
+    R, V = logits.shape
+    dev = logits.device
+    if labels.numel() != R:
+        raise ValueError("token_topk: one label per row")
+    H.ptr(logits, _F)                                       # refuses CPU tensors before anything is allocated beside them
+    top_prob = torch.empty(R, k, dtype=_F, device=dev)
+    top_idx = torch.empty(R, k, dtype=torch.int64, device=dev)
+    label_prob = torch.empty(R, dtype=_F, device=dev)
+    probs = torch.empty(R, V, dtype=_F, device=dev) if want_probs else None
+    H.check(H.lib().cvcl_token_topk(H.ptr(logits, _F), H.ptr(labels, torch.int64), R, V, int(k), int(pad_id), H.ptr(top_prob),
+                                    H.ptr(top_idx), H.ptr(label_prob), H.ptr(probs), H.stream_ptr()), "cvcl_token_topk")
+    return top_prob, top_idx, label_prob, probs
