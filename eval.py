@@ -78,13 +78,14 @@ def results_filename(args, cfg):
 
 
 @torch.no_grad()
-def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention_maps=False):
+def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention_maps=False, rollout=False):
     """trials: list of collated batch-1 items (img, label, label_len, raw_label).  Returns per trial (soft-max list, pred).
     All trials of the list are encoded in one pass; trial t's logits are the t-th diagonal block.
     ``attention_maps``: returns (per-trial results, Grad-CAM maps [T, 4, h, w]) -- per trial the maps of its 4 images w.r.t. its
     label (``image``) or of its image w.r.t. its 4 labels (``text``), from the same encoder pass as the logits.  A ViT encoder has
     no Grad-CAM: its maps are the CLS token's last-block self-attention [T, 4, gh, gw], which do not depend on the label (``text``:
-    the one image's map repeated 4 times, so the array keeps its shape)."""
+    the one image's map repeated 4 times, so the array keeps its shape); with ``rollout`` they are the CLS token's attention rollout
+    over all blocks instead, same shape."""
     T = len(trials)
     if eval_type == "image":
         imgs = torch.cat([t[0].squeeze(0) for t in trials], 0).to(device)                    # [4T, ...]
@@ -106,7 +107,7 @@ def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention
         imgs = datamodule.on_after_batch_transfer((imgs,), 1, training=False)[0]
     maps = None
     if attention_maps and getattr(getattr(model, "vision_encoder", None), "vit_dino", False):
-        logits_per_image, logits_per_text, maps = model.self_attention_maps(imgs, labels.to(device), lens.to(device))
+        logits_per_image, logits_per_text, maps = model.self_attention_maps(imgs, labels.to(device), lens.to(device), rollout=rollout)
         if eval_type == "image":                          # [4T, gh, gw] -> [T, 4, gh, gw]
             maps = maps.view(T, n_per, *maps.shape[1:])
         else:                                             # one image per trial: its map along the 4 axis
@@ -179,6 +180,12 @@ def main(args):
     correct_pred = {c: 0 for c in classes}
     total_pred = {c: 0 for c in classes}
 
+    if args.attention_rollout and not getattr(model.vision_encoder, "vit_dino", False):
+        raise SystemExit("--attention_rollout is defined for a ViT checkpoint (--vit_dino) only: a ResNeXt encoder has no "
+                         "self-attention to roll out; its --attention_maps are Grad-CAM maps")
+    if args.attention_rollout and not (args.attention_maps or args.plot_attention):
+        raise SystemExit("--attention_rollout selects the kind of map --attention_maps DIR / --plot_attention write; give one of them")
+
     results, pending, first = [], [], 0
     want_maps = bool(args.attention_maps or args.plot_attention)
     cams = []
@@ -187,7 +194,7 @@ def main(args):
 
     def flush():
         nonlocal first
-        res = evaluate_trials(model, pending, args.eval_type, device, data, attention_maps=want_maps)
+        res = evaluate_trials(model, pending, args.eval_type, device, data, attention_maps=want_maps, rollout=args.attention_rollout)
         if want_maps:
             res, maps = res
             cams.append(maps.cpu())
@@ -271,6 +278,10 @@ def _parser():
     parser.add_argument("--plot_attention", action="store_true",
                         help="save one overlay PNG per trial, {model}_{class}_{i %% 100}_attn_map.png, under the --attention_maps "
                              "directory (results/ without it); needs matplotlib")
+    parser.add_argument("--attention_rollout", action="store_true",
+                        help="ViT checkpoints: the maps of --attention_maps / --plot_attention are the CLS token's attention rollout "
+                             "over all blocks (head-mean attention plus the residual path, multiplied through the blocks) instead of "
+                             "the last block's CLS row; same shape [n_trials, 4, gh, gw].  An error with a ResNeXt checkpoint")
     return parser
 
 

@@ -684,6 +684,24 @@ int cvcl_attention_probs(int dtype, const void* qkv, float* probs, int B, int T,
  * out [B][T-1] = the mean over the heads (mean != 0; summed h = 0 first, then / heads) or out [B][heads][T-1] = a copy without
  * the CLS column (mean == 0).  T > 1; out must not alias probs.  CVCL_K_OTHER.                                                 */
 int cvcl_cls_attention_maps(const float* probs, float* out, int B, int heads, int T, int mean, void* stream);
+/* Attention rollout (Abnar & Zuidema 2020; the reference's ViT has none, so the formula below is the specification).
+ * cvcl_attention_head_fuse (csrc/vit_maps.hip): qkv of ONE block as cvcl_attention_probs takes it -> fused [B][T][T] fp32,
+ *   F[b] = fuse_h softmax(q k^T * scale)[b, h],  fuse = CVCL_FUSE_MEAN (the sum in head order, times 1 / heads once), MAX or MIN.
+ * The softmax passes are those of cvcl_attention_probs (same routes, same limits: hd = 64 MFMA, other hd % 4 == 0 <= 128 VALU, qkv
+ * 16-byte aligned on the MFMA route); one workgroup owns a [128 queries][T] tile of F[b] (VALU: one wave per row), visits the heads
+ * in index order and folds each into its own elements of the tile, which stays in the L2: no [B][heads][T][T] intermediate, no
+ * atomics, two calls give the same bits.  CVCL_EINVAL as cvcl_attention_probs, and on an unknown fuse.  CVCL_K_ATTENTION.
+ * cvcl_attention_rollout (csrc/vit_rollout.hip): fused [n_layers][B][T][T] fp32 (layer 0 = the earliest block) ->
+ *   out [B][q_rows][T] fp32 = the first q_rows rows of  A^_{n_layers-1} . A^_{n_layers-2} ... A^_{start_layer},
+ *   A^_l = (F_l + I) / rowsum(F_l + I)  (the row sum is computed: it is 2 only for MEAN).
+ * A^ is formed on the fly; one workgroup per (image, 8 rows; 1 row at q_rows = 1), the row vectors in LDS, r'[j] = sum_i r[i] A^[i][j]
+ * summed over i = 0 .. T-1 in order with fp64 accumulators, the reads of F coalesced along j.  Deterministic; row q does not
+ * depend on q_rows.  1 <= n_layers, 0 <= start_layer < n_layers, 1 <= q_rows <= T <= 960 (LDS: 17 T floats); out must not alias
+ * fused.  No workspace.  CVCL_K_ATTENTION.                                                                                     */
+enum { CVCL_FUSE_MEAN = 0, CVCL_FUSE_MAX = 1, CVCL_FUSE_MIN = 2 };
+int cvcl_attention_head_fuse(int dtype, const void* qkv, float* fused, int B, int T, int heads, int head_dim, float scale, int fuse,
+                             void* stream);
+int cvcl_attention_rollout(const float* fused, float* out, int n_layers, int B, int T, int start_layer, int q_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Beam-search decoding of the LSTM language model (csrc/textgen.hip; its LSTM cells: csrc/lstm.hip).  Replaces the reference's LanguageModel.beam_search_decode

@@ -4,6 +4,8 @@
 //
 //   cvcl_attention_probs     qkv [B][T][3][heads][hd] (fp32 or bf16) -> probs [B][heads][q_rows][T] fp32, queries 0 .. q_rows-1
 //   cvcl_cls_attention_maps  the CLS query's row without its CLS column, per head or averaged over the heads
+//   cvcl_attention_head_fuse the same softmax passes, folded over the heads (mean / max / min) -> F [B][T][T] fp32: the input of the
+//                            attention rollout (csrc/vit_rollout.hip); no [B][heads][T][T] intermediate
 //
 // head_dim 64 (every DINO ViT), MFMA route.  One 256-thread workgroup owns (image, head, tile of 128 queries); each of its 4 waves owns
 // 32 queries, whose q rows stay in registers as the MFMA A operand.  The keys stream through LDS in tiles of 64 (two buffers, one barrier
@@ -55,24 +57,24 @@ __device__ __forceinline__ f32x16 ap_mma(f32x16 acc, const bf16x8& a, const bf16
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
 }
 
-template <typename T>
-__global__ __launch_bounds__(AP_THREADS) void attention_probs_kernel(const T* __restrict__ qkv, float* __restrict__ probs, int Tn,
-                                                                     int heads, float scale, int q_rows, int nqt) {
+// One (image, head, tile of 128 queries): both softmax passes.  ``base`` is q of token 0 of that image and head (k at + D), q0 this
+// wave's first query, sK the workgroup's two key buffers; emit(row, key, p) receives every probability of the rows < q_rows exactly
+// once, row by row in runs of 32 keys per half wave.  Shared by cvcl_attention_probs (emit = a store) and cvcl_attention_head_fuse
+// (emit = the fold into the head-fused tile).  A workgroup may call it again at once (the next head): the buffer a call stages first
+// was last read before the previous call's final barrier, the other one before the barrier of the new call's first tile.
+template <typename T, typename Emit>
+__device__ __forceinline__ void ap_softmax_tile(T (&sK)[2][AP_KT * ApTraits<T>::kPitch], const T* __restrict__ base, int Tn, int D,
+                                                float scale, int q_rows, int q0, Emit emit) {
     using Tr = ApTraits<T>;
     using Frag = typename Tr::Frag;
     constexpr int PER = ElemTraits<T>::kPerChunk;            // elements per 16-byte chunk
     constexpr int CPR = 64 / PER;                            // chunks per key row
     constexpr int NCH = AP_KT * CPR / AP_THREADS;            // chunks a thread stages per tile
     constexpr int RSTEP = AP_THREADS / CPR;                  // key rows between a thread's chunks
-    __shared__ __attribute__((aligned(16))) T sK[2][AP_KT * Tr::kPitch];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
-    const int qt = blockIdx.x % nqt, hh = (blockIdx.x / nqt) % heads, b = blockIdx.x / (nqt * heads);
-    const int D = heads * 64;
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
     const long rs = 3L * D;
-    const T* base = qkv + (long)b * Tn * rs + hh * 64;      // q of token 0; k at + D
     const int nkt = cvcl_div_up(Tn, AP_KT);
-    const int q0 = qt * AP_QT + wave * 32;
     const bool active = q0 < q_rows;                         // wave-uniform; idle waves still stage and meet the barriers
 
     // this wave's queries: lane (l31, h) holds the dims its half contracts, for query q0 + l31 (clamped: masked at the store)
@@ -97,7 +99,6 @@ __global__ __launch_bounds__(AP_THREADS) void attention_probs_kernel(const T* __
     float m[16], l[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { m[r] = -INFINITY; l[r] = 0.f; }
-    float* out = probs + ((long)(b * heads + hh) * q_rows) * Tn;
 
     fetch(0);
     for (int st = 0; st < 2 * nkt; ++st) {
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(AP_THREADS) void attention_probs_kernel(const T* __
                         for (int r = 0; r < 16; ++r) {
                             const int row = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
                             const float p = __builtin_amdgcn_exp2f((s[r] * scale - m[r]) * AP_LOG2E) * l[r];
-                            if (row < q_rows) out[(long)row * Tn + key] = p;
+                            if (row < q_rows) emit(row, key, p);
                         }
                     }
                 }
@@ -158,10 +159,73 @@ __global__ __launch_bounds__(AP_THREADS) void attention_probs_kernel(const T* __
     }
 }
 
+template <typename T>
+__global__ __launch_bounds__(AP_THREADS) void attention_probs_kernel(const T* __restrict__ qkv, float* __restrict__ probs, int Tn,
+                                                                     int heads, float scale, int q_rows, int nqt) {
+    __shared__ __attribute__((aligned(16))) T sK[2][AP_KT * ApTraits<T>::kPitch];
+    const int wave = threadIdx.x >> 6;
+    const int qt = blockIdx.x % nqt, hh = (blockIdx.x / nqt) % heads, b = blockIdx.x / (nqt * heads);
+    const int D = heads * 64;
+    float* out = probs + ((long)(b * heads + hh) * q_rows) * Tn;
+    ap_softmax_tile<T>(sK, qkv + (long)b * Tn * 3L * D + hh * 64, Tn, D, scale, q_rows, qt * AP_QT + wave * 32,
+                       [=](int row, int key, float p) { out[(long)row * Tn + key] = p; });
+}
+
+// cvcl_attention_head_fuse, MFMA route: one workgroup owns the [128 queries][T] tile of F[b] and visits the heads in index order.  A
+// thread meets the same (row, key) in every head (the operand maps do not depend on the head), so it folds each head into ITS OWN
+// elements of the tile in global memory: head 0 stores, the later heads read back what the same thread stored, no atomics, no
+// barrier, no [heads][T][T] intermediate.  The tile (100 KB at T = 197) stays in the L2 between the heads.
+enum { FUSE_MEAN = 0, FUSE_MAX = 1, FUSE_MIN = 2 };
+
+__device__ __forceinline__ float fuse_fold(int fuse, float acc, float p) {
+    return fuse == FUSE_MEAN ? acc + p : (fuse == FUSE_MAX ? fmaxf(acc, p) : fminf(acc, p));
+}
+
+template <typename T>
+__global__ __launch_bounds__(AP_THREADS) void attention_head_fuse_kernel(const T* __restrict__ qkv, float* fused, int Tn, int heads,
+                                                                         float scale, int fuse, float inv_heads, int nqt) {
+    __shared__ __attribute__((aligned(16))) T sK[2][AP_KT * ApTraits<T>::kPitch];
+    const int wave = threadIdx.x >> 6;
+    const int qt = blockIdx.x % nqt, b = blockIdx.x / nqt;
+    const int D = heads * 64;
+    float* out = fused + (long)b * Tn * Tn;
+    for (int hh = 0; hh < heads; ++hh) {
+        const bool first = hh == 0, scale_now = fuse == FUSE_MEAN && hh == heads - 1;
+        ap_softmax_tile<T>(sK, qkv + (long)b * Tn * 3L * D + hh * 64, Tn, D, scale, Tn, qt * AP_QT + wave * 32,
+                           [=](int row, int key, float p) {
+                               float* o = out + (long)row * Tn + key;
+                               float v = first ? p : fuse_fold(fuse, *o, p);
+                               if (scale_now) v *= inv_heads;
+                               *o = v;
+                           });
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // any head_dim % 4 == 0, <= 128: one wave per query row, the lanes stride over the keys; fp32 fmaf chains in d order
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int AV_MAXHD = 128;
+
+// One query row on one wave: q [hd] fp32 (LDS), k of token 0 at ``kbase``; emit(key, p) receives the row's probabilities, lane l the
+// keys l, l + 64, ...
+template <typename T, typename Emit>
+__device__ __forceinline__ void av_softmax_row(const float* q, const T* __restrict__ kbase, long rs, int hd, int Tn, float scale, Emit emit) {
+    const int lane = threadIdx.x & 63;
+    auto score = [&](int key) {
+        const T* k = kbase + (long)key * rs;
+        float s = 0.f;
+        for (int d = 0; d < hd; ++d) s = fmaf(q[d], ElemTraits<T>::to_f(k[d]), s);
+        return s * scale;
+    };
+    float M = -INFINITY;
+    for (int key = lane; key < Tn; key += 64) M = fmaxf(M, score(key));
+    M = wave_max(M);
+    float L = 0.f;
+    for (int key = lane; key < Tn; key += 64) L += __builtin_amdgcn_exp2f((score(key) - M) * AP_LOG2E);
+    L = wave_sum(L);
+    const float inv = 1.f / L;
+    for (int key = lane; key < Tn; key += 64) emit(key, __builtin_amdgcn_exp2f((score(key) - M) * AP_LOG2E) * inv);
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void attention_probs_valu_kernel(const T* __restrict__ qkv, float* __restrict__ probs, int Tn, int heads,
@@ -178,22 +242,36 @@ __global__ __launch_bounds__(256) void attention_probs_valu_kernel(const T* __re
         for (int d = lane; d < hd; d += 64) sQ[wave][d] = ElemTraits<T>::to_f(base[(long)row * rs + d]);
     __syncthreads();
     if (!active) return;
-    const float* q = sQ[wave];
-    auto score = [&](int key) {
-        const T* k = base + D + (long)key * rs;
-        float s = 0.f;
-        for (int d = 0; d < hd; ++d) s = fmaf(q[d], ElemTraits<T>::to_f(k[d]), s);
-        return s * scale;
-    };
-    float M = -INFINITY;
-    for (int key = lane; key < Tn; key += 64) M = fmaxf(M, score(key));
-    M = wave_max(M);
-    float L = 0.f;
-    for (int key = lane; key < Tn; key += 64) L += __builtin_amdgcn_exp2f((score(key) - M) * AP_LOG2E);
-    L = wave_sum(L);
-    const float inv = 1.f / L;
     float* out = probs + ((long)(b * heads + hh) * q_rows + row) * Tn;
-    for (int key = lane; key < Tn; key += 64) out[key] = __builtin_amdgcn_exp2f((score(key) - M) * AP_LOG2E) * inv;
+    av_softmax_row<T>(sQ[wave], base + D, rs, hd, Tn, scale, [=](int key, float p) { out[key] = p; });
+}
+
+// cvcl_attention_head_fuse, VALU route: one wave per row of F[b], the heads in index order; a lane folds into its own keys.
+template <typename T>
+__global__ __launch_bounds__(256) void attention_head_fuse_valu_kernel(const T* __restrict__ qkv, float* fused, int Tn, int heads, int hd,
+                                                                       float scale, int fuse, float inv_heads, int nqt) {
+    __shared__ float sQ[4][AV_MAXHD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int qt = blockIdx.x % nqt, b = blockIdx.x / nqt;
+    const int D = heads * hd;
+    const long rs = 3L * D;
+    const int row = qt * 4 + wave;
+    const bool active = row < Tn;
+    float* out = fused + ((long)b * Tn + row) * Tn;
+    for (int hh = 0; hh < heads; ++hh) {
+        const T* base = qkv + (long)b * Tn * rs + hh * hd;
+        __syncthreads();                                     // the previous head's reads of sQ
+        if (active)
+            for (int d = lane; d < hd; d += 64) sQ[wave][d] = ElemTraits<T>::to_f(base[(long)row * rs + d]);
+        __syncthreads();
+        if (!active) continue;
+        const bool first = hh == 0, scale_now = fuse == FUSE_MEAN && hh == heads - 1;
+        av_softmax_row<T>(sQ[wave], base + D, rs, hd, Tn, scale, [=](int key, float p) {
+            float v = first ? p : fuse_fold(fuse, out[key], p);
+            if (scale_now) v *= inv_heads;
+            out[key] = v;
+        });
+    }
 }
 
 // probs [B][heads][1][T] -> out [B][T-1] (mean over the heads, h = 0 first) or out [B][heads][T-1] (a copy without column 0)
@@ -247,6 +325,44 @@ extern "C" int cvcl_attention_probs(int dtype, const void* qkv, float* probs, in
         else
             hipLaunchKernelGGL(attention_probs_valu_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)qkv, probs, T, heads,
                                head_dim, scale, q_rows, nqt);
+    }
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
+}
+
+extern "C" int cvcl_attention_head_fuse(int dtype, const void* qkv, float* fused, int B, int T, int heads, int head_dim, float scale,
+                                        int fuse, void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_attention_head_fuse");
+    CVCL_CHECK_ARG(qkv && fused, "cvcl_attention_head_fuse: null qkv / fused");
+    CVCL_CHECK_ARG(B > 0 && T > 0 && heads > 0, "cvcl_attention_head_fuse: sizes must be positive (B %d T %d heads %d)", B, T, heads);
+    CVCL_CHECK_ARG(head_dim > 0 && head_dim % 4 == 0 && head_dim <= AV_MAXHD,
+                   "cvcl_attention_head_fuse: head_dim %d is not a multiple of 4 in 4 .. %d", head_dim, AV_MAXHD);
+    CVCL_CHECK_ARG(scale == scale && scale - scale == 0.f, "cvcl_attention_head_fuse: scale must be finite");
+    CVCL_CHECK_ARG(fuse == CVCL_FUSE_MEAN || fuse == CVCL_FUSE_MAX || fuse == CVCL_FUSE_MIN,
+                   "cvcl_attention_head_fuse: fuse %d is not CVCL_FUSE_MEAN / MAX / MIN", fuse);
+    static_assert(CVCL_FUSE_MEAN == FUSE_MEAN && CVCL_FUSE_MAX == FUSE_MAX && CVCL_FUSE_MIN == FUSE_MIN, "fuse codes");
+    const bool mfma = head_dim == 64;
+    const int nqt = cvcl_div_up(T, mfma ? AP_QT : 4);
+    const long grid = (long)B * nqt;
+    CVCL_CHECK_ARG(grid <= 0x7fffffffL, "cvcl_attention_head_fuse: grid of %ld workgroups is too large", grid);
+    CVCL_CHECK_ARG(!mfma || cvcl_aligned16(qkv), "cvcl_attention_head_fuse: qkv must be 16-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    const float inv_heads = 1.f / (float)heads;
+    CvclProfScope prof(stream, CVCL_K_ATTENTION);
+    if (mfma) {
+        if (dtype == CVCL_F32)
+            hipLaunchKernelGGL(attention_head_fuse_kernel<float>, dim3((unsigned)grid), dim3(AP_THREADS), 0, s, (const float*)qkv, fused, T,
+                               heads, scale, fuse, inv_heads, nqt);
+        else
+            hipLaunchKernelGGL(attention_head_fuse_kernel<bf16_t>, dim3((unsigned)grid), dim3(AP_THREADS), 0, s, (const bf16_t*)qkv, fused,
+                               T, heads, scale, fuse, inv_heads, nqt);
+    } else {
+        if (dtype == CVCL_F32)
+            hipLaunchKernelGGL(attention_head_fuse_valu_kernel<float>, dim3((unsigned)grid), dim3(256), 0, s, (const float*)qkv, fused, T,
+                               heads, head_dim, scale, fuse, inv_heads, nqt);
+        else
+            hipLaunchKernelGGL(attention_head_fuse_valu_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)qkv, fused, T,
+                               heads, head_dim, scale, fuse, inv_heads, nqt);
     }
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;

@@ -20,6 +20,7 @@ ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 ABI_VERSION = 7
 PACK_DENSE, PACK_STEM7, PACK_GCONV3 = 0, 1, 2
 GRADCAM_ALL, GRADCAM_BLOCK_IMAGE, GRADCAM_BLOCK_TEXT = 0, 1, 2      # cvcl_hip.h CVCL_GRADCAM_*
+FUSE_MEAN, FUSE_MAX, FUSE_MIN = 0, 1, 2                             # cvcl_hip.h CVCL_FUSE_*
 BEAM_MAX_K, BEAM_MAX_T = 16, 128                                 # cvcl_hip.h CVCL_BEAM_MAX_*
 TOKEN_TOPK_MAX_K = 16                                            # cvcl_hip.h CVCL_TOKEN_TOPK_MAX_K
 KERNEL_CLASSES = ("gemm", "gconv3x3", "stem7x7", "bn_finalize", "bn_add_relu", "bn_relu_maxpool", "avgpool", "head",
@@ -206,6 +207,8 @@ SIGNATURES = {
     # ViT self-attention maps (csrc/vit_maps.hip)
     "cvcl_attention_probs": (_I, [_I, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     "cvcl_cls_attention_maps": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "cvcl_attention_head_fuse": (_I, [_I, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
+    "cvcl_attention_rollout": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     # beam-search decoding (csrc/textgen.hip; the decode cell and the first BPTT step of the captioning state: csrc/lstm.hip)
     "cvcl_beam_step": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "cvcl_beam_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -244,6 +244,22 @@ def vit_cls_attention(vision_model, x, size=None, heads="mean"):
     return maps
 
 
+@torch.no_grad()
+def vit_attention_rollout(vision_model, x, size=None, head_fusion="mean", start_layer=0):
+    """The CLS token's attention rollout over the patch tokens (Abnar & Zuidema 2020): row 0, without column 0, of
+    A^_L ... A^_{start_layer + 1} with A^_l = (F_l + I) / rowsum(F_l + I), F_l block l's attention fused over the heads
+    (``head_fusion``: "mean", "max", "min") -> [B, gh, gw] fp32.  Where vit_cls_attention shows the last block's mixing step alone,
+    this attributes the CLS token to the input patches through every block and the residual paths.  Each map sums to 1 - R[0, 0].
+    ``size=(H, W)``: resized bicubically (cvcl_bicubic_resize).  The ``discard_ratio`` variant is not built."""
+    from . import vit_maps
+    vit = _vit_of(vision_model)
+    rows, (gh, gw) = vit_maps.attention_rollout(vit, x, head_fusion, start_layer, q_rows=1)
+    maps = rows[:, 0, 1:].contiguous().view(-1, gh, gw)
+    if size is not None:
+        maps = bicubic_resize(maps, size)
+    return maps
+
+
 # ---- per-word maps of the captioning language model ----------------------------------------------------------------------
 
 MAX_CAPTION_LEN = 32                                       # the LSTM path's limit (text_train.transformer_text_train, ops.lstm_text)

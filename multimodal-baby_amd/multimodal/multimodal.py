@@ -588,6 +588,14 @@ class MultiModalModel(nn.Module):
         logits_per_image, logits_per_text = self(image, text, text_length)
         return logits_per_image, logits_per_text, maps
 
+    def attention_rollout_maps(self, image, text, text_length, head_fusion="mean", start_layer=0):
+        """self_attention_maps with the CLS token's attention rollout over all blocks in place of the last block's CLS row
+        (attention_maps.vit_attention_rollout): -> (logits_per_image, logits_per_text, maps [N, gh, gw])."""
+        from .attention_maps import vit_attention_rollout
+        maps = vit_attention_rollout(self.image_embed, image, head_fusion=head_fusion, start_layer=start_layer)
+        logits_per_image, logits_per_text = self(image, text, text_length)
+        return logits_per_image, logits_per_text, maps
+
     def calculate_contrastive_loss(self, x, y, y_len):
         logits_per_image, logits_per_text, image_features, image_feature_map, text_outputs = self(
             x, y, y_len, return_image_features=True, return_text_outputs=True)

@@ -139,8 +139,11 @@ class MultiModalLitModel(LightningModule):
         """(logits_per_image, logits_per_text, Grad-CAM maps) of one encoder pass: MultiModalModel.attention_maps."""
         return self.model.attention_maps(x, y, y_len, pairs=pairs, resize=resize)
 
-    def self_attention_maps(self, x, y, y_len):
-        """(logits_per_image, logits_per_text, the ViT's CLS self-attention maps [N, gh, gw]): MultiModalModel.self_attention_maps."""
+    def self_attention_maps(self, x, y, y_len, rollout=False, head_fusion="mean", start_layer=0):
+        """(logits_per_image, logits_per_text, the ViT's CLS self-attention maps [N, gh, gw]): MultiModalModel.self_attention_maps,
+        or with ``rollout`` the attention rollout over all blocks: MultiModalModel.attention_rollout_maps."""
+        if rollout:
+            return self.model.attention_rollout_maps(x, y, y_len, head_fusion=head_fusion, start_layer=start_layer)
         return self.model.self_attention_maps(x, y, y_len)
 
     @staticmethod

@@ -150,6 +150,12 @@ class VisionTransformer(nn.Module):
         from . import vit_maps
         return vit_maps.intermediate_layers(self, x, n)
 
+    def get_attention_rollout(self, x, head_fusion="mean", start_layer=0, q_rows=1):
+        """-> the first ``q_rows`` rows of the attention rollout A^_L ... A^_{start_layer + 1} (Abnar & Zuidema 2020), [B, q_rows, T]
+        fp32, A^_l = (F_l + I) / rowsum, F_l the block's attention fused over the heads ("mean", "max", "min"); see vit_maps."""
+        from . import vit_maps
+        return vit_maps.attention_rollout(self, x, head_fusion, start_layer, q_rows)[0]
+
 
 def vit_tiny(patch_size=16, **kw):
     return VisionTransformer(patch_size=patch_size, embed_dim=192, depth=12, num_heads=3, mlp_ratio=4, qkv_bias=True,

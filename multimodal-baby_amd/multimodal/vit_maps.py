@@ -1,6 +1,7 @@
 """The DINO ViT's two analysis entry points on libcvcl_hip (reference multimodal/vision_transformer_dino_mugs.py:252-269):
 ``get_last_selfattention`` (the last block's softmax(q k^T scale), written out by csrc/vit_maps.hip) and
-``get_intermediate_layers`` (the final ``norm`` of the token matrix after each of the last ``n`` blocks).
+``get_intermediate_layers`` (the final ``norm`` of the token matrix after each of the last ``n`` blocks); and the attention
+rollout over all blocks (``attention_rollout``; Abnar & Zuidema 2020, not in the reference), which shares the walk.
 
 Both need the token matrix part of the way through the trunk, so this module holds a plain launch sequence of the first ``k``
 blocks in the model's compute dtype (fp32 or bf16): cvcl_im2col_patches, the patch GEMM, cvcl_vit_assemble_tokens, then per block
@@ -67,9 +68,11 @@ class _Trunk:
         H.gemm(self.y, bw["qkv_w"], out=self.qkv, bias=bw["qkv_b"])
         return self.qkv
 
-    def block(self, bw):
+    def block(self, bw, have_qkv=False):
+        """Advance the tokens by block ``bw``; ``have_qkv``: self.qkv already holds qkv_of(bw) of the current tokens."""
         B, T, D, h = self.B, self.T, self.D, self.h
-        self.qkv_of(bw)
+        if not have_qkv:
+            self.qkv_of(bw)
         H.check(self.lib.cvcl_attention(self.cd, H.ptr(self.qkv), None, H.ptr(self.att), B, T, bw["heads"], D // bw["heads"], bw["scale"],
                                         H.stream_ptr()), "cvcl_attention")
         H.gemm(self.att, bw["proj_w"], out=h, bias=bw["proj_b"], residual=h)          # h = h + proj(att)   (vit:146)
@@ -127,6 +130,98 @@ def intermediate_layers(model, x: torch.Tensor, n: int = 1):
             if depth - i <= n:
                 out.append(t.normed())
         return out
+
+
+HEAD_FUSIONS = {"mean": H.FUSE_MEAN, "max": H.FUSE_MAX, "min": H.FUSE_MIN}
+ROLLOUT_SLAB_BYTES = 1 << 30         # budget of the head-fused slab [L - s, B, T, T] fp32; a larger batch is walked in chunks
+ROLLOUT_MAX_T = 960                  # cvcl_attention_rollout's LDS limit
+
+
+def attention_head_fuse(qkv: torch.Tensor, B: int, T: int, heads: int, head_dim: int, scale: float, head_fusion: str = "mean",
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """fuse_h softmax(q k^T scale)[b, h] of a qkv matrix [B T, 3 heads head_dim] (fp32 or bf16) -> [B, T, T] fp32
+    (``head_fusion``: "mean", "max" or "min" over the heads).  The [B, heads, T, T] tensor is never written."""
+    if head_fusion not in HEAD_FUSIONS:
+        raise ValueError(f"head_fusion = {head_fusion!r}: one of {sorted(HEAD_FUSIONS)}")
+    if qkv.numel() != B * T * 3 * heads * head_dim:
+        raise H.CvclError(f"qkv of {qkv.numel()} elements is not [B {B}][T {T}][3][heads {heads}][{head_dim}]")
+    if out is None:
+        out = torch.empty(B, T, T, dtype=torch.float32, device=qkv.device)
+    elif out.shape != (B, T, T) or not out.is_contiguous():
+        raise H.CvclError(f"out {tuple(out.shape)} is not a contiguous [B {B}, T {T}, T {T}]")
+    H.check(H.lib().cvcl_attention_head_fuse(H.cvcl_dtype(qkv.dtype), H.ptr(qkv), H.ptr(out, torch.float32), B, T, heads, head_dim,
+                                             float(scale), HEAD_FUSIONS[head_fusion], H.stream_ptr()), "cvcl_attention_head_fuse")
+    return out
+
+
+def rollout_chain(fused: torch.Tensor, start_layer: int = 0, q_rows: int = 1) -> torch.Tensor:
+    """fused [n, B, T, T] fp32 (block order) -> the first ``q_rows`` rows of A^_{n-1} ... A^_{start_layer}, [B, q_rows, T] fp32,
+    A^_l = (F_l + I) / rowsum(F_l + I)."""
+    if fused.dim() != 4 or fused.shape[2] != fused.shape[3] or fused.dtype != torch.float32 or not fused.is_contiguous():
+        raise H.CvclError(f"fused {tuple(fused.shape)} {fused.dtype} is not a contiguous fp32 [n, B, T, T]")
+    n, B, T, _ = fused.shape
+    if not 0 <= start_layer < n:
+        raise ValueError(f"start_layer = {start_layer} outside 0 .. {n - 1}")
+    if not 1 <= q_rows <= T:
+        raise ValueError(f"q_rows = {q_rows} outside 1 .. T = {T}")
+    out = torch.empty(B, q_rows, T, dtype=torch.float32, device=fused.device)
+    H.check(H.lib().cvcl_attention_rollout(H.ptr(fused, torch.float32), H.ptr(out), n, B, T, start_layer, q_rows, H.stream_ptr()),
+            "cvcl_attention_rollout")
+    return out
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def attention_rollout(model, x: torch.Tensor, head_fusion: str = "mean", start_layer: int = 0, q_rows: int = 1,
+                      slab_bytes: int | None = None):
+    """-> (R [B, q_rows, T] fp32, (gh, gw)): the first ``q_rows`` rows of A^_L ... A^_{s+1}, s = ``start_layer``, where
+    A^_l = (F_l + I) / rowsum(F_l + I) and F_l is block l's softmax(q k^T scale) fused over the heads by ``head_fusion``.  Row 0
+    without column 0 is the CLS token's map over the patch grid.  One walk over the blocks: each block past ``start_layer`` has its
+    qkv fused into a slab [L - s, B, T, T] (cvcl_attention_head_fuse), then one cvcl_attention_rollout launch runs the chain.  A batch
+    whose slab would exceed ``slab_bytes`` (default ROLLOUT_SLAB_BYTES) is walked in chunks of images; an image's rows do not depend
+    on the chunking.  The last block's attention output and MLP are not computed: nothing reads them."""
+    depth = len(model.blocks)
+    if head_fusion not in HEAD_FUSIONS:
+        raise ValueError(f"head_fusion = {head_fusion!r}: one of {sorted(HEAD_FUSIONS)}")
+    if depth < 1:
+        raise H.CvclError("the ViT has no blocks")
+    if not _is_int(start_layer) or not 0 <= start_layer < depth:
+        raise ValueError(f"start_layer = {start_layer!r} outside 0 .. depth - 1 = {depth - 1}")
+    if x.dim() != 4:
+        raise H.CvclError(f"expected NCHW fp32 images, got {tuple(x.shape)} {x.dtype}")
+    p = model.patch_size
+    B, gh, gw = x.shape[0], x.shape[2] // p, x.shape[3] // p
+    T = gh * gw + 1
+    if not _is_int(q_rows) or not 1 <= q_rows <= T:
+        raise ValueError(f"q_rows = {q_rows!r} outside 1 .. T = {T}")
+    if T > ROLLOUT_MAX_T:
+        raise NotImplementedError(f"attention rollout keeps its row tile in LDS: T = {T} > {ROLLOUT_MAX_T} tokens")
+    budget = ROLLOUT_SLAB_BYTES if slab_bytes is None else int(slab_bytes)
+    n = depth - start_layer
+    per_image = n * T * T * 4
+    chunk = max(1, min(B, budget // per_image)) if B else 1
+    with torch.no_grad():
+        if not x.is_cuda:
+            raise H.CvclError("the ViT attention maps need device tensors (got a CPU tensor); there is no CPU fallback")
+        out = torch.empty(B, q_rows, T, dtype=torch.float32, device=x.device) if chunk < B else None
+        for b0 in range(0, B, chunk):
+            t = _Trunk(model, x[b0:b0 + chunk])
+            blocks = t.w["blocks"]
+            slab = torch.empty(n, t.B, T, T, dtype=torch.float32, device=x.device)
+            for i, bw in enumerate(blocks):
+                fused = i >= start_layer
+                if fused:
+                    attention_head_fuse(t.qkv_of(bw), t.B, T, bw["heads"], t.D // bw["heads"], bw["scale"], head_fusion,
+                                        out=slab[i - start_layer])
+                if i + 1 < depth:
+                    t.block(bw, have_qkv=fused)
+            rows = rollout_chain(slab, 0, q_rows)
+            if chunk >= B:
+                return rows, (gh, gw)
+            out[b0:b0 + chunk] = rows
+        return out, (gh, gw)
 
 
 def cls_maps(probs: torch.Tensor, mean: bool) -> torch.Tensor:

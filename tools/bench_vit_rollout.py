@@ -1,0 +1,143 @@
+"""ViT attention rollout at B = 256, 224 x 224, ViT-B/16 and ViT-B/14, bf16 and fp32 (random-init weights):
+  vit_attention_rollout against the eager torch composition on the device (per block softmax(q k^T scale), head mean, + I,
+  normalise, and the bmm chain, on torch's ROCm ops with the same weights; under torch.autocast(bfloat16) for the bf16 rows), and
+  vit_cls_attention as the cost floor of walking the blocks.  Then the two kernels alone on one block's qkv and a 12-layer slab:
+  cvcl_attention_head_fuse (ms, GB/s of the qkv it reads and the F it writes; next to it cvcl_attention_probs at q_rows = T, the
+  [B, heads, T, T] write the fusion replaces) and cvcl_attention_rollout at q_rows = 1 and T (ms, GB/s of the slab it reads).
+The sides of a comparison alternate window by window: warm-up, then ``--repeats`` device-event windows of ``--iters`` calls for each
+side in turn; reported as median [min, max].  Prints one JSON line.
+
+    python tools/bench_vit_rollout.py [--batch 256] [--iters 3] [--repeats 5] [--patches 16,14] [--dtypes bf16,f32] [--kernel-only]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
+
+from multimodal import vision_transformer_dino_mugs as vits          # noqa: E402
+from multimodal import vit_maps                                       # noqa: E402
+from multimodal.attention_maps import vit_attention_rollout, vit_cls_attention               # noqa: E402
+
+
+def _window(fn, iters):
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def timed(fns, iters, repeats):
+    """fns: {name: callable}.  One window per side in turn, ``repeats`` rounds -> {name: {ms (median), min, max}}."""
+    out = {k: [] for k in fns}
+    for _ in range(repeats):
+        for k, fn in fns.items():
+            out[k].append(_window(fn, iters))
+    return {k: {"ms": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)} for k, v in out.items()}
+
+
+def eager_rollout(model, x):
+    """Row 0 of the rollout without its CLS column, [B, T - 1]: the composition on torch ops, the chain carried as the CLS row."""
+    B = x.shape[0]
+    D, heads = model.embed_dim, model.num_heads
+    h = model.patch_embed.proj(x).flatten(2).transpose(1, 2)
+    h = torch.cat([model.cls_token.expand(B, -1, -1).to(h.dtype), h], dim=1) + model.pos_embed
+    T, depth, mats = h.shape[1], len(model.blocks), []
+    eye = torch.eye(T, device=x.device)
+    for i, blk in enumerate(model.blocks):
+        y = blk.norm1(h)
+        qkv = blk.attn.qkv(y).reshape(B, T, 3, heads, D // heads).permute(2, 0, 3, 1, 4)
+        attn = ((qkv[0] @ qkv[1].transpose(-2, -1)) * blk.attn.scale).softmax(dim=-1)
+        A = attn.float().mean(1) + eye
+        mats.append(A / A.sum(-1, keepdim=True))
+        if i == depth - 1:
+            break
+        h = h + blk.attn.proj((attn @ qkv[2]).transpose(1, 2).reshape(B, T, D))
+        h = h + blk.mlp.fc2(F.gelu(blk.mlp.fc1(blk.norm2(h))))
+    r = mats[-1][:, :1]
+    for A in reversed(mats[:-1]):
+        r = torch.bmm(r, A)
+    return r[:, 0, 1:].float()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--patches", type=str, default="16,14")
+    ap.add_argument("--dtypes", type=str, default="bf16,f32")
+    ap.add_argument("--kernel-only", action="store_true", help="time the two kernels alone (the run to put under rocprofv3)")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B = args.batch
+    res = {"batch": B, "iters": args.iters, "repeats": args.repeats, "cases": []}
+    for patch in (int(p) for p in args.patches.split(",")):
+        torch.manual_seed(0)
+        model = vits.vit_base(patch_size=patch, num_classes=0).to(dev).eval()
+        for p in model.parameters():
+            p.requires_grad_(False)
+        x = torch.randn(B, 3, 224, 224, device=dev)
+        T, heads, depth = (224 // patch) ** 2 + 1, model.num_heads, len(model.blocks)
+        for name in args.dtypes.split(","):
+            dt = torch.bfloat16 if name == "bf16" else torch.float32
+            model.compute_dtype = dt
+            case = {"patch": patch, "dtype": name, "T": T}
+            cast = torch.autocast("cuda", dtype=torch.bfloat16, enabled=dt == torch.bfloat16)
+            if not args.kernel_only:
+                def ref():
+                    with torch.no_grad(), cast:
+                        return eager_rollout(model, x)
+                sides = {"vit_attention_rollout": lambda: vit_attention_rollout(model, x), "eager_torch": ref,
+                         "vit_cls_attention": lambda: vit_cls_attention(model, x)}
+                for fn in sides.values():                              # warm-up: packing, allocator, library handles
+                    fn()
+                torch.cuda.empty_cache()
+                case.update(timed(sides, args.iters, args.repeats))
+                case["speedup_vs_eager"] = round(case["eager_torch"]["ms"] / case["vit_attention_rollout"]["ms"], 2)
+                case["rollout_over_cls_floor_ms"] = round(case["vit_attention_rollout"]["ms"] - case["vit_cls_attention"]["ms"], 3)
+                torch.cuda.empty_cache()
+            # the kernels alone: one block's qkv, then a depth-layer slab of row-stochastic matrices
+            qkv = torch.randn(B * T, 3 * model.embed_dim, device=dev).to(dt)
+            fused = torch.empty(B, T, T, dtype=torch.float32, device=dev)
+            sides = {"head_fuse": lambda: vit_maps.attention_head_fuse(qkv, B, T, heads, 64, 0.125, "mean", out=fused),
+                     "attention_probs_q_rows_T": lambda: vit_maps.attention_probs(qkv, B, T, heads, 64, 0.125, T)}
+            for fn in sides.values():
+                fn()
+            t = timed(sides, max(args.iters, 10), args.repeats)
+            for key, nbytes in (("head_fuse", qkv.numel() * qkv.element_size() * 2 // 3 + B * T * T * 4),
+                                ("attention_probs_q_rows_T", qkv.numel() * qkv.element_size() * 2 // 3 + B * heads * T * T * 4)):
+                t[key]["bytes"] = nbytes
+                t[key]["gbs"] = round(nbytes / (t[key]["ms"] * 1e-3) / 1e9, 1)
+                case["kernel_" + key] = t[key]
+            del qkv, fused
+            torch.cuda.empty_cache()
+            slab = torch.randn(depth, B, T, T, device=dev).softmax(-1)
+            sides = {"rollout_q_rows_1": lambda: vit_maps.rollout_chain(slab, 0, 1),
+                     "rollout_q_rows_T": lambda: vit_maps.rollout_chain(slab, 0, T)}
+            for fn in sides.values():
+                fn()
+            t = timed(sides, max(args.iters, 10), args.repeats)
+            for key in sides:
+                t[key]["slab_bytes"] = slab.numel() * 4
+                t[key]["slab_gbs"] = round(slab.numel() * 4 / (t[key]["ms"] * 1e-3) / 1e9, 1)
+                case["kernel_" + key] = t[key]
+            del slab
+            torch.cuda.empty_cache()
+            res["cases"].append(case)
+        del model, x
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
