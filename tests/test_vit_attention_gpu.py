@@ -267,6 +267,26 @@ def test_frozen_forward_untouched(dev, dt):
         m.compute_dtype = torch.float32
 
 
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_intermediate_layers_are_the_plain_forward(dev, dt):
+    """The analysis walk and the forward's plain route (fp32; bf16 with ln_fold False) are one launch sequence, vit_hip._Trunk: the
+    CLS rows of the last layer are forward(x) bit for bit, and so is the last of two layers the only one of one.  No tolerance."""
+    from multimodal import vision_transformer_dino_mugs as vits
+    torch.manual_seed(11)
+    m = vits.VisionTransformer(img_size=[224], patch_size=16, embed_dim=128, depth=2, num_heads=2, mlp_ratio=4, qkv_bias=True,
+                               norm_layer=partial(torch.nn.LayerNorm, eps=1e-6))
+    for p in m.parameters():
+        p.requires_grad_(False)
+        p.add_(0.05 * torch.randn_like(p))                  # biases and LayerNorm parameters off their initial 0 / 1
+    m = m.to(dev).eval()
+    m.compute_dtype, m.ln_fold = dt, False
+    xd = torch.randn(2, 3, 224, 224).to(dev)
+    last = m.get_intermediate_layers(xd, 1)[0]
+    assert last.shape == (2, 197, 128) and last.dtype == torch.float32
+    assert torch.equal(last[:, 0], m(xd))
+    assert torch.equal(m.get_intermediate_layers(xd, 2)[-1], last)
+
+
 def _patched_vit():
     from multimodal import vision_transformer_dino_mugs as vits
     return lambda name, pretrained: vits.VisionTransformer(img_size=[224], patch_size=16, embed_dim=768, depth=2, num_heads=12, mlp_ratio=4,
