@@ -94,6 +94,17 @@ static inline int cvcl_storage_dtype(int d) { return d == CVCL_F32X3 ? CVCL_F32 
 #define CVCL_CHECK_DTYPE(d, fn) CVCL_CHECK_ARG(cvcl_dtype_plain(d), "%s: dtype %d is not accepted here (CVCL_F32 / CVCL_BF16)", fn, (int)(d))
 #define CVCL_CHECK_DTYPE_TRUNK(d, fn) CVCL_CHECK_ARG(cvcl_dtype_trunk(d), "%s: unknown dtype %d", fn, (int)(d))
 
+// ---- between the GEMM dispatcher (csrc/gemm.hip plan_gemm) and the kernels it routes to; the public entries are in cvcl_hip.h ----
+// a statistics buffer that came with the block holds the `rows` partial rows a kernel writes (an accumulator takes any number)
+static inline bool cvcl_stats_rows_fit(const cvcl_gemm_args* a, int rows) {
+    return !a->stats || a->stats_rows == CVCL_STATS_ACCUMULATE || a->stats_rows >= rows;
+}
+// csrc/gemm8w.hip: why the 8-wave kernel does not take epilogue `epi` of this block, or NULL.  direct: asked by cvcl_gemm8w itself (all
+// of its checks, with the text for cvcl_last_error), not by the dispatcher (DESIGN.md "GEMM routing" lists what only the entry checks)
+const char* cvcl_gemm8w_refusal(int epi, const cvcl_gemm_args* a, bool direct);
+// csrc/gemm_pro.hip: cvcl_gemm_pro_supported with "statistics are asked for" given by the caller instead of read from a->stats
+bool cvcl_gemm_pro_takes(const cvcl_gemm_args* a, bool stats);
+
 // CVCL_F32X3 products (csrc/gemm_split.hip): split terms per product (3: hi/lo x hi/lo without lo.lo; 6: three-way split of both
 // operands) and the bf16 parts per operand that go with them.  6: the 3-term form measured ~7e-4 relative on the pooled trunk output
 // at the noise point, too close to the 1e-3 gate (DESIGN.md "32-split").  The kernels are templates on the term count; both forms

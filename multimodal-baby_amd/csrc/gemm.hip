@@ -25,6 +25,7 @@
 //  * the epilogue goes through LDS so that C is written as full 128-byte row segments (16 B per lane).
 //  * the BatchNorm(+ReLU) of the *producer* layer is applied to A while it is staged (per-K scale /
 //    shift), so a normalised activation tensor is never written to HBM.
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -874,17 +875,20 @@ int grid_m_for(int M, int N, int capacity) {
     return best;
 }
 
-template <typename T> int grid_m_query(int M, int N);
+// every variant of one dtype is compiled for the same occupancy target, so one query stands for all of them
+template <typename T>
+int grid_m_query(int M, int N) {
+    return grid_m_for(M, N, resident_per_cu<T, 0, true>() * num_cus());
+}
 
+// gm = grid_m_query<T>: the persistent grid's rows, one BN-statistics row each (plan_gemm has checked the caller's buffer against it)
 template <typename T, int PRO, bool LEAN, int TR = 0>
-int launch_gemm_v(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
-    const int gm = grid_m_query<T>(a->M, a->N);      // same capacity for every variant (see grid_m_query)
-    if (a->stats) CVCL_CHECK_ARG(a->stats_rows == CVCL_STATS_ACCUMULATE || a->stats_rows >= gm, "cvcl_gemm: stats_rows %d < grid_m %d", a->stats_rows, gm);
+int launch_gemm_v(const GemmDev& d, int gm, hipStream_t stream) {
     static CvclLdsAttr attr_set;
     constexpr int lds = gemm_lds_bytes<T>();
     if (const int rc = cvcl_raise_lds_limit(attr_set, (const void*)gemm_kernel<T, PRO, LEAN, TR>, lds, "cvcl_gemm")) return rc;
     attr_set.mark();
-    dim3 grid(gm, cvcl_div_up(a->N, BN));
+    dim3 grid(gm, cvcl_div_up(d.N, BN));
     CvclProfScope prof(stream, sizeof(T) == 2 ? CVCL_K_GEMM : CVCL_K_GEMM_F32);
     hipLaunchKernelGGL((gemm_kernel<T, PRO, LEAN, TR>), grid, dim3(256), lds, stream, d);
     CVCL_LAUNCH_CHECK();
@@ -1130,73 +1134,189 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const float* __r
     }
 }
 
-}  // namespace
-extern "C" int cvcl_gemm_pro(const cvcl_gemm_args* a, void* stream);
-extern "C" int cvcl_gemm_pro_supported(const cvcl_gemm_args* a);
-extern "C" int cvcl_gemm_pro_stats_rows(int M, int N);
-extern "C" int cvcl_gemm8w(int epi, const cvcl_gemm_args* a, void* stream);
-extern "C" int cvcl_gemm8w_supported(int M, int N, int K, int lda, int ldw, int ldc);
-extern "C" int cvcl_gemm8w_stats_rows(int M, int N);
-namespace {
+// ---- Routing: which kernel takes an argument block -----------------------------------------------------------------------------
+// plan_gemm decides it once, for the launch (cvcl_gemm) and for the two probes (cvcl_gemm_stats_rows, cvcl_gemm_ln_supported).
+// DESIGN.md "GEMM routing" has the table of routes and conditions.
+enum GemmRoute {
+    ROUTE_PRO,           // gemm_pro.hip: the streaming kernel
+    ROUTE_8W,            // gemm8w.hip, epi 0 (convolution) | 1 (linear)
+    ROUTE_GLDS,          // gemm_glds_kernel<epi>, epi 0-6
+    ROUTE_F32_SMALL,     // gemm_f32_small_kernel<tr>
+    ROUTE_F32_SPLIT64,   // gemm_f32_split_kernel<tr>
+    ROUTE_TILED,         // gemm_kernel<T, pro, lean, tr>
+    ROUTE_SPLIT3         // gemm_split.hip (CVCL_F32X3)
+};
 
-// Policy for the 8-wave 256 (224) x 256 kernel (gemm8w.hip): the MFMA-bound shapes -- K >= 256, N a multiple of 256, enough
-// 256-row tiles to occupy the chip at one workgroup per CU, plain operands (no BN prologue, no output
-// scale, no Bottleneck-tail / GELU-backward epilogue) -- and, when BN statistics are requested, a statistics buffer sized by
-// cvcl_gemm_stats_rows.  Measured on MI355X (tools/gemm_lab, profiles/r02_gemm_lab.txt): ResNeXt layer-3/4 1x1 convolutions
-// and ViT-B linears 10-25 % faster than the 128 x 128 kernel below; $CVCL_GEMM8W=0 switches it off.
-// Returns -1 (not selected) or the epilogue id.
-inline int pick_gemm8w(int dtype, const cvcl_gemm_args* a) {
-    static const bool on = cvcl_env_on("CVCL_GEMM8W");
-    if (!on || dtype != CVCL_BF16) return -1;
-    if (!cvcl_gemm8w_supported(a->M, a->N, a->K, a->lda, a->ldw, a->ldc) || a->K < 256) return -1;
-    if (a->a_scale || a->exp_scale || a->c_scale || a->C_pre || a->G) return -1;
-    if (a->ln_stats && (a->R || !a->ln_colsum || !a->bias || a->row_part)) return -1;
-    if (a->row_part && (!a->R || a->act != CVCL_ACT_NONE)) return -1;
-    if (!cvcl_aligned16(a->A) || !cvcl_aligned16(a->W) || !cvcl_aligned16(a->C) || !cvcl_aligned16(a->R) || !cvcl_aligned16(a->bias) || (a->R && a->ldr % 8)) return -1;
-    long a_rows = a->M;
-    if (a->gather_stride > 1) {                              // strided 1x1 convolution (the downsample branch of blocks 2.0 / 3.0 / 4.0)
-        if (a->gather_ho <= 0 || a->gather_wo <= 0 || a->M % (a->gather_ho * a->gather_wo)) return -1;
-        a_rows = (long)(a->M / (a->gather_ho * a->gather_wo)) * a->gather_hi * a->gather_wi;
+struct GemmPlan {
+    GemmRoute route = ROUTE_TILED;
+    bool bf16 = false;
+    int epi = 0, pro = 0, tr = 0;    // the route's template arguments (see GemmRoute)
+    bool lean = false, vec_in = false, vec_out = false;
+    int stats_rows = 0;  // BN-statistics rows the route writes (= grid rows of ROUTE_GLDS / ROUTE_TILED); 0: the route takes none
+    int rc = CVCL_OK;    // != CVCL_OK: cvcl_gemm refuses the block with msg (written only then)
+    char msg[256];
+};
+
+#define PLAN_REQUIRE(cond, ...)                              \
+    do {                                                     \
+        if (!(cond)) {                                       \
+            p.rc = CVCL_EINVAL;                              \
+            snprintf(p.msg, sizeof(p.msg), __VA_ARGS__);     \
+            return p;                                        \
+        }                                                    \
+    } while (0)
+
+// Step 3 of plan_gemm: which kernel of this file takes a block that cvcl_gemm's own checks have passed and that neither the
+// streaming nor the 8-wave kernel took -- or why none does.  Sets route, epi / pro / lean / tr and the vector flags.
+GemmPlan& plan_own_kernel(GemmPlan& p, const cvcl_gemm_args* a) {
+    const bool bf16 = p.bf16, stats = a->stats != nullptr, gather = a->gather_stride > 1, split = a->f32_split != 0;
+    auto to = [&p](GemmRoute route, int epi) -> GemmPlan& { p.route = route; p.epi = epi; return p; };
+    const int epc = bf16 ? ElemTraits<bf16_t>::kPerChunk : ElemTraits<float>::kPerChunk;
+    p.vec_in = (a->K % epc == 0) && (a->lda % epc == 0) && (a->ldw % epc == 0) && cvcl_aligned16(a->A) && cvcl_aligned16(a->W);
+    p.vec_out = (a->ldc % epc == 0) && cvcl_aligned16(a->C) && (!a->R || ((a->ldr % epc == 0) && cvcl_aligned16(a->R)));
+    p.pro = !a->a_scale ? 0 : (a->a_relu ? 2 : 1);
+    p.lean = p.vec_in && p.vec_out && !a->bias && !a->exp_scale && !a->R && !a->G && !a->C_pre && a->act == CVCL_ACT_NONE && (a->N % BN) == 0;
+    if (bf16) {
+        const bool glds_in = p.vec_in && p.vec_out && p.pro == 0 && a->K % 64 == 0;
+        if (a->c_scale) {                // Bottleneck tail epilogue: only the direct-to-LDS kernel implements it
+            PLAN_REQUIRE(glds_in && a->N % BN == 0 && a->R && a->c_shift && !a->bias && !a->exp_scale && !stats &&
+                             (a->r_scale == nullptr) == (a->r_shift == nullptr),
+                         "cvcl_gemm: the c_scale epilogue needs bf16, K %% 64 == 0, N %% 128 == 0, a residual and no bias/stats");
+            return to(ROUTE_GLDS, 2);
+        }
+        if (p.lean && p.pro == 0 && a->K % 64 == 0) return to(ROUTE_GLDS, 0);
+        // ViT / nn.Linear shapes: bias, activation, residual, no statistics
+        const bool lin_ok = glds_in && a->N % BN == 0 && !a->exp_scale && !stats && cvcl_aligned16(a->bias) && !gather;
+        if (a->C_pre || a->G) {                          // training epilogues: only this kernel implements them
+            PLAN_REQUIRE(lin_ok, "cvcl_gemm: the C_pre / G epilogues need bf16, K %% 64 == 0, N %% 128 == 0 and 16-byte aligned rows");
+            if (a->C_pre) {
+                PLAN_REQUIRE(a->act == CVCL_ACT_GELU && !a->R && !a->G && cvcl_aligned16(a->C_pre), "cvcl_gemm: C_pre goes with act = GELU and no residual");
+                return to(ROUTE_GLDS, 5);
+            }
+            PLAN_REQUIRE(a->act == CVCL_ACT_NONE && !a->R && !a->bias && a->ldg % 8 == 0 && cvcl_aligned16(a->G),
+                         "cvcl_gemm: G (GELU-backward epilogue) takes no bias / activation / residual");
+            return to(ROUTE_GLDS, 6);
+        }
+        if (lin_ok) return to(ROUTE_GLDS, a->act == CVCL_ACT_GELU ? 4 : a->act == CVCL_ACT_RELU ? 3 : 1);
     }
-    if (a_rows * a->lda >= (1L << 31) || (long)a->N * a->ldw >= (1L << 31)) return -1;
-    if ((long)cvcl_div_up(a->M, 256) * (a->N / 256) < 96) return -1;
-    // bandwidth-bound shapes stay with the 128 x 128 kernel (two workgroups per CU keep more bytes in flight): layer-2 block-0
-    // conv1, M 802816 x N 256 x K 256, measured 176 us there vs 191-197 us here; N K / (N + K) = flop per byte of A + C traffic
-    if ((long)a->N * a->K < 170L * (a->N + a->K)) return -1;
+    PLAN_REQUIRE(a->C && !a->c_scale, "cvcl_gemm: statistics-only / BN-tail epilogues need the direct-to-LDS bf16 path");
+    if (!bf16) {
+        // measured cost models (us, MI355X): the split-K VALU kernel runs ~13.4 GMAC/s-per-us of work on any shape; the 128-tile
+        // fp32 MFMA kernel needs ~4.6 us per 64-deep K step per round of <= 256 tiles, whatever M and N are (4.2 with split
+        // arithmetic: its K step is bound by the serial load -> LDS -> multiply structure at one wave per SIMD, not by the matrix
+        // pipe); the 64 x 64 split kernel ~1 us per (tile, 32-deep K step) with ~4 workgroups per CU overlapping
+        const bool bare = p.pro == 0 && !gather && !stats && !a->R && !a->centre;
+        const bool split64_ok = split && bare && !a->exp_scale && (a->act == CVCL_ACT_NONE || a->act == CVCL_ACT_RELU);
+        const double t_small = (double)a->M * a->N * a->K / 13.4e6 + 5.0;
+        const double t_mfma128 = 12.0 + (a->K / 64.0) * (split ? 4.2 : 4.6) * cvcl_div_up((long)cvcl_div_up(a->M, BM) * cvcl_div_up(a->N, BN), 256);
+        const double t_split64 = split64_ok ? 6.0 + (double)cvcl_div_up(a->M, TS) * cvcl_div_up(a->N, TS) * cvcl_div_up(a->K, 32) / 1024.0 +
+                                              0.25 * cvcl_div_up(a->K, 32) : 1e30;
+        if (bare && a->act == CVCL_ACT_NONE && a->K % 4 == 0 && a->lda % 4 == 0 && a->ldw % 4 == 0 && cvcl_aligned16(a->A) && cvcl_aligned16(a->W) &&
+            !a->a_rowsum && t_small < t_mfma128 && t_small < t_split64)
+            return to(ROUTE_F32_SMALL, 0);
+        if (split64_ok && t_split64 < t_mfma128) return to(ROUTE_F32_SPLIT64, 0);      // the tail's products: many 64 x 64 workgroups
+        if (p.tr || split) {
+            PLAN_REQUIRE(p.pro == 0, "cvcl_gemm: K-major operands take no prologue");
+            p.tr |= split ? 4 : 0;                       // gemm_kernel<float, 0, false, TR>: TR 1-7
+            p.lean = false;
+        }
+    }
+    return to(ROUTE_TILED, 0);
+}
+
+// assume_stats: answer as if a statistics buffer of sufficient size came with the block.  That is cvcl_gemm_stats_rows' question;
+// it has never validated a block, so it is answered from step 1 alone.
+// No side effect beyond the cached CU-count / occupancy queries and the two environment switches read once.
+GemmPlan plan_gemm(int dtype, const cvcl_gemm_args* a, bool assume_stats) {
+    static const bool g8_on = cvcl_env_on("CVCL_GEMM8W"), pro_on = cvcl_env_on("CVCL_GEMM_PRO");
+    GemmPlan p;
+    p.bf16 = dtype == CVCL_BF16;
+    const bool bf16 = p.bf16, stats = assume_stats || a->stats, shape_ok = a->M > 0 && a->N > 0 && a->K > 0;
     const bool plain = !a->bias && !a->R && a->act == CVCL_ACT_NONE;
-    if (a->stats) {
-        if (!plain || (a->stats_rows != CVCL_STATS_ACCUMULATE && a->stats_rows < cvcl_gemm8w_stats_rows(a->M, a->N))) return -1;
-        return 0;
+    // THE statistics-rows check: the buffer that came with the block holds the rows a route writes
+    auto rows_fit = [&](int rows) { return assume_stats || cvcl_stats_rows_fit(a, rows); };
+    auto grid_rows = [&] { return bf16 ? grid_m_query<bf16_t>(a->M, a->N) : grid_m_query<float>(a->M, a->N); };
+
+    // ---- 1. the kernels of the other files, chosen on the block alone (each kernel's own "can I take this" plus policy).
+    //         A block without a positive shape selects neither kernel, and no row count is computed from a non-positive M or N:
+    //         step 2 refuses it, cvcl_gemm_ln_supported says no, cvcl_gemm_stats_rows answers 0.
+    if (dtype == CVCL_F32X3) {
+        p.route = ROUTE_SPLIT3;
+        p.stats_rows = cvcl_gemm_split_stats_rows(a->M, a->N);
+    } else if (shape_ok && bf16) {
+        // Streaming kernel (gemm_pro.hip): conv3 of ResNeXt layers 1-2, the producer's BN + ReLU on its input.  A plain operand takes
+        // it only where it is a byte stream: M >= 2^17 rows of K <= 256 (conv1 of layer2.0 at B >= 64); smaller products stay on
+        // the tiled kernels.  $CVCL_GEMM_PRO=0 refuses it (callers then have to normalise the operand themselves).
+        if (pro_on && cvcl_gemm_pro_takes(a, stats) && (a->a_scale || a->M >= (1 << 17))) {
+            const int rows = cvcl_gemm_pro_stats_rows(a->M, a->N);
+            if (rows_fit(rows)) { p.route = ROUTE_PRO; p.stats_rows = rows; }
+        }
+        // 8-wave 256 (224) x 256 kernel (gemm8w.hip): the MFMA-bound shapes -- K >= 256, enough 256-row tiles to occupy the chip at
+        // one workgroup per CU -- with statistics on the convolution epilogue only.  Measured on MI355X (tools/gemm_lab,
+        // profiles/r02_gemm_lab.txt): ResNeXt layer-3/4 1x1 convolutions and ViT-B linears 10-25 % faster than the 128 x 128
+        // kernels; $CVCL_GEMM8W=0 switches it off.  Bandwidth-bound shapes stay with the 128 x 128 kernel (two workgroups per CU
+        // keep more bytes in flight): layer-2 block-0 conv1, M 802816 x N 256 x K 256, measured 176 us there vs 191-197 us here;
+        // N K / (N + K) = flop per byte of A + C traffic.
+        if (p.route != ROUTE_PRO && g8_on && a->K >= 256 && (plain || !stats) && !cvcl_gemm8w_refusal(plain ? 0 : 1, a, false) &&
+            (long)cvcl_div_up(a->M, 256) * (a->N / 256) >= 96 && (long)a->N * a->K >= 170L * (a->N + a->K)) {
+            const int rows = plain ? cvcl_gemm8w_stats_rows(a->M, a->N) : 0;
+            if (rows_fit(rows)) { p.route = ROUTE_8W; p.epi = plain ? 0 : 1; p.stats_rows = rows; }
+        }
+        // (a buffer too small for either kernel's rows is no refusal: the block goes on to the kernels of this file)
     }
-    if (plain) return 0;
-    if (!a->C || (a->R && a->act != CVCL_ACT_NONE)) return -1;     // (activation + residual together: the 128 x 128 kernel)
-    return 1;
-}
+    if (assume_stats) {
+        if (p.route == ROUTE_TILED && a->M > 0 && a->N > 0) p.stats_rows = grid_rows();     // (= cvcl_gemm_grid_m, which has no K)
+        return p;
+    }
 
-// Bandwidth-bound 1x1 convolution with the producer's BN + ReLU on its input (gemm_pro.hip): conv3 of ResNeXt layers 1-2.
-// $CVCL_GEMM_PRO=0 refuses it (callers then have to normalise the operand themselves).
-inline bool pick_gemm_pro(int dtype, const cvcl_gemm_args* a) {
-    static const bool on = cvcl_env_on("CVCL_GEMM_PRO");
-    if (!on || dtype != CVCL_BF16 || !cvcl_gemm_pro_supported(a)) return false;
-    // a plain operand takes this kernel only where it is a byte stream: M >= 2^17 rows of K <= 256 (conv1 of layer2.0 at B >= 64);
-    // smaller products stay on the tiled kernels
-    if (!a->a_scale && a->M < (1 << 17)) return false;
-    return !a->stats || a->stats_rows == CVCL_STATS_ACCUMULATE || a->stats_rows >= cvcl_gemm_pro_stats_rows(a->M, a->N);
-}
+    // ---- 2. what cvcl_gemm refuses whatever the route ----
+    if ((a->ln_stats || a->ln_colsum || a->row_part) && !(p.route == ROUTE_8W && p.epi == 1)) {
+        p.rc = CVCL_EUNSUPPORTED;
+        snprintf(p.msg, sizeof(p.msg), "cvcl_gemm: ln_stats / row_part (LayerNorm folded into the linear) exist in the 8-wave bf16 kernel only; these "
+                 "arguments do not select it (M %d N %d K %d) -- ask cvcl_gemm_ln_supported first", a->M, a->N, a->K);
+        return p;
+    }
+    PLAN_REQUIRE(!a->c_scale || bf16, "cvcl_gemm: the c_scale epilogue exists for bf16 only");
+    PLAN_REQUIRE(shape_ok, "cvcl_gemm: bad shape %d %d %d", a->M, a->N, a->K);
+    PLAN_REQUIRE((a->a_scale == nullptr) == (a->a_shift == nullptr), "cvcl_gemm: a_scale/a_shift must come together");
+    // centred storage belongs to the convolution epilogues (plain / statistics / Bottleneck tail); nn.Linear epilogues have no BN behind them
+    PLAN_REQUIRE(!a->centre || (cvcl_aligned16(a->centre) && !a->bias && !a->exp_scale && !a->C_pre && !a->G &&
+                                (a->c_scale || (!a->R && a->act == CVCL_ACT_NONE))),
+                 "cvcl_gemm: centre goes with the convolution epilogues only (16-byte aligned, no bias / activation / residual)");
+    if (p.route == ROUTE_SPLIT3) return p;
+    p.tr = (a->a_trans ? 1 : 0) | (a->w_trans ? 2 : 0);
+    if (p.tr || a->a_rowsum || a->f32_split) {
+        // K-major operands / fused row sums: the fp32 gradient GEMMs of the trainable tail (no prologue, gather, statistics or BN tail)
+        PLAN_REQUIRE(dtype == CVCL_F32, "cvcl_gemm: a_trans / w_trans / a_rowsum / f32_split are fp32 options");
+        PLAN_REQUIRE(!a->a_rowsum || a->a_trans, "cvcl_gemm: a_rowsum goes with a_trans (the bias gradient beside dW = dY^T X)");
+        PLAN_REQUIRE(!a->a_scale && !(a->gather_stride > 1) && !stats && !a->centre && !a->c_scale && !a->C_pre && !a->G && a->C,
+                     "cvcl_gemm: K-major operands / split arithmetic take no prologue / gather / statistics / BN-tail options");
+    }
+    if (p.route != ROUTE_TILED) return p;
 
-inline bool is_lean(const cvcl_gemm_args* a, const GemmDev& d) {
-    return d.vec_in && d.vec_out && !a->bias && !a->exp_scale && !a->R && !a->G && !a->C_pre && a->act == CVCL_ACT_NONE && (a->N % BN) == 0;
+    // ---- 3. the kernels of this file; the two persistent ones write one statistics row per grid row ----
+    if (plan_own_kernel(p, a).rc != CVCL_OK) return p;
+    if (p.route == ROUTE_GLDS || p.route == ROUTE_TILED) {
+        p.stats_rows = grid_rows();
+        PLAN_REQUIRE(rows_fit(p.stats_rows), "cvcl_gemm: stats_rows %d < grid_m %d", a->stats_rows, p.stats_rows);
+    }
+    return p;
 }
-inline int pro_kind(const cvcl_gemm_args* a) { return !a->a_scale ? 0 : (a->a_relu ? 2 : 1); }
+#undef PLAN_REQUIRE
+
+// f(std::integral_constant<int, i>) for the run-time i in [0, N): the one place a run-time choice becomes a template argument
+template <int N, typename F>
+int with_const(int i, F&& f) {
+    if constexpr (N == 1) return f(std::integral_constant<int, 0>{});
+    else return i >= N - 1 ? f(std::integral_constant<int, N - 1>{}) : with_const<N - 1>(i, f);
+}
 
 template <int EPI>
-int launch_gemm_glds(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
-    const int gm = grid_m_query<bf16_t>(a->M, a->N);
-    if (a->stats) CVCL_CHECK_ARG(a->stats_rows == CVCL_STATS_ACCUMULATE || a->stats_rows >= gm, "cvcl_gemm: stats_rows %d < grid_m %d", a->stats_rows, gm);
+int launch_gemm_glds(const GemmDev& d, int gm, hipStream_t stream) {
     static CvclLdsAttr attr_set;
     if (const int rc = cvcl_raise_lds_limit(attr_set, (const void*)gemm_glds_kernel<EPI>, GL_LDS, "cvcl_gemm")) return rc;
     attr_set.mark();
-    dim3 grid(gm, a->N / BN);
+    dim3 grid(gm, d.N / BN);
     CvclProfScope prof(stream, CVCL_K_GEMM);
     hipLaunchKernelGGL(gemm_glds_kernel<EPI>, grid, dim3(256), GL_LDS, stream, d);
     CVCL_LAUNCH_CHECK();
@@ -1204,8 +1324,48 @@ int launch_gemm_glds(const cvcl_gemm_args* a, GemmDev& d, hipStream_t stream) {
 }
 
 template <typename T>
-int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
-    constexpr int EPC = ElemTraits<T>::kPerChunk;
+int launch_gemm_tiled(const GemmPlan& p, const GemmDev& d, hipStream_t stream) {
+    if constexpr (sizeof(T) == 4) {
+        if (p.tr) return with_const<8>(p.tr, [&](auto TR) { return launch_gemm_v<float, 0, false, decltype(TR)::value>(d, p.stats_rows, stream); });
+    }
+    return with_const<3>(p.pro, [&](auto PRO) {
+        return p.lean ? launch_gemm_v<T, decltype(PRO)::value, true>(d, p.stats_rows, stream)
+                      : launch_gemm_v<T, decltype(PRO)::value, false>(d, p.stats_rows, stream);
+    });
+}
+
+int launch_gemm(const GemmPlan& p, const cvcl_gemm_args* a, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const float* A = (const float*)a->A; const float* W = (const float*)a->W; float* C = (float*)a->C;
+    switch (p.route) {
+        case ROUTE_SPLIT3: return cvcl_gemm_split(a, stream_);
+        case ROUTE_PRO: return cvcl_gemm_pro(a, stream_);
+        case ROUTE_8W: return cvcl_gemm8w(p.epi, a, stream_);
+        case ROUTE_F32_SMALL: {
+            CvclProfScope prof(stream, CVCL_K_GEMM_F32);
+            const dim3 grid(cvcl_div_up(a->N, 16), cvcl_div_up(a->M, 16));
+            with_const<4>(p.tr, [&](auto TR) {
+                hipLaunchKernelGGL(gemm_f32_small_kernel<decltype(TR)::value>, grid, dim3(256), 0, stream, A, W, C, a->M, a->N, a->K, a->lda, a->ldw,
+                                   a->ldc, a->exp_scale, a->bias);
+                return 0;
+            });
+            CVCL_LAUNCH_CHECK();
+            return CVCL_OK;
+        }
+        case ROUTE_F32_SPLIT64: {
+            const int vec = (a->lda % 4 == 0) && (a->ldw % 4 == 0) && cvcl_aligned16(a->A) && cvcl_aligned16(a->W) && cvcl_aligned16(a->C);
+            CvclProfScope prof(stream, CVCL_K_GEMM_F32);
+            const dim3 grid(cvcl_div_up(a->M, TS), cvcl_div_up(a->N, TS));
+            with_const<4>(p.tr, [&](auto TR) {
+                hipLaunchKernelGGL(gemm_f32_split_kernel<decltype(TR)::value>, grid, dim3(256), 0, stream, A, W, C, a->M, a->N, a->K, a->lda, a->ldw,
+                                   a->ldc, a->bias, a->act, a->a_rowsum, vec);
+                return 0;
+            });
+            CVCL_LAUNCH_CHECK();
+            return CVCL_OK;
+        }
+        default: break;
+    }
     GemmDev d;
     d.A = a->A; d.W = a->W; d.C = a->C;
     d.M = a->M; d.N = a->N; d.K = a->K; d.lda = a->lda; d.ldw = a->ldw; d.ldc = a->ldc;
@@ -1216,112 +1376,14 @@ int launch_gemm(const cvcl_gemm_args* a, hipStream_t stream) {
     d.R = a->R; d.ldr = a->ldr; d.stats = a->stats; d.centre = a->centre;
     d.stats_acc = a->stats && a->stats_rows == CVCL_STATS_ACCUMULATE;
     d.c_scale = a->c_scale; d.c_shift = a->c_shift; d.r_scale = a->r_scale; d.r_shift = a->r_shift;
-    d.vec_in = (a->K % EPC == 0) && (a->lda % EPC == 0) && (a->ldw % EPC == 0) && cvcl_aligned16(a->A) && cvcl_aligned16(a->W);
-    d.vec_out = (a->ldc % EPC == 0) && cvcl_aligned16(a->C) && (!a->R || ((a->ldr % EPC == 0) && cvcl_aligned16(a->R)));
+    d.vec_in = p.vec_in; d.vec_out = p.vec_out;
     d.num_m_tiles = cvcl_div_up(a->M, BM);
-    d.C2 = nullptr;
+    d.C2 = p.epi == 5 ? a->C_pre : nullptr;                  // (epi is 0 on ROUTE_TILED)
     d.a_rowsum = a->a_rowsum;
-    const int tr = (a->a_trans ? 1 : 0) | (a->w_trans ? 2 : 0);
-    const bool split = a->f32_split != 0;
-    if (tr || a->a_rowsum || split) {
-        // K-major operands / fused row sums: the fp32 gradient GEMMs of the trainable tail (no prologue, gather, statistics or BN tail)
-        CVCL_CHECK_ARG(sizeof(T) == 4, "cvcl_gemm: a_trans / w_trans / a_rowsum / f32_split are fp32 options");
-        CVCL_CHECK_ARG(!a->a_rowsum || a->a_trans, "cvcl_gemm: a_rowsum goes with a_trans (the bias gradient beside dW = dY^T X)");
-        CVCL_CHECK_ARG(!a->a_scale && !(a->gather_stride > 1) && !a->stats && !a->centre && !a->c_scale && !a->C_pre && !a->G && a->C,
-                       "cvcl_gemm: K-major operands / split arithmetic take no prologue / gather / statistics / BN-tail options");
-    }
-    const bool lean = is_lean(a, d);
-    if constexpr (sizeof(T) == 2) {
-        if (pick_gemm_pro(CVCL_BF16, a)) return cvcl_gemm_pro(a, stream);
-        const int e8 = pick_gemm8w(CVCL_BF16, a);
-        if (e8 >= 0) return cvcl_gemm8w(e8, a, stream);
-        if (a->c_scale) {                // Bottleneck tail epilogue: only the direct-to-LDS kernel implements it
-            CVCL_CHECK_ARG(d.vec_in && d.vec_out && pro_kind(a) == 0 && a->K % 64 == 0 && a->N % BN == 0 && a->R && a->c_shift &&
-                               !a->bias && !a->exp_scale && !a->stats && (a->r_scale == nullptr) == (a->r_shift == nullptr),
-                           "cvcl_gemm: the c_scale epilogue needs bf16, K %% 64 == 0, N %% 128 == 0, a residual and no bias/stats");
-            return launch_gemm_glds<2>(a, d, stream);
-        }
-        if (lean && pro_kind(a) == 0 && a->K % 64 == 0) return launch_gemm_glds<0>(a, d, stream);
-        // ViT / nn.Linear shapes: bias, activation, residual, no statistics
-        const bool al = ((uintptr_t)a->bias & 15) == 0;
-        const bool lin_ok = d.vec_in && d.vec_out && pro_kind(a) == 0 && a->K % 64 == 0 && a->N % BN == 0 && !a->exp_scale &&
-                            !a->stats && al && !(a->gather_stride > 1);
-        if (a->C_pre || a->G) {                          // training epilogues: only this kernel implements them
-            CVCL_CHECK_ARG(lin_ok, "cvcl_gemm: the C_pre / G epilogues need bf16, K %% 64 == 0, N %% 128 == 0 and 16-byte aligned rows");
-            if (a->C_pre) {
-                CVCL_CHECK_ARG(a->act == CVCL_ACT_GELU && !a->R && !a->G && ((uintptr_t)a->C_pre & 15) == 0,
-                               "cvcl_gemm: C_pre goes with act = GELU and no residual");
-                d.C2 = a->C_pre;
-                return launch_gemm_glds<5>(a, d, stream);
-            }
-            CVCL_CHECK_ARG(a->act == CVCL_ACT_NONE && !a->R && !a->bias && a->ldg % 8 == 0 && ((uintptr_t)a->G & 15) == 0,
-                           "cvcl_gemm: G (GELU-backward epilogue) takes no bias / activation / residual");
-            d.R = a->G; d.ldr = a->ldg;
-            return launch_gemm_glds<6>(a, d, stream);
-        }
-        if (lin_ok)
-            return a->act == CVCL_ACT_GELU ? launch_gemm_glds<4>(a, d, stream)
-                 : a->act == CVCL_ACT_RELU ? launch_gemm_glds<3>(a, d, stream) : launch_gemm_glds<1>(a, d, stream);
-    }
-    CVCL_CHECK_ARG(a->C && !a->c_scale, "cvcl_gemm: statistics-only / BN-tail epilogues need the direct-to-LDS bf16 path");
-    if constexpr (sizeof(T) == 4) {
-        // measured cost models (us, MI355X): the split-K VALU kernel runs ~13.4 GMAC/s-per-us of work on any shape; the 128-tile
-        // fp32 MFMA kernel needs ~4.6 us per 64-deep K step per round of <= 256 tiles, whatever M and N are (4.2 with split
-        // arithmetic: its K step is bound by the serial load -> LDS -> multiply structure at one wave per SIMD, not by the matrix
-        // pipe); the 64 x 64 split kernel ~1 us per (tile, 32-deep K step) with ~4 workgroups per CU overlapping
-        const bool split64_ok = split && pro_kind(a) == 0 && !(a->gather_stride > 1) && !a->stats && !a->R && !a->centre && !a->exp_scale &&
-                                (a->act == CVCL_ACT_NONE || a->act == CVCL_ACT_RELU);
-        const double t_small = (double)a->M * a->N * a->K / 13.4e6 + 5.0;
-        const double t_mfma128 = 12.0 + (a->K / 64.0) * (split ? 4.2 : 4.6) * cvcl_div_up((long)cvcl_div_up(a->M, BM) * cvcl_div_up(a->N, BN), 256);
-        const double t_split64 = split64_ok ? 6.0 + (double)cvcl_div_up(a->M, TS) * cvcl_div_up(a->N, TS) * cvcl_div_up(a->K, 32) / 1024.0 +
-                                              0.25 * cvcl_div_up(a->K, 32) : 1e30;
-        if (pro_kind(a) == 0 && !(a->gather_stride > 1) && !a->stats && !a->R && !a->centre && a->act == CVCL_ACT_NONE && a->K % 4 == 0 &&
-            a->lda % 4 == 0 && a->ldw % 4 == 0 && cvcl_aligned16(a->A) && cvcl_aligned16(a->W) && !a->a_rowsum && t_small < t_mfma128 && t_small < t_split64) {
-            CvclProfScope prof(stream, CVCL_K_GEMM_F32);
-            const dim3 grid(cvcl_div_up(a->N, 16), cvcl_div_up(a->M, 16));
-#define CVCL_SMALL(TR_) hipLaunchKernelGGL(gemm_f32_small_kernel<TR_>, grid, dim3(256), 0, stream, (const float*)a->A, (const float*)a->W, \
-                                           (float*)a->C, a->M, a->N, a->K, a->lda, a->ldw, a->ldc, a->exp_scale, a->bias)
-            switch (tr) { case 0: CVCL_SMALL(0); break; case 1: CVCL_SMALL(1); break; case 2: CVCL_SMALL(2); break; default: CVCL_SMALL(3); }
-#undef CVCL_SMALL
-            CVCL_LAUNCH_CHECK();
-            return CVCL_OK;
-        }
-        if (split64_ok && t_split64 < t_mfma128) {
-            // the tail's products: many 64 x 64 workgroups (gemm_f32_split_kernel)
-            const int vec = (a->lda % 4 == 0) && (a->ldw % 4 == 0) && cvcl_aligned16(a->A) && cvcl_aligned16(a->W) && cvcl_aligned16(a->C);
-            CvclProfScope prof(stream, CVCL_K_GEMM_F32);
-            const dim3 grid(cvcl_div_up(a->M, TS), cvcl_div_up(a->N, TS));
-#define CVCL_SPLIT(TR_) hipLaunchKernelGGL(gemm_f32_split_kernel<TR_>, grid, dim3(256), 0, stream, (const float*)a->A, (const float*)a->W, \
-                                           (float*)a->C, a->M, a->N, a->K, a->lda, a->ldw, a->ldc, a->bias, a->act, a->a_rowsum, vec)
-            switch (tr) { case 0: CVCL_SPLIT(0); break; case 1: CVCL_SPLIT(1); break; case 2: CVCL_SPLIT(2); break; default: CVCL_SPLIT(3); }
-#undef CVCL_SPLIT
-            CVCL_LAUNCH_CHECK();
-            return CVCL_OK;
-        }
-        if (tr || split) {
-            CVCL_CHECK_ARG(pro_kind(a) == 0, "cvcl_gemm: K-major operands take no prologue");
-            switch (tr | (split ? 4 : 0)) {
-                case 1: return launch_gemm_v<float, 0, false, 1>(a, d, stream);
-                case 2: return launch_gemm_v<float, 0, false, 2>(a, d, stream);
-                case 3: return launch_gemm_v<float, 0, false, 3>(a, d, stream);
-                case 4: return launch_gemm_v<float, 0, false, 4>(a, d, stream);
-                case 5: return launch_gemm_v<float, 0, false, 5>(a, d, stream);
-                case 6: return launch_gemm_v<float, 0, false, 6>(a, d, stream);
-                default: return launch_gemm_v<float, 0, false, 7>(a, d, stream);
-            }
-        }
-    }
-    switch (pro_kind(a)) {
-        case 0: return lean ? launch_gemm_v<T, 0, true>(a, d, stream) : launch_gemm_v<T, 0, false>(a, d, stream);
-        case 1: return lean ? launch_gemm_v<T, 1, true>(a, d, stream) : launch_gemm_v<T, 1, false>(a, d, stream);
-        default: return lean ? launch_gemm_v<T, 2, true>(a, d, stream) : launch_gemm_v<T, 2, false>(a, d, stream);
-    }
-}
-
-// every variant of one dtype is compiled for the same occupancy target, so one query stands for all of them
-template <typename T>
-int grid_m_query(int M, int N) {
-    return grid_m_for(M, N, resident_per_cu<T, 0, true>() * num_cus());
+    if (p.epi == 6) { d.R = a->G; d.ldr = a->ldg; }
+    if (p.route == ROUTE_GLDS)
+        return with_const<7>(p.epi, [&](auto EPI) { return launch_gemm_glds<decltype(EPI)::value>(d, p.stats_rows, stream); });
+    return p.bf16 ? launch_gemm_tiled<bf16_t>(p, d, stream) : launch_gemm_tiled<float>(p, d, stream);
 }
 
 }  // namespace
@@ -1336,38 +1398,24 @@ extern "C" int cvcl_gemm_grid_m(int dtype, int M, int N, int has_prologue) {
 // the answer assumes a buffer of that many rows will be passed)
 extern "C" int cvcl_gemm_stats_rows(int dtype, const cvcl_gemm_args* a) {
     if (!a || !cvcl_dtype_trunk(dtype)) return 0;
-    if (dtype == CVCL_F32X3) return cvcl_gemm_split_stats_rows(a->M, a->N);
-    cvcl_gemm_args t = *a;
-    static float dummy;
-    t.stats = &dummy;
-    t.stats_rows = 1 << 30;
-    if (pick_gemm_pro(dtype, &t)) return cvcl_gemm_pro_stats_rows(a->M, a->N);
-    if (pick_gemm8w(dtype, &t) == 0) return cvcl_gemm8w_stats_rows(a->M, a->N);
-    return cvcl_gemm_grid_m(dtype, a->M, a->N, 0);
+    return plan_gemm(dtype, a, true).stats_rows;
 }
 
-extern "C" int cvcl_gemm_ln_supported(const cvcl_gemm_args* a) { return a && pick_gemm8w(CVCL_BF16, a) == 1; }
+extern "C" int cvcl_gemm_ln_supported(const cvcl_gemm_args* a) {
+    if (!a) return 0;
+    const GemmPlan p = plan_gemm(CVCL_BF16, a, false);
+    return p.route == ROUTE_8W && p.epi == 1;
+}
 
 extern "C" int cvcl_gemm(int dtype, const cvcl_gemm_args* a, void* stream) {
     CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_gemm");
     CVCL_CHECK_ARG(a && a->A && a->W && (a->C || a->stats), "cvcl_gemm: null operand");
-    if ((a->ln_stats || a->ln_colsum || a->row_part) && !(dtype == CVCL_BF16 && pick_gemm8w(dtype, a) == 1)) {
-        cvcl_set_error("cvcl_gemm: ln_stats / row_part (LayerNorm folded into the linear) exist in the 8-wave bf16 kernel only; these "
-                       "arguments do not select it (M %d N %d K %d) -- ask cvcl_gemm_ln_supported first", a->M, a->N, a->K);
-        return CVCL_EUNSUPPORTED;
+    const GemmPlan p = plan_gemm(dtype, a, false);
+    if (p.rc != CVCL_OK) {
+        cvcl_set_error("%s", p.msg);
+        return p.rc;
     }
-    CVCL_CHECK_ARG(!a->c_scale || dtype == CVCL_BF16, "cvcl_gemm: the c_scale epilogue exists for bf16 only");
-    CVCL_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "cvcl_gemm: bad shape %d %d %d", a->M, a->N, a->K);
-    CVCL_CHECK_ARG((a->a_scale == nullptr) == (a->a_shift == nullptr), "cvcl_gemm: a_scale/a_shift must come together");
-    // centred storage belongs to the convolution epilogues (plain / statistics / Bottleneck tail); nn.Linear epilogues have no BN behind them
-    CVCL_CHECK_ARG(!a->centre || (((uintptr_t)a->centre & 15) == 0 && !a->bias && !a->exp_scale && !a->C_pre && !a->G &&
-                                  (a->c_scale || (!a->R && a->act == CVCL_ACT_NONE))),
-                   "cvcl_gemm: centre goes with the convolution epilogues only (16-byte aligned, no bias / activation / residual)");
-    if (dtype == CVCL_F32) return launch_gemm<float>(a, (hipStream_t)stream);
-    if (dtype == CVCL_F32X3) return cvcl_gemm_split(a, stream);
-    if (dtype == CVCL_BF16) return launch_gemm<bf16_t>(a, (hipStream_t)stream);
-    cvcl_set_error("cvcl_gemm: unknown dtype %d", dtype);
-    return CVCL_EINVAL;
+    return launch_gemm(p, a, stream);
 }
 
 extern "C" int cvcl_transpose_f32(const float* in, float* out, int rows, int cols, void* stream) {

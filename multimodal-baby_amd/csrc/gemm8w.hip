@@ -3,6 +3,7 @@
 // the 1x1 convolutions of ResNeXt layers 2-4 (reference call site multimodal/multimodal.py:101) and the ViT linears
 // (multimodal/vision_transformer_dino_mugs.py:92-94,113-115).
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 #include "gemm8w_kernel.h"
@@ -85,9 +86,6 @@ int g8_superrow(int grid, int ncol) {
 }
 
 int g8_linear(g8w::Dev d, const cvcl_gemm_args* a, hipStream_t st) {
-    // the linear epilogue comes in two instantiations: activation (no residual) and residual (no activation) -- the only
-    // combinations nn.Linear call sites on the path use (vit:92-94 fc1 + GELU, :113-115 / :146-147 proj, fc2 + residual)
-    CVCL_CHECK_ARG(!(a->R && a->act != CVCL_ACT_NONE), "cvcl_gemm8w: activation and residual together are not implemented");
     const G8Plan pl = g8_plan(a->M, d.ncol);
     CvclProfScope prof(st, CVCL_K_GEMM8W);
     d.tiles_m = cvcl_div_up(d.M, pl.bm);
@@ -115,51 +113,66 @@ extern "C" int cvcl_gemm8w_supported(int M, int N, int K, int lda, int ldw, int 
            ldc % 8 == 0;
 }
 
-// Tile height for an [M, N] output: 256 rows (MI 8) or 224 (MI 7).  M of the ResNeXt activations is 49 * 2^k: 224 = 7 * 32
-// divides it and leaves 7/8 of the workgroup slots busy in the last round where 256-row tiles leave ~5/8.  Picks the height
-// with the smaller (rounds x height); ties -> 256.
-extern "C" int cvcl_gemm8w_tile_rows(int M, int N) {
+// "Can I take this": one spelling for cvcl_gemm8w below (direct) and for the dispatcher's routing (cvcl_common.h): the reason as
+// cvcl_gemm8w reports it, or NULL.  The checks under `direct` are those only the entry has ever made -- the dispatcher routes such
+// a block here and the entry then refuses it; they stand between the others because the entry's first failing check names the reason.
+static const char G8_BAD_SHAPE[] = "cvcl_gemm8w: unsupported shape / options", G8_BAD_EPI[] = "cvcl_gemm8w: epilogue";   // + numbers
+const char* cvcl_gemm8w_refusal(int epi, const cvcl_gemm_args* a, bool direct) {
+    if (!cvcl_gemm8w_supported(a->M, a->N, a->K, a->lda, a->ldw, a->ldc) || a->a_scale || a->exp_scale || a->c_scale || a->C_pre || a->G)
+        return G8_BAD_SHAPE;
+    if (epi != 0 && epi != 1) return G8_BAD_EPI;
+    if (epi == 0 && (a->bias || a->R || a->act != CVCL_ACT_NONE)) return "cvcl_gemm8w: epilogue 0 takes no bias / activation / residual";
+    if (epi == 1 && (!a->C || a->stats)) return "cvcl_gemm8w: epilogue 1 writes C and takes no statistics";
+    if (direct && epi == 1 && a->centre) return "cvcl_gemm8w: centre goes with the convolution epilogue only";
+    if (a->ln_stats && (epi != 1 || a->R || !a->ln_colsum || !a->bias || a->row_part))
+        return "cvcl_gemm8w: ln_stats goes with the bias / activation epilogue and needs ln_colsum and the folded bias";
+    if (a->row_part && (epi != 1 || !a->R)) return "cvcl_gemm8w: row_part goes with the bias + residual epilogue";
+    if (direct && a->ln_colsum && !a->ln_stats) return "cvcl_gemm8w: ln_colsum without ln_stats";
+    if (!cvcl_aligned16(a->A) || !cvcl_aligned16(a->W) || !cvcl_aligned16(a->C) || !cvcl_aligned16(a->R) || !cvcl_aligned16(a->bias) ||
+        (a->R && a->ldr % 8) || (direct && (!cvcl_aligned16(a->ln_stats) || !cvcl_aligned16(a->ln_colsum) || ((uintptr_t)a->row_part & 7))))
+        return "cvcl_gemm8w: operands must be 16-byte aligned";
+    long a_rows = a->M;
+    if (a->gather_stride > 1) {                              // strided 1x1 convolution (the downsample branch of blocks 2.0 / 3.0 / 4.0)
+        if (a->gather_ho <= 0 || a->gather_wo <= 0 || a->M % (a->gather_ho * a->gather_wo) ||
+            (direct && ((a->gather_ho - 1) * a->gather_stride >= a->gather_hi || (a->gather_wo - 1) * a->gather_stride >= a->gather_wi)))
+            return "cvcl_gemm8w: gather geometry";
+        a_rows = (long)(a->M / (a->gather_ho * a->gather_wo)) * a->gather_hi * a->gather_wi;
+    }
+    if (a_rows * a->lda >= (1L << 31) || (long)a->N * a->ldw >= (1L << 31)) return "cvcl_gemm8w: operand offsets must fit 31 bits";
+    // the linear epilogue comes in two instantiations: activation (no residual) and residual (no activation) -- the only
+    // combinations nn.Linear call sites on the path use (vit:92-94 fc1 + GELU, :113-115 / :146-147 proj, fc2 + residual)
+    if (epi == 1 && a->R && a->act != CVCL_ACT_NONE) return "cvcl_gemm8w: activation and residual together are not implemented";
+    return nullptr;
+}
+
+// Column-fixed mapping (epi 0) of an [M, N] output: tile height 256 rows (MI 8) or 224 (MI 7), and the grid rows that go with it (one
+// BN-statistics row each).  M of the ResNeXt activations is 49 * 2^k: 224 = 7 * 32 divides it and leaves 7/8 of the workgroup slots
+// busy in the last round where 256-row tiles leave ~5/8.  Picks the height with the smaller (rounds x height); ties -> 256.
+static G8Plan g8_conv_plan(int M, int N) {
     const int ncol = N / 256;
-    int best = 256;
+    G8Plan best = {256, 8};
     long best_cost = -1;
     for (int bm : {256, 224}) {
         const int tiles = cvcl_div_up(M, bm), gm = g8_grid_m(tiles, ncol);
         const long cost = (long)cvcl_div_up(tiles, gm) * bm;
-        if (best_cost < 0 || cost < best_cost) { best = bm; best_cost = cost; }
+        if (best_cost < 0 || cost < best_cost) { best = {bm, gm}; best_cost = cost; }
     }
     return best;
 }
-
-// BN-statistics rows cvcl_gemm8w writes for an [M, N] output (one per grid row)
-extern "C" int cvcl_gemm8w_stats_rows(int M, int N) {
-    const int bm = cvcl_gemm8w_tile_rows(M, N);
-    return g8_grid_m(cvcl_div_up(M, bm), N / 256);
-}
+extern "C" int cvcl_gemm8w_tile_rows(int M, int N) { return g8_conv_plan(M, N).bm; }
+extern "C" int cvcl_gemm8w_stats_rows(int M, int N) { return g8_conv_plan(M, N).grid; }
 
 // epi 0: convolution epilogue (round + BN partial sums; C may be NULL = statistics only); epi 1: bias / activation / residual
 extern "C" int cvcl_gemm8w(int epi, const cvcl_gemm_args* a, void* stream) {
     CVCL_CHECK_ARG(a && a->A && a->W && (a->C || a->stats), "cvcl_gemm8w: null operand");
-    CVCL_CHECK_ARG(cvcl_gemm8w_supported(a->M, a->N, a->K, a->lda, a->ldw, a->ldc) && !a->a_scale &&
-                       !a->exp_scale && !a->c_scale && !a->C_pre && !a->G,
-                   "cvcl_gemm8w: unsupported shape / options (M %d N %d K %d)", a->M, a->N, a->K);
-    CVCL_CHECK_ARG(epi == 0 || epi == 1, "cvcl_gemm8w: epilogue %d", epi);
-    CVCL_CHECK_ARG(epi == 1 || (!a->bias && !a->R && a->act == CVCL_ACT_NONE), "cvcl_gemm8w: epilogue 0 takes no bias / activation / residual");
-    CVCL_CHECK_ARG(epi == 0 || (a->C && !a->stats), "cvcl_gemm8w: epilogue 1 writes C and takes no statistics");
-    CVCL_CHECK_ARG(epi == 0 || !a->centre, "cvcl_gemm8w: centre goes with the convolution epilogue only");
-    CVCL_CHECK_ARG(!a->ln_stats || (epi == 1 && !a->R && a->ln_colsum && a->bias && !a->row_part),
-                   "cvcl_gemm8w: ln_stats goes with the bias / activation epilogue and needs ln_colsum and the folded bias");
-    CVCL_CHECK_ARG(!a->row_part || (epi == 1 && a->R), "cvcl_gemm8w: row_part goes with the bias + residual epilogue");
-    CVCL_CHECK_ARG(!a->ln_colsum || a->ln_stats, "cvcl_gemm8w: ln_colsum without ln_stats");
-    CVCL_CHECK_ARG(cvcl_aligned16(a->A) && cvcl_aligned16(a->W) && cvcl_aligned16(a->C) && cvcl_aligned16(a->R) && cvcl_aligned16(a->bias) && (!a->R || a->ldr % 8 == 0) &&
-                       cvcl_aligned16(a->ln_stats) && cvcl_aligned16(a->ln_colsum) && (((uintptr_t)a->row_part & 7) == 0),
-                   "cvcl_gemm8w: operands must be 16-byte aligned");
+    if (const char* why = cvcl_gemm8w_refusal(epi, a, true)) {
+        if (why == G8_BAD_SHAPE) cvcl_set_error("%s (M %d N %d K %d)", why, a->M, a->N, a->K);
+        else if (why == G8_BAD_EPI) cvcl_set_error("%s %d", why, epi);
+        else cvcl_set_error("%s", why);
+        return CVCL_EINVAL;
+    }
     const bool gather = a->gather_stride > 1;
-    if (gather)
-        CVCL_CHECK_ARG(a->gather_ho > 0 && a->gather_wo > 0 && a->M % (a->gather_ho * a->gather_wo) == 0 &&
-                           (a->gather_ho - 1) * a->gather_stride < a->gather_hi && (a->gather_wo - 1) * a->gather_stride < a->gather_wi,
-                       "cvcl_gemm8w: gather geometry");
     const long a_rows = gather ? (long)(a->M / (a->gather_ho * a->gather_wo)) * a->gather_hi * a->gather_wi : a->M;
-    CVCL_CHECK_ARG(a_rows * a->lda < (1L << 31) && (long)a->N * a->ldw < (1L << 31), "cvcl_gemm8w: operand offsets must fit 31 bits");
     g8w::Dev d;
     d.A = (const bf16_t*)a->A; d.W = (const bf16_t*)a->W; d.C = (bf16_t*)a->C; d.R = (const bf16_t*)a->R;
     d.bias = a->bias; d.stats = a->stats; d.centre = a->centre;
@@ -169,21 +182,16 @@ extern "C" int cvcl_gemm8w(int epi, const cvcl_gemm_args* a, void* stream) {
     d.ncol = a->N / 256;
     d.gs = gather ? a->gather_stride : 1; d.g_hw = gather ? a->gather_ho * a->gather_wo : 1; d.g_wo = gather ? a->gather_wo : 1;
     d.g_hi = a->gather_hi; d.g_wi = a->gather_wi; d.a_rows = (int)a_rows;
-    int bm, grid;
     // a plain product without BN statistics has no reason to keep a column tile per workgroup: it takes the linear epilogue's
     // supertile walk (bias NULL = 0) -- the large square products of tools/blaslt_compare.py; every convolution of the trunk asks
     // for statistics and keeps the column-fixed mapping
     if (epi == 0 && !a->stats && !a->centre && !gather && a->C) epi = 1;
-    if (epi == 0) {                                          // column-fixed mapping: grid_m workgroups per column tile
-        bm = cvcl_gemm8w_tile_rows(a->M, a->N);
-        d.tiles_m = cvcl_div_up(a->M, bm);
-        d.grid_m = g8_grid_m(d.tiles_m, d.ncol);
-        if (a->stats) CVCL_CHECK_ARG(d.stats_acc || a->stats_rows >= d.grid_m, "cvcl_gemm8w: stats_rows %d < %d", a->stats_rows, d.grid_m);
-        grid = d.grid_m * d.ncol;
-    } else {
-        return g8_linear(d, a, (hipStream_t)stream);
-    }
+    if (epi == 1) return g8_linear(d, a, (hipStream_t)stream);
+    const G8Plan pl = g8_conv_plan(a->M, a->N);              // column-fixed mapping: pl.grid workgroups per column tile
+    d.tiles_m = cvcl_div_up(a->M, pl.bm);
+    d.grid_m = pl.grid;
+    CVCL_CHECK_ARG(cvcl_stats_rows_fit(a, pl.grid), "cvcl_gemm8w: stats_rows %d < %d", a->stats_rows, pl.grid);
     CvclProfScope prof(stream, CVCL_K_GEMM8W);
     hipStream_t st = (hipStream_t)stream;
-    return bm == 256 ? g8_launch<8, 0>(d, grid, st) : g8_launch<7, 0>(d, grid, st);
+    return pl.bm == 256 ? g8_launch<8, 0>(d, pl.grid * d.ncol, st) : g8_launch<7, 0>(d, pl.grid * d.ncol, st);
 }

@@ -85,8 +85,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pro_kernel(ProDev p) {
     // plain operand (a_scale == NULL, round 6): A is multiplied as stored -- conv1 of layer2.0 (M = 802 816, K = 256, N = 256: 822 MB
     // of traffic for 105 GFLOP) streams through this kernel 15 % faster than through the 128 x 128 direct-to-LDS kernel
     // It runs the SAME instruction stream with scale 1, shift 0 and the ReLU floor at -32768 (x * 1 + 0 rounds back to x for every
-    // bf16 x): a branch around the staging math sits between the tile loads and their use, and the compiler then waits for ALL loads
-    // in flight before it (measured: this launch 215 us with the branch, 150 without; the tails slowed down with it).
+    // bf16 x but -0.0, which becomes +0.0 and multiplies to the same product): a branch around the staging math sits between the
+    // tile loads and their use, and the compiler then waits for ALL loads in flight before it (measured: this launch 215 us with the branch, 150 without; the tails slowed down with it).
     const bool plain = p.a_scale == nullptr;
     const short fl = plain ? (short)-32768 : (short)0;            // ReLU on rounded bf16 pairs = packed int16 max
     const s16x2 floor2 = s16x2{fl, fl};
@@ -445,22 +445,23 @@ int pro_launch(const ProDev& d, dim3 grid, hipStream_t stream) {
 
 // the cvcl_gemm argument blocks this kernel takes: bf16, BN + ReLU operand prologue (or, for the first two epilogues, the operand
 // as stored), K = 128 | 256, N % 256 == 0, and one of {statistics only, C + statistics, Bottleneck tail (c_scale / c_shift + residual)}
-extern "C" int cvcl_gemm_pro_supported(const cvcl_gemm_args* a) {
-    if (!a) return 0;
+// (stats: statistics are asked for -- the entry reads it from a->stats, the dispatcher's row-count probe assumes it)
+bool cvcl_gemm_pro_takes(const cvcl_gemm_args* a, bool stats) {
     const bool plain = !a->a_scale && !a->a_shift;        // round 6: A as stored (no tail epilogue, no recomputed downsample)
-    if (!plain && (!a->a_scale || !a->a_shift || !a->a_relu)) return 0;
-    if (plain && (a->c_scale || a->A2 || a->W2)) return 0;
-    if ((a->K != 128 && a->K != 256) || a->N % PN != 0 || a->M < 1) return 0;
-    if (a->lda % 8 || a->ldw % 8 || (a->C && a->ldc % 8) || a->gather_stride > 1 || a->exp_scale || a->bias || a->C_pre || a->G) return 0;
-    if (!cvcl_aligned16(a->A) || !cvcl_aligned16(a->W) || !cvcl_aligned16(a->C) || !cvcl_aligned16(a->R)) return 0;
+    if (!plain && (!a->a_scale || !a->a_shift || !a->a_relu)) return false;
+    if (plain && (a->c_scale || a->A2 || a->W2)) return false;
+    if ((a->K != 128 && a->K != 256) || a->N % PN != 0 || a->M < 1) return false;
+    if (a->lda % 8 || a->ldw % 8 || (a->C && a->ldc % 8) || a->gather_stride > 1 || a->exp_scale || a->bias || a->C_pre || a->G) return false;
+    if (!cvcl_aligned16(a->A) || !cvcl_aligned16(a->W) || !cvcl_aligned16(a->C) || !cvcl_aligned16(a->R)) return false;
     if (a->c_scale && a->A2)                              // tail with the downsample branch recomputed from the block input
-        return a->c_shift && !a->R && a->C && !a->stats && a->act == CVCL_ACT_RELU && a->W2 && a->K2 == K2 && a->K == 128 && a->r_scale &&
+        return a->c_shift && !a->R && a->C && !stats && a->act == CVCL_ACT_RELU && a->W2 && a->K2 == K2 && a->K == 128 && a->r_scale &&
                a->r_shift && a->lda2 % 8 == 0 && a->ldw2 % 8 == 0 && cvcl_aligned16(a->A2) && cvcl_aligned16(a->W2);
-    if (a->A2 || a->W2) return 0;
-    if (a->c_scale) return a->c_shift && a->R && a->C && !a->stats && a->ldr % 8 == 0 && a->act == CVCL_ACT_RELU &&
+    if (a->A2 || a->W2) return false;
+    if (a->c_scale) return a->c_shift && a->R && a->C && !stats && a->ldr % 8 == 0 && a->act == CVCL_ACT_RELU &&
                            (a->r_scale == nullptr) == (a->r_shift == nullptr);
-    return !a->R && a->act == CVCL_ACT_NONE && (a->C || a->stats);
+    return !a->R && a->act == CVCL_ACT_NONE && (a->C || stats);
 }
+extern "C" int cvcl_gemm_pro_supported(const cvcl_gemm_args* a) { return a && cvcl_gemm_pro_takes(a, a->stats != nullptr); }
 
 // statistics rows written: one per workgroup row (grid.x)
 extern "C" int cvcl_gemm_pro_stats_rows(int M, int N) {
@@ -481,7 +482,7 @@ extern "C" int cvcl_gemm_pro(const cvcl_gemm_args* a, void* stream) {
     d.A2 = (const bf16_t*)a->A2; d.W2 = (const bf16_t*)a->W2; d.centre2 = a->centre2; d.lda2 = a->lda2; d.ldw2 = a->ldw2;
     d.tiles = cvcl_div_up(a->M, PM);
     const int gx = cvcl_gemm_pro_stats_rows(a->M, a->N);
-    if (a->stats) CVCL_CHECK_ARG(d.stats_acc || a->stats_rows >= gx, "cvcl_gemm_pro: stats_rows %d < %d", a->stats_rows, gx);
+    CVCL_CHECK_ARG(cvcl_stats_rows_fit(a, gx), "cvcl_gemm_pro: stats_rows %d < %d", a->stats_rows, gx);
     dim3 grid(gx, a->N / PN);
     const int mode = a->c_scale ? (a->A2 ? PRO_TAIL_DS : PRO_TAIL) : (a->C ? PRO_STORE : PRO_STATS);
     CvclProfScope prof(stream, CVCL_K_GEMM_PRO);
