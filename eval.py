@@ -11,6 +11,11 @@ used: ``--trial_batch T`` trials are encoded together (4T images + T labels in o
 BatchNorm is per-sample so the numbers are those of the batch-1 calls) and each trial's 4 logits are read off the
 block diagonal of the T x 4T logit matrix -- the batch-1 path is launch-latency bound (~0.6 ms per trial).
 
+``--clip_eval --clip_checkpoint PATH --clip_bpe PATH`` scores the same trials with an OpenAI-layout CLIP (the reference's upper-bound
+baseline, eval.py:29-45, 122-124, 205-207, 224-226, 287-288) through multimodal/clip_model.py: the weights (a TorchScript archive or
+a state dict) and the tokenizer's merges file are the user's; frames get CLIP's normalisation and labels CLIP's tokenizer in the
+data module.
+
 ``--eval_dataset saycam | object_categories`` read the reference's private evaluation frames from hard-coded cluster paths
 and are not available here; ``synthetic`` uses the synthetic trials of the data module (same item layout)."""
 import argparse
@@ -78,16 +83,22 @@ def results_filename(args, cfg):
 
 
 @torch.no_grad()
-def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention_maps=False, rollout=False):
+def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention_maps=False, rollout=False, clip=False):
     """trials: list of collated batch-1 items (img, label, label_len, raw_label).  Returns per trial (soft-max list, pred).
     All trials of the list are encoded in one pass; trial t's logits are the t-th diagonal block.
     ``attention_maps``: returns (per-trial results, Grad-CAM maps [T, 4, h, w]) -- per trial the maps of its 4 images w.r.t. its
     label (``image``) or of its image w.r.t. its 4 labels (``text``), from the same encoder pass as the logits.  A ViT encoder has
     no Grad-CAM: its maps are the CLS token's last-block self-attention [T, 4, gh, gw], which do not depend on the label (``text``:
     the one image's map repeated 4 times, so the array keeps its shape); with ``rollout`` they are the CLS token's attention rollout
-    over all blocks instead, same shape."""
+    over all blocks instead, same shape.
+    ``clip``: the labels are CLIP token rows ([1, 1, 77] / [1, 4, 77] per trial, reference eval.py:205-207, 224-226): stacked to
+    [T, 77] / [4T, 77] and scored by ``model(imgs, tokens)``."""
     T = len(trials)
-    if eval_type == "image":
+    if clip:
+        imgs = torch.cat([t[0].squeeze(0) for t in trials], 0).to(device)
+        n_per = trials[0][0].shape[1] if eval_type == "image" else trials[0][1].shape[1]
+        tokens = torch.cat([t[1].squeeze(0) for t in trials], 0).to(device)
+    elif eval_type == "image":
         imgs = torch.cat([t[0].squeeze(0) for t in trials], 0).to(device)                    # [4T, ...]
         n_per = trials[0][0].shape[1]
         L = max(t[1].shape[1] for t in trials)
@@ -106,7 +117,9 @@ def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention
     if imgs.dtype == torch.uint8 and datamodule is not None:                                 # --device_frames: base transform on the GPU
         imgs = datamodule.on_after_batch_transfer((imgs,), 1, training=False)[0]
     maps = None
-    if attention_maps and getattr(getattr(model, "vision_encoder", None), "vit_dino", False):
+    if clip:
+        logits_per_image, logits_per_text = model(imgs, tokens)
+    elif attention_maps and getattr(getattr(model, "vision_encoder", None), "vit_dino", False):
         logits_per_image, logits_per_text, maps = model.self_attention_maps(imgs, labels.to(device), lens.to(device), rollout=rollout)
         if eval_type == "image":                          # [4T, gh, gw] -> [T, 4, gh, gw]
             maps = maps.view(T, n_per, *maps.shape[1:])
@@ -144,27 +157,56 @@ def plot_attention(path, image, cam):
     plt.close(fig)
 
 
+CLIP_CONFIG = {"model": "clip", "seed": None, "shuffle_utterances": None, "cnn": "clip", "augment_frames": None,
+               "multiple_frames": None}                    # the run attributes of a --clip_eval record (eval.py:39-47)
+
+
+def clip_results_filename(args):
+    """eval.py:287-288."""
+    return f"results/{args.eval_dataset}/clip_{args.eval_type}_{args.eval_dataset}_{args.stage}_eval_predictions.json"
+
+
+def check_clip_args(args):
+    """What --clip_eval needs and what it does not combine with, before anything is loaded."""
+    if not (args.clip_checkpoint and args.clip_bpe):
+        raise SystemExit("--clip_eval needs --clip_checkpoint PATH (OpenAI CLIP weights: a TorchScript archive such as ViT-L-14.pt, or a "
+                         "state_dict file) and --clip_bpe PATH (CLIP's bpe_simple_vocab_16e6.txt or .txt.gz); neither is shipped or fetched")
+    for flag, on in (("--attention_maps", args.attention_maps), ("--plot_attention", args.plot_attention),
+                     ("--attention_rollout", args.attention_rollout), ("--hip_graph", args.hip_graph)):
+        if on:
+            raise SystemExit(f"{flag} is not built for --clip_eval (CLIP attention maps and graph replay of the CLIP towers are out of scope)")
+    if args.precision not in ("32", "bf16"):
+        raise SystemExit(f"--clip_eval runs in --precision 32 or bf16, not {args.precision}")
+
+
 def main(args):
     if args.clip_eval:
-        raise SystemExit("--clip_eval evaluates OpenAI CLIP ViT-L/14 through the `clip` package, which is not part of this path")
+        check_clip_args(args)
     if args.eval_dataset != "synthetic":
         raise SystemExit(f"--eval_dataset {args.eval_dataset} reads the reference's private evaluation frames from hard-coded "
                          "cluster paths and is not available here; use --eval_dataset synthetic")
     device = torch.device("cuda:0")
-    checkpoint_name = args.checkpoint
-    checkpoint = resolve_checkpoint(checkpoint_name, args.checkpoints_root)
-    cfg = config_from_checkpoint_name(checkpoint_name)
-    model = MultiModalLitModel.load_from_checkpoint(checkpoint, map_location=device)
-    model.to(device)
-    model.eval()
-    if args.precision != "32":                             # (32: the exact-fp32 mode a loaded model starts in)
-        model.set_precision(args.precision)
-    if args.hip_graph:                                     # replay the image encoder's launches as a HIP graph per batch shape
-        model.vision_encoder.enable_hip_graphs(True)
-
     data_args = _setup_parser().parse_args("")
-    for key, value in model.args.items():
-        setattr(data_args, key, value)
+    if args.clip_eval:                                     # eval.py:29-47
+        from multimodal import clip_model
+        checkpoint_name = "clip_vitl_14"
+        model, _ = clip_model.load(args.clip_checkpoint, device)
+        model.set_precision(args.precision)
+        cfg = dict(CLIP_CONFIG)
+        data_args.clip_eval, data_args.clip_bpe = True, args.clip_bpe      # CLIP's frame statistics and tokenizer (eval.py:122-124)
+    else:
+        checkpoint_name = args.checkpoint
+        checkpoint = resolve_checkpoint(checkpoint_name, args.checkpoints_root)
+        cfg = config_from_checkpoint_name(checkpoint_name)
+        model = MultiModalLitModel.load_from_checkpoint(checkpoint, map_location=device)
+        model.to(device)
+        model.eval()
+        if args.precision != "32":                         # (32: the exact-fp32 mode a loaded model starts in)
+            model.set_precision(args.precision)
+        if args.hip_graph:                                 # replay the image encoder's launches as a HIP graph per batch shape
+            model.vision_encoder.enable_hip_graphs(True)
+        for key, value in model.args.items():
+            setattr(data_args, key, value)
     data_args.augment_frames = False                       # deterministic frames (eval.py:115)
     data_args.eval_include_sos_eos = args.eval_include_sos_eos
     data_args.eval_type = args.eval_type
@@ -180,7 +222,7 @@ def main(args):
     correct_pred = {c: 0 for c in classes}
     total_pred = {c: 0 for c in classes}
 
-    if args.attention_rollout and not getattr(model.vision_encoder, "vit_dino", False):
+    if args.attention_rollout and not getattr(model.vision_encoder, "vit_dino", False):        # (never under --clip_eval)
         raise SystemExit("--attention_rollout is defined for a ViT checkpoint (--vit_dino) only: a ResNeXt encoder has no "
                          "self-attention to roll out; its --attention_maps are Grad-CAM maps")
     if args.attention_rollout and not (args.attention_maps or args.plot_attention):
@@ -194,7 +236,8 @@ def main(args):
 
     def flush():
         nonlocal first
-        res = evaluate_trials(model, pending, args.eval_type, device, data, attention_maps=want_maps, rollout=args.attention_rollout)
+        res = evaluate_trials(model, pending, args.eval_type, device, data, attention_maps=want_maps, rollout=args.attention_rollout,
+                              clip=args.clip_eval)
         if want_maps:
             res, maps = res
             cams.append(maps.cpu())
@@ -239,7 +282,7 @@ def main(args):
         np.save(out, torch.cat(cams, 0).numpy())
 
     if args.save_predictions:
-        filename = results_filename(args, cfg)
+        filename = clip_results_filename(args) if args.clip_eval else results_filename(args, cfg)
         os.makedirs(os.path.dirname(filename), exist_ok=True)
         print(f"Saving predictions to {filename}")
         with open(filename, "w") as f:
@@ -259,9 +302,13 @@ def _parser():
                         help="Which evaluation dataset to use")
     parser.add_argument("--eval_metadata_filename", type=str, default="eval_test.json",
                         help="JSON file with metadata evaluation split to use")
-    parser.add_argument("--use_kitty_label", action="store_true", help="replaces cat label with kitty")
+    parser.add_argument("--use_kitty_label", action="store_true", help="replaces cat label with kitty (ignored under --clip_eval)")
     parser.add_argument("--save_predictions", action="store_true", help="save model predictions to JSON")
     # additions of this implementation
+    parser.add_argument("--clip_checkpoint", type=str, default=None, metavar="PATH",
+                        help="--clip_eval: OpenAI CLIP weights (TorchScript archive, e.g. ViT-L-14.pt, or a state_dict file); not shipped")
+    parser.add_argument("--clip_bpe", type=str, default=None, metavar="PATH",
+                        help="--clip_eval: CLIP's BPE merges file bpe_simple_vocab_16e6.txt(.gz); not shipped")
     parser.add_argument("--trial_batch", type=int, default=64, help="trials encoded per device pass (1 = the reference's loop)")
     parser.add_argument("--hip_graph", action="store_true", help="capture the eval-mode image encoder into a HIP graph per batch "
                                                                   "shape and replay it (removes the host's launch lead; same results)")

@@ -56,7 +56,11 @@ extern "C" {
 
 enum { CVCL_OK = 0, CVCL_EINVAL = -1, CVCL_ELAUNCH = -2, CVCL_EWORKSPACE = -3, CVCL_EUNSUPPORTED = -4 };
 enum { CVCL_F32 = 0, CVCL_BF16 = 1, CVCL_F32X3 = 2 };
-enum { CVCL_ACT_NONE = 0, CVCL_ACT_RELU = 1, CVCL_ACT_GELU = 2 };
+enum { CVCL_ACT_NONE = 0, CVCL_ACT_RELU = 1, CVCL_ACT_GELU = 2, CVCL_ACT_QUICK_GELU = 3 };
+/* CVCL_ACT_QUICK_GELU: x sigmoid(1.702 x), the MLP activation of OpenAI's CLIP towers (the reference's --clip_eval baseline, eval.py:29-45,
+ * 205-207, 224-226).  cvcl_gemm implements it in the bias / activation epilogues of the 8-wave kernel, of the direct-to-LDS bf16 kernel
+ * and of the tiled kernel (fp32: v / (1 + expf(-1.702 v))); fp8, LayerNorm-folded, C_pre / G and CVCL_F32X3 blocks with it are refused
+ * before anything is enqueued, and the small / 64 x 64 split fp32 kernels are not selected for it.                                  */
 /* BatchNorm accumulators (round 6).  A convolution hands its per-channel batch statistics on either as partial ROWS (one per
  * workgroup, reduced by cvcl_bn_finalize) or, with stats_rows == CVCL_STATS_ACCUMULATE, by atomically ADDING them to a caller-zeroed
  * accumulator: int64 [8][2][N] (8 rows = one per XCD; [0] sums, [1] sums of squares), fixed point with 24 fractional bits -- integer
@@ -402,6 +406,15 @@ int cvcl_layernorm(int dtype, const void* x, long x_row_stride, const float* gam
  * (vit:119-127; nn.MultiheadAttention inside nn.TransformerEncoderLayer).  bf16, hd = 64, no mask -> MFMA kernel. */
 int cvcl_attention(int dtype, const void* qkv, const int64_t* key_tok, void* out, int B, int T, int heads, int head_dim,
                    float scale, void* stream);
+/* the same attention under a causal mask: query t attends to keys 0..t, and only those products are computed (the text tower of
+ * OpenAI's CLIP, which the reference scores as its --clip_eval baseline: eval.py:205-207, 224-226).  fp32 or bf16 storage, the generic
+ * kernel in both (the text tower is a negligible share of a CLIP pass).  Same argument checks as cvcl_attention.                   */
+int cvcl_attention_causal(int dtype, const void* qkv, void* out, int B, int T, int heads, int head_dim, float scale, void* stream);
+/* CLIP's text pooling (eval.py:205-207, 224-226 through clip's encode_text): out[b,:] = LayerNorm(x[b, argmax_l tok[b,l], :]; gamma,
+ * beta, eps) -- the end-of-text id is the largest of the vocabulary, the FIRST maximum wins (torch.argmax); one workgroup per sequence,
+ * so ln_final costs B rows instead of B L.  x [B,L,W] f32, tok [B,L] int64, out [B,W] f32.                                          */
+int cvcl_clip_text_pool(const float* x, const int64_t* tok, const float* gamma, const float* beta, float eps, float* out, int B, int L,
+                        int W, void* stream);
 /* same attention (bf16 qkv, head_dim 64, 32 < T), output written as e4m3 [B*T][heads*64] + e8m0 block scales tiled
  * [heads*64/128][B*T][4] -- cvcl_gemm_fp8_mx's MX input, so the fp8 projection needs no quantisation pass in between. */
 int cvcl_attention_mx(const void* qkv, void* out8, void* out_block_scales, int B, int T, int heads, int head_dim, float scale,

@@ -383,6 +383,21 @@ __device__ inline f32x2 gelu_bf16out2(f32x2 v) {
     const f32x2 d = f32x2{1.f, 1.f} + f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
     return v * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
+// ---- QuickGELU x sigmoid(1.702 x) (OpenAI CLIP's MLP activation) for bf16 OUTPUTS: the sigmoid as v_exp_f32 + v_rcp_f32, both good to
+// ~1 ulp of fp32 -- the result is within ~3 fp32 ulp of the exact value and is then rounded to bf16 (2^-9 relative), so the fast
+// forms cost no accuracy there.  6 VALU instructions (gelu_bf16out: 9; no clamp needed: exp2 overflows to +inf -> rcp gives 0, the
+// limit).  The fp32 kernels evaluate v / (1 + expf(-1.702 v)) instead (gemm.hip apply_act).
+__device__ inline float quick_gelu_bf16out(float v) {
+    const float e = __builtin_amdgcn_exp2f(v * (-1.702f * 1.4426950408889634f));      // exp(-1.702 v)
+    return v * __builtin_amdgcn_rcpf(1.f + e);
+}
+// the same function on a pair (bit-identical per element), packed multiplies / add as gelu_bf16out2
+__device__ inline f32x2 quick_gelu_bf16out2(f32x2 v) {
+    constexpr float L = -1.702f * 1.4426950408889634f;
+    const f32x2 t = v * f32x2{L, L};
+    const f32x2 d = f32x2{1.f, 1.f} + f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
+    return v * f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+}
 // d gelu(v) / dv in the erf form (backward of the fused GELU epilogue / cvcl_gelu_bf16).  NOTE: the bf16 FORWARD epilogues use the
 // fitted gelu_bf16out above (|gelu_bf16out - gelu_erf| <= 2.6e-5), the backward differentiates the erf form: the two are the same
 // function to ~1e-4 of the derivative -- far below the bf16 rounding of the gradients it multiplies, and it keeps the fine-tuning

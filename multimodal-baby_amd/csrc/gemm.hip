@@ -71,6 +71,7 @@ template <> struct FragOps<float> {
 __device__ inline float apply_act(float v, int act) {
     if (act == CVCL_ACT_RELU) return fmaxf(v, 0.f);
     if (act == CVCL_ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+    if (act == CVCL_ACT_QUICK_GELU) return v / (1.f + expf(-1.702f * v));          // x sigmoid(1.702 x) (CLIP's MLP)
     return v;
 }
 
@@ -79,6 +80,7 @@ __device__ inline float apply_act(float v, int act) {
 __device__ inline float apply_act_bf16(float v, int act) {
     if (act == CVCL_ACT_RELU) return fmaxf(v, 0.f);
     if (act == CVCL_ACT_GELU) return gelu_bf16out(v);
+    if (act == CVCL_ACT_QUICK_GELU) return quick_gelu_bf16out(v);
     return v;
 }
 
@@ -537,13 +539,14 @@ __device__ __forceinline__ void glds16(const bf16_t* src, char* lds_wave_base) {
 //          BatchNorm of this conv's (rounded) output + identity / normalised downsample branch + ReLU, no statistics.
 // EPI = 5: linear + GELU for training: C2 = u = round(acc + bias) (kept for the backward), C = round(gelu(u)).
 // EPI = 6: data-gradient GEMM through a GELU: C = round(round(acc) * gelu'(R)), R = the saved pre-activation tile.
+// EPI = 7: the linear epilogue of EPI 1 / 3 / 4 with QuickGELU (CLIP's MLP).
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmDev p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // EPI 1 / 3 / 4 = linear epilogue with activation none / ReLU / GELU compiled in (a run-time switch per element cost
     // two scalar branches per value and inlined erff 64 times behind them)
-    constexpr bool LIN = EPI == 1 || EPI == 3 || EPI == 4 || EPI == 5 || EPI == 6;
-    constexpr int ACT = EPI == 3 ? CVCL_ACT_RELU : (EPI == 4 ? CVCL_ACT_GELU : CVCL_ACT_NONE);
+    constexpr bool LIN = EPI == 1 || EPI == 3 || EPI == 4 || EPI == 5 || EPI == 6 || EPI == 7;
+    constexpr int ACT = EPI == 3 ? CVCL_ACT_RELU : (EPI == 4 ? CVCL_ACT_GELU : (EPI == 7 ? CVCL_ACT_QUICK_GELU : CVCL_ACT_NONE));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int l31 = lane & 31, h = lane >> 5;
@@ -1140,7 +1143,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(const float* __r
 enum GemmRoute {
     ROUTE_PRO,           // gemm_pro.hip: the streaming kernel
     ROUTE_8W,            // gemm8w.hip, epi 0 (convolution) | 1 (linear)
-    ROUTE_GLDS,          // gemm_glds_kernel<epi>, epi 0-6
+    ROUTE_GLDS,          // gemm_glds_kernel<epi>, epi 0-7
     ROUTE_F32_SMALL,     // gemm_f32_small_kernel<tr>
     ROUTE_F32_SPLIT64,   // gemm_f32_split_kernel<tr>
     ROUTE_TILED,         // gemm_kernel<T, pro, lean, tr>
@@ -1197,7 +1200,7 @@ GemmPlan& plan_own_kernel(GemmPlan& p, const cvcl_gemm_args* a) {
                          "cvcl_gemm: G (GELU-backward epilogue) takes no bias / activation / residual");
             return to(ROUTE_GLDS, 6);
         }
-        if (lin_ok) return to(ROUTE_GLDS, a->act == CVCL_ACT_GELU ? 4 : a->act == CVCL_ACT_RELU ? 3 : 1);
+        if (lin_ok) return to(ROUTE_GLDS, a->act == CVCL_ACT_GELU ? 4 : a->act == CVCL_ACT_RELU ? 3 : a->act == CVCL_ACT_QUICK_GELU ? 7 : 1);
     }
     PLAN_REQUIRE(a->C && !a->c_scale, "cvcl_gemm: statistics-only / BN-tail epilogues need the direct-to-LDS bf16 path");
     if (!bf16) {
@@ -1283,6 +1286,10 @@ GemmPlan plan_gemm(int dtype, const cvcl_gemm_args* a, bool assume_stats) {
     PLAN_REQUIRE(!a->centre || (cvcl_aligned16(a->centre) && !a->bias && !a->exp_scale && !a->C_pre && !a->G &&
                                 (a->c_scale || (!a->R && a->act == CVCL_ACT_NONE))),
                  "cvcl_gemm: centre goes with the convolution epilogues only (16-byte aligned, no bias / activation / residual)");
+    // QuickGELU: the linear epilogues of the 8-wave, direct-to-LDS and tiled kernels only
+    PLAN_REQUIRE(a->act != CVCL_ACT_QUICK_GELU || (p.route != ROUTE_SPLIT3 && p.route != ROUTE_PRO && !a->ln_stats && !a->ln_colsum &&
+                                                   !a->row_part && !a->C_pre && !a->G && !a->c_scale && !a->centre),
+                 "cvcl_gemm: QuickGELU goes with the plain bias / activation / residual epilogue (not CVCL_F32X3, LayerNorm-folded, C_pre / G)");
     if (p.route == ROUTE_SPLIT3) return p;
     p.tr = (a->a_trans ? 1 : 0) | (a->w_trans ? 2 : 0);
     if (p.tr || a->a_rowsum || a->f32_split) {
@@ -1382,7 +1389,7 @@ int launch_gemm(const GemmPlan& p, const cvcl_gemm_args* a, void* stream_) {
     d.a_rowsum = a->a_rowsum;
     if (p.epi == 6) { d.R = a->G; d.ldr = a->ldg; }
     if (p.route == ROUTE_GLDS)
-        return with_const<7>(p.epi, [&](auto EPI) { return launch_gemm_glds<decltype(EPI)::value>(d, p.stats_rows, stream); });
+        return with_const<8>(p.epi, [&](auto EPI) { return launch_gemm_glds<decltype(EPI)::value>(d, p.stats_rows, stream); });
     return p.bf16 ? launch_gemm_tiled<bf16_t>(p, d, stream) : launch_gemm_tiled<float>(p, d, stream);
 }
 

@@ -93,6 +93,8 @@ int g8_linear(g8w::Dev d, const cvcl_gemm_args* a, hipStream_t st) {
     const bool tall = pl.bm == 256;
     if (a->row_part) return tall ? g8_launch<8, 2, true>(d, pl.grid, st) : g8_launch<7, 2, true>(d, pl.grid, st);
     if (a->R) return tall ? g8_launch<8, 2>(d, pl.grid, st) : g8_launch<7, 2>(d, pl.grid, st);
+    if (a->act == CVCL_ACT_QUICK_GELU)                       // CLIP's MLP; never LayerNorm-folded (cvcl_gemm8w_refusal)
+        return tall ? g8_launch<8, 1, false, CVCL_ACT_QUICK_GELU>(d, pl.grid, st) : g8_launch<7, 1, false, CVCL_ACT_QUICK_GELU>(d, pl.grid, st);
     // the bias / activation epilogue: one instantiation per activation (gemm8w_kernel.h "ACT")
 #define G8_ACT(LNF_)                                                                                                                       \
     switch (a->act) {                                                                                                                      \
@@ -142,6 +144,8 @@ const char* cvcl_gemm8w_refusal(int epi, const cvcl_gemm_args* a, bool direct) {
     // the linear epilogue comes in two instantiations: activation (no residual) and residual (no activation) -- the only
     // combinations nn.Linear call sites on the path use (vit:92-94 fc1 + GELU, :113-115 / :146-147 proj, fc2 + residual)
     if (epi == 1 && a->R && a->act != CVCL_ACT_NONE) return "cvcl_gemm8w: activation and residual together are not implemented";
+    // QuickGELU (CLIP's MLP) exists in the plain bias / activation instantiation only: not LayerNorm-folded
+    if (a->act == CVCL_ACT_QUICK_GELU && (epi != 1 || a->ln_stats)) return "cvcl_gemm8w: QuickGELU goes with the plain bias epilogue (no ln_stats)";
     return nullptr;
 }
 

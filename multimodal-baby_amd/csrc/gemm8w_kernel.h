@@ -368,6 +368,7 @@ __global__ __launch_bounds__(512, 2) void gemm8w_kernel(Dev p) {
                         else v = v + b2;
                         if constexpr (ACT == CVCL_ACT_RELU) v = f32x2{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)};
                         else if constexpr (ACT == CVCL_ACT_GELU) v = gelu_bf16out2(v);
+                        else if constexpr (ACT == CVCL_ACT_QUICK_GELU) v = quick_gelu_bf16out2(v);
                         q[e] = (bf16_t)v[0];
                         q[e + 1] = (bf16_t)v[1];
                     }

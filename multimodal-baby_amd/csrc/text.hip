@@ -214,6 +214,39 @@ __global__ __launch_bounds__(256) void scale_add_kernel(const float* __restrict_
         y[i] = alpha * (a[i] + (b ? b[i] : 0.f));
 }
 
+// CLIP's text pooling: out[b][:] = LayerNorm(x[b][argmax_l tok[b][l]][:]) -- the end-of-text id is the largest id, the first maximum
+// wins (torch.argmax).  One wave per sequence; the LayerNorm is the arithmetic of cvcl_layernorm's scalar kernel (vit.hip).
+__global__ __launch_bounds__(256) void clip_text_pool_kernel(const float* __restrict__ x, const int64_t* __restrict__ tok,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                             float* __restrict__ out, int B, int L, int W) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const int64_t* tb = tok + (long)b * L;
+    long long best = tb[0];
+    int at = 0;
+    for (int l = lane; l < L; l += 64) {                     // ascending l per lane: a strict > keeps the lane's first maximum
+        const long long t = tb[l];
+        if (t > best) { best = t; at = l; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {                       // (id desc, position asc): the same winner in every lane
+        const long long t = __shfl_xor(best, o, 64);
+        const int l = __shfl_xor(at, o, 64);
+        if (t > best || (t == best && l < at)) { best = t; at = l; }
+    }
+    const float* xr = x + ((long)b * L + at) * W;
+    float s = 0.f;
+    for (int d = lane; d < W; d += 64) s += xr[d];
+    const float mean = wave_sum(s) / (float)W;
+    float q = 0.f;
+    for (int d = lane; d < W; d += 64) {
+        const float c = xr[d] - mean;
+        q = fmaf(c, c, q);
+    }
+    const float rstd = 1.f / sqrtf(wave_sum(q) / (float)W + eps);
+    for (int d = lane; d < W; d += 64) out[(long)b * W + d] = (xr[d] - mean) * rstd * gamma[d] + beta[d];
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -297,6 +330,17 @@ extern "C" int cvcl_scale_add_f32(const float* a, const float* b, float alpha, f
     CVCL_CHECK_ARG(a && y && n > 0, "cvcl_scale_add_f32: bad args");
     CvclProfScope prof(stream, CVCL_K_OTHER);
     hipLaunchKernelGGL(scale_add_kernel, dim3(cvcl_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, a, b, alpha, y, n);
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
+}
+
+// the end-of-text pooling + ln_final of CLIP's encode_text (the reference's --clip_eval baseline, eval.py:205-207, 224-226)
+extern "C" int cvcl_clip_text_pool(const float* x, const int64_t* tok, const float* gamma, const float* beta, float eps, float* out, int B,
+                                   int L, int W, void* stream) {
+    CVCL_CHECK_ARG(x && tok && gamma && beta && out && B > 0 && L > 0 && W > 0, "cvcl_clip_text_pool: bad args");
+    CvclProfScope prof(stream, CVCL_K_LAYERNORM);
+    hipLaunchKernelGGL(clip_text_pool_kernel, dim3(cvcl_div_up(B, 4)), dim3(256), 0, (hipStream_t)stream, x, tok, gamma, beta, eps, out, B, L,
+                       W);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }

@@ -293,8 +293,9 @@ __global__ __launch_bounds__(256) void row_stats_finalize_kernel(const float* __
 // ------------------------------------------------------------------------------------------------
 // Attention, generic (any head_dim <= 128, any T, optional key padding mask): one wave per (b, head, query).
 // qkv [B, T, 3, heads, hd] -> out [B, T, heads*hd].  P is rounded to the storage type before P.V.
+// CAUSAL (cvcl_attention_causal, the CLIP text tower): query t walks keys 0..t only -- the masked products are never formed.
 // ------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void attention_valu_kernel(const T* __restrict__ qkv, const int64_t* __restrict__ key_tok,
                                                              T* __restrict__ out, int B, int Tn, int heads, int hd,
                                                              float scale) {
@@ -309,9 +310,10 @@ __global__ __launch_bounds__(256) void attention_valu_kernel(const T* __restrict
     const int D = heads * hd;
     const T* base = qkv + (long)b * Tn * 3 * D;
     const T* qp = base + (long)qi * 3 * D + hh * hd;
+    const int Tk = CAUSAL ? qi + 1 : Tn;                     // keys this query attends to
     for (int d = lane; d < hd; d += 64) sq[d] = ElemTraits<T>::to_f(qp[d]);
     float mx = -INFINITY;
-    for (int j = lane; j < Tn; j += 64) {
+    for (int j = lane; j < Tk; j += 64) {
         const T* kp = base + (long)j * 3 * D + D + hh * hd;
         float s = 0.f;
         for (int d = 0; d < hd; ++d) s = fmaf(sq[d], ElemTraits<T>::to_f(kp[d]), s);
@@ -322,17 +324,17 @@ __global__ __launch_bounds__(256) void attention_valu_kernel(const T* __restrict
     }
     mx = wave_max(mx);
     float sum = 0.f;
-    for (int j = lane; j < Tn; j += 64) {
+    for (int j = lane; j < Tk; j += 64) {
         const float e = expf(sp[j] - mx);
         sp[j] = e;
         sum += e;
     }
     sum = wave_sum(sum);
-    for (int j = lane; j < Tn; j += 64) sp[j] = ElemTraits<T>::to_f(ElemTraits<T>::from_f(sp[j] / sum));
+    for (int j = lane; j < Tk; j += 64) sp[j] = ElemTraits<T>::to_f(ElemTraits<T>::from_f(sp[j] / sum));
     T* op = out + ((long)b * Tn + qi) * D + hh * hd;
     for (int d = lane; d < hd; d += 64) {
         float acc = 0.f;
-        for (int j = 0; j < Tn; ++j) acc = fmaf(sp[j], ElemTraits<T>::to_f(base[(long)j * 3 * D + 2 * D + hh * hd + d]), acc);
+        for (int j = 0; j < Tk; ++j) acc = fmaf(sp[j], ElemTraits<T>::to_f(base[(long)j * 3 * D + 2 * D + hh * hd + d]), acc);
         op[d] = ElemTraits<T>::from_f(acc);
     }
 }
@@ -770,6 +772,24 @@ extern "C" int cvcl_attention_train(const void* qkv, void* out, float* lse, int 
     return CVCL_OK;
 }
 
+namespace {
+template <bool CAUSAL>
+int launch_attention_valu(int dtype, const void* qkv, const int64_t* key_tok, void* out, int B, int T, int heads, int head_dim, float scale,
+                          hipStream_t s, const char* who) {
+    const long nwork = (long)B * heads * T;
+    const size_t lds = (size_t)4 * (head_dim + T) * sizeof(float);
+    CVCL_CHECK_ARG(lds <= 64 * 1024, "%s: sequence too long for the generic kernel (%d)", who, T);
+    if (dtype == CVCL_F32)
+        hipLaunchKernelGGL((attention_valu_kernel<float, CAUSAL>), dim3(cvcl_div_up(nwork, 4)), dim3(256), lds, s, (const float*)qkv, key_tok,
+                           (float*)out, B, T, heads, head_dim, scale);
+    else
+        hipLaunchKernelGGL((attention_valu_kernel<bf16_t, CAUSAL>), dim3(cvcl_div_up(nwork, 4)), dim3(256), lds, s, (const bf16_t*)qkv,
+                           key_tok, (bf16_t*)out, B, T, heads, head_dim, scale);
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
+}
+}  // namespace
+
 extern "C" int cvcl_attention(int dtype, const void* qkv, const int64_t* key_tok, void* out, int B, int T, int heads,
                               int head_dim, float scale, void* stream) {
     CVCL_CHECK_DTYPE(dtype, "cvcl_attention");
@@ -782,15 +802,15 @@ extern "C" int cvcl_attention(int dtype, const void* qkv, const int64_t* key_tok
         CVCL_LAUNCH_CHECK();
         return CVCL_OK;
     }
-    const long nwork = (long)B * heads * T;
-    const size_t lds = (size_t)4 * (head_dim + T) * sizeof(float);
-    CVCL_CHECK_ARG(lds <= 64 * 1024, "cvcl_attention: sequence too long for the generic kernel (%d)", T);
-    if (dtype == CVCL_F32)
-        hipLaunchKernelGGL(attention_valu_kernel<float>, dim3(cvcl_div_up(nwork, 4)), dim3(256), lds, s, (const float*)qkv, key_tok,
-                           (float*)out, B, T, heads, head_dim, scale);
-    else
-        hipLaunchKernelGGL(attention_valu_kernel<bf16_t>, dim3(cvcl_div_up(nwork, 4)), dim3(256), lds, s, (const bf16_t*)qkv,
-                           key_tok, (bf16_t*)out, B, T, heads, head_dim, scale);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
+    return launch_attention_valu<false>(dtype, qkv, key_tok, out, B, T, heads, head_dim, scale, s, "cvcl_attention");
+}
+
+// causal self-attention of the CLIP text tower (reference eval.py:205-207, 224-226: clip's encode_text): the generic kernel for both
+// storage types -- at 77 tokens the text tower is a negligible share of a CLIP pass, so the MFMA kernel has no causal form
+extern "C" int cvcl_attention_causal(int dtype, const void* qkv, void* out, int B, int T, int heads, int head_dim, float scale,
+                                     void* stream) {
+    CVCL_CHECK_DTYPE(dtype, "cvcl_attention_causal");
+    CVCL_CHECK_ARG(qkv && out && B > 0 && T > 0 && heads > 0 && head_dim > 0 && head_dim <= 128, "cvcl_attention_causal: bad args");
+    CvclProfScope prof(stream, CVCL_K_ATTENTION);
+    return launch_attention_valu<true>(dtype, qkv, nullptr, out, B, T, heads, head_dim, scale, (hipStream_t)stream, "cvcl_attention_causal");
 }

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libcvcl_hip.so")
 
 F32, BF16, F32X3 = 0, 1, 2          # cvcl_hip.h dtypes (F32X3: fp32 storage, split-bf16 trunk products; ABI v7)
-ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3   # cvcl_hip.h CVCL_ACT_* (QUICK_GELU: CLIP's MLP)
 ABI_VERSION = 7
 PACK_DENSE, PACK_STEM7, PACK_GCONV3 = 0, 1, 2
 GRADCAM_ALL, GRADCAM_BLOCK_IMAGE, GRADCAM_BLOCK_TEXT = 0, 1, 2      # cvcl_hip.h CVCL_GRADCAM_*
@@ -112,6 +112,8 @@ SIGNATURES = {
     "cvcl_vit_assemble_tokens": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cvcl_layernorm": (_I, [_I, _P, C.c_long, _P, _P, _F, _P, _I, C.c_long, _I, _P]),
     "cvcl_attention": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "cvcl_attention_causal": (_I, [_I, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "cvcl_clip_text_pool": (_I, [_P, _P, _P, _P, _F, _P, _I, _I, _I, _P]),
     "cvcl_embed_gather_pos": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cvcl_seq_sum_div": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "cvcl_lstm_cell": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),

@@ -27,6 +27,7 @@ PAD_TOKEN, UNK_TOKEN, SOS_TOKEN, EOS_TOKEN = "<pad>", "<unk>", "<sos>", "<eos>"
 PAD_TOKEN_ID, UNK_TOKEN_ID, SOS_TOKEN_ID, EOS_TOKEN_ID = 0, 1, 2, 3
 IMAGE_H = IMAGE_W = 224
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)       # reference :262
 CLIP_EVAL = False
 VOCAB_FILENAME = os.path.join(os.path.dirname(os.path.abspath(__file__)), "vocab.json")
 
@@ -133,12 +134,17 @@ class SyntheticEvalTrials(torch.utils.data.Dataset):
     """4-way evaluation trials with the item layout of the reference's LabeledSEvalDataset (``eval_type='image'``:
     (imgs [4,3,H,W] target first, label ids [L], label length, [raw category]); multimodal_data_module.py:112-160) or
     LabeledSTextEvalDataset (``eval_type='text'``: (img [1,3,H,W], label ids [4,L] target first, [4 lengths], [raw target]);
-    :163-213).  ``metadata()`` is the list the reference reads from eval_*.json (target_category / foil_categories)."""
+    :163-213).  ``metadata()`` is the list the reference reads from eval_*.json (target_category / foil_categories).
+    ``clip_bpe`` (``--clip_eval``, :143-155, 191-202, 256-262): the same frames under CLIP's normalisation -- they are already 224 x 224,
+    so the resize and centre crop of CLIP's transform do not apply -- and the raw category names through the CLIP tokenizer:
+    label [1, 77] (``image``) or [4, 77] (``text``), lengths counting rows as in the reference."""
 
-    def __init__(self, n_trials, vocab_size, seed=0, eval_include_sos_eos=False, n_images=4, raw_frames=False, eval_type="image"):
+    def __init__(self, n_trials, vocab_size, seed=0, eval_include_sos_eos=False, n_images=4, raw_frames=False, eval_type="image",
+                 clip_bpe=None):
         self.n, self.v, self.seed, self.sos_eos, self.n_images = n_trials, vocab_size, seed, eval_include_sos_eos, n_images
-        self.raw_frames = raw_frames
+        self.raw_frames = raw_frames and clip_bpe is None
         self.eval_type = eval_type
+        self.clip_bpe = clip_bpe
 
     def __len__(self):
         return self.n
@@ -164,9 +170,14 @@ class SyntheticEvalTrials(torch.utils.data.Dataset):
         if self.raw_frames:
             imgs = torch.randint(0, 256, (n_img, IMAGE_H, IMAGE_W, 3), dtype=torch.uint8, generator=g)
         else:
-            mean = torch.tensor(IMAGENET_MEAN).view(1, 3, 1, 1)
-            std = torch.tensor(IMAGENET_STD).view(1, 3, 1, 1)
+            mean = torch.tensor(CLIP_MEAN if self.clip_bpe else IMAGENET_MEAN).view(1, 3, 1, 1)
+            std = torch.tensor(CLIP_STD if self.clip_bpe else IMAGENET_STD).view(1, 3, 1, 1)
             imgs = (torch.rand(n_img, 3, IMAGE_H, IMAGE_W, generator=g) - mean) / std
+        if self.clip_bpe:
+            from .clip_model import tokenize
+            names = [f"w{w}" for w in (words[:1] if self.eval_type == "image" else words)]
+            label = tokenize(names, self.clip_bpe)
+            return imgs, label, (len(label) if self.eval_type == "image" else [1] * len(names)), [f"w{words[0]}"]
         if self.eval_type == "image":
             label = self._wrap(words[0])
             return imgs, torch.tensor(label, dtype=torch.long), len(label), [f"w{words[0]}"]
@@ -195,10 +206,15 @@ class SyntheticDataModule(MultiModalDataModule):
         sos_eos = bool(self.args.get("eval_include_sos_eos", False))
         et = self.args.get("eval_type", EVAL_TYPE) or EVAL_TYPE
         n_trials = int(self.args.get("n_eval_trials", 4) or 4)
+        bpe = None
+        if self.args.get("clip_eval", CLIP_EVAL):          # CLIP's frame statistics and tokenizer for the evaluation trials (:143-155, 256-262)
+            bpe = self.args.get("clip_bpe")
+            if not bpe:
+                raise ValueError("clip_eval needs clip_bpe: the path of CLIP's bpe_simple_vocab_16e6.txt(.gz)")
         self.eval_sets = {"val": SyntheticEvalTrials(n_trials, v, seed=self.seed + 3, eval_include_sos_eos=sos_eos, raw_frames=raw,
-                                                     eval_type=et),
+                                                     eval_type=et, clip_bpe=bpe),
                           "test": SyntheticEvalTrials(n_trials, v, seed=self.seed + 4, eval_include_sos_eos=sos_eos, raw_frames=raw,
-                                                      eval_type=et)}
+                                                      eval_type=et, clip_bpe=bpe)}
 
     def set_epoch(self, epoch: int):
         self._epoch = int(epoch)

@@ -5,8 +5,13 @@ fc2 GEMM(+bias, +residual)] -> LN of the cls rows -> [B, D] fp32.  Weights are c
 the compute dtype (bf16 perf mode / fp32 parity mode).
 
 ``_Trunk`` is the one spelling of prepare_tokens and of the plain block; the frozen forward here (three routes over the blocks:
-e4m3 linears, LayerNorm-folded bf16, plain), the analysis walks of vit_maps.py and the fine-tuning forward of vit_train.py
-(``--finetune_cnn``, which keeps each block's activations) all start from it."""
+e4m3 linears, LayerNorm-folded bf16, plain), the analysis walks of vit_maps.py, the fine-tuning forward of vit_train.py
+(``--finetune_cnn``, which keeps each block's activations) and the image tower of clip_model.py all start from it.
+
+The walk reads one packed-weight dict per model.  ``_packed`` below builds the DINO ViT's; a model class with a
+``packed_weights(dt, device)`` method brings its own (clip_model.VisionTransformer).  Besides the blocks the dict says what differs
+between the two: ``pe_b`` (patch bias, or None), ``pre`` (None, or (gamma, beta, eps) of a LayerNorm applied to the assembled
+tokens: CLIP's ln_pre), ``act`` (the MLP activation) and ``proj`` (None, or an fp32 [E, D] projection of the normalised CLS rows)."""
 from __future__ import annotations
 
 import os
@@ -81,6 +86,7 @@ def _packed(model, dt, device):
                 q, sc = _quant_weight(Wg.contiguous(), device)
                 bw[name + "_q_ln"], bw[name + "_sw_ln"], bw[name + "_b8_ln"] = q, sc, b_ln
                 bw[name + "_cs_ln"] = (q.view(torch.float8_e4m3fn).double().sum(1) * sc.double()).float().contiguous()
+    w["pre"], w["act"], w["proj"] = None, H.ACT_GELU, None
     w["nw"], w["nb"], w["neps"] = model.norm.weight.detach().float().contiguous(), model.norm.bias.detach().float().contiguous(), model.norm.eps
     if torch.device(device).type == "cuda":
         torch.cuda.current_stream(device).synchronize()      # packed once, then read by every stream that runs the trunk
@@ -204,8 +210,9 @@ class _Trunk:
         self.lib = H.lib()
         self.gh, self.gw = Hh // p, Ww // p
         self.B, self.T, self.D = B, self.gh * self.gw + 1, model.embed_dim
-        self.native = self.T == model.pos_embed.shape[1] and Hh == Ww       # else: the resampled position table
-        self.w = _packed(model, self.dt, x.device)
+        pack = getattr(model, "packed_weights", None)                       # a model with its own packer (clip_model), else the DINO ViT
+        self.w = pack(self.dt, x.device) if pack is not None else _packed(model, self.dt, x.device)
+        self.native = self.T == self.w["pos"].shape[0] and Hh == Ww         # else: the resampled position table
 
     def tokens(self, work_buffers=True):
         """prepare_tokens (vit:232-247) -> self.h; ``work_buffers``: also the buffers that ``block`` overwrites."""
@@ -226,8 +233,11 @@ class _Trunk:
         H.check(self.lib.cvcl_im2col_patches(cd, H.ptr(x), H.ptr(self.cols), B, Hh, Ww, p, w["Kpad"], s), "cvcl_im2col_patches")
         tok = H.gemm(self.cols, w["pe_w"], bias=w["pe_b"])
         self.h = torch.empty(B * T, D, dtype=dt, device=dev)
-        H.check(self.lib.cvcl_vit_assemble_tokens(cd, H.ptr(tok), H.ptr(w["cls"]), H.ptr(pos), H.ptr(self.h), B, T, D, s),
+        raw = self.h if w["pre"] is None else torch.empty_like(self.h)
+        H.check(self.lib.cvcl_vit_assemble_tokens(cd, H.ptr(tok), H.ptr(w["cls"]), H.ptr(pos), H.ptr(raw), B, T, D, s),
                 "cvcl_vit_assemble_tokens")
+        if w["pre"] is not None:                                 # CLIP's ln_pre: every token row, before the first block
+            _ln(cd, raw, D, *w["pre"], self.h, False, B * T, D)
         if work_buffers:
             self.y = torch.empty_like(self.h)
             self.att = torch.empty_like(self.h)
@@ -255,7 +265,7 @@ class _Trunk:
         self.attention(bw)
         H.gemm(self.att, bw["proj_w"], out=h, bias=bw["proj_b"], residual=h)          # h = h + proj(att)   (vit:146)
         _ln(self.cd, h, D, bw["n2w"], bw["n2b"], bw["eps"], self.y, False, B * T, D)
-        H.gemm(self.y, bw["fc1_w"], out=self.mid, bias=bw["fc1_b"], act=H.ACT_GELU)
+        H.gemm(self.y, bw["fc1_w"], out=self.mid, bias=bw["fc1_b"], act=self.w["act"])
         H.gemm(self.mid, bw["fc2_w"], out=h, bias=bw["fc2_b"], residual=h)            # h = h + mlp(...)     (vit:147)
 
     def norm(self, cls_out=None):
@@ -268,6 +278,14 @@ class _Trunk:
         out = torch.empty(B, T, D, dtype=torch.float32, device=self.h.device)
         _ln(self.cd, self.h, D, w["nw"], w["nb"], w["neps"], out, True, B * T, D)
         return out
+
+    def features(self, cls_out=None):
+        """How every frozen forward ends -- the trunk's output, fp32: ``norm`` of the CLS rows [B, D] (the DINO ViT: written into
+        ``cls_out`` where given), then the model's projection where it has one ([B, E], fp32 GEMM: CLIP's ``visual.proj``)."""
+        proj = self.w["proj"]
+        cls = cls_out if proj is None and cls_out is not None else torch.empty(self.B, self.D, dtype=torch.float32, device=self.h.device)
+        self.norm(cls_out=cls)
+        return cls if proj is None else H.gemm(cls, proj, out=cls_out)
 
 
 def _blocks_e4m3(t, model):
@@ -410,4 +428,4 @@ def _vit_forward_impl(model, x: torch.Tensor, slot) -> torch.Tensor:
             if key not in ring:
                 ring[key] = torch.empty(B, D, dtype=torch.float32, device=dev)
             cls = ring[key]
-        return t.norm(cls_out=cls)
+        return t.features(cls_out=cls)
