@@ -601,6 +601,31 @@ int cvcl_cbow(const float* x, float* y, int B, int L, int E, int crange, void* s
 int cvcl_augment_frames(const void* frames, int B, int H, int W, const int32_t* crop, const float* blur_sigma, const int32_t* flip,
                         const float* mean, const float* std3, void* out, int out_h, int out_w, void* out_u8, int max_crop_h,
                         void* stream);
+
+/* ---- evaluation-time frame transform (csrc/preprocess.hip) ------------------------------------------------------------------
+ * The PIL transform every evaluation entry point of the reference runs per image, for a ragged batch in one launch:
+ *   Resize((224, 224), BICUBIC) -> ToTensor -> Normalize      multimodal_lit.py:143-147 (the `preprocess` load_model returns; demo.py),
+ *                                                             analysis_cvcl/alignment.py, embeddings.py:32-37,
+ *                                                             generate_attention_maps.py:63-67,
+ *                                                             object_categories_data_module.py:49-52, 106-109
+ *   Resize(224, BICUBIC) -> CenterCrop(224) -> ToTensor -> Normalize     multimodal_data_module.py:259-266,
+ *                                                             object_categories_data_module.py:38-45 (CLIP's transform)
+ * bit-identically to Pillow's Resample.c (bicubic a = -0.5, support 2 widened by the down-scale; coefficients normalised in double
+ * and rounded to 22 fractional bits; horizontal pass, then vertical pass, each rounded and clamped to uint8; a pass whose size does
+ * not change is the identity) and torch's fp32 (u8 / 255 - mean) / std.  Only the out_h x out_w window of the resized image is
+ * computed, which equals resize-then-crop bit for bit.
+ *   frames       uint8, device: decoded RGB frames (HWC), each of its own size, packed into one buffer of frames_bytes bytes
+ *   table        int64 [B][CVCL_PREPROCESS_TABLE_COLS], HOST: byte offset of the frame, source H, W, resized rh, rw, window
+ *                origin ct, cl inside the resized image.  Validated before anything is enqueued
+ *   table_dev    the same table in device memory (what the kernel reads)
+ *   mean, std3   3 HOST floats each
+ *   out          fp32 [B][3][out_h][out_w]; out_u8 (nullable): uint8 [B][out_h][out_w][3], the image before ToTensor
+ * Sources up to 4096 x 4096, resized sizes up to 65536, windows up to 1024 x 1024, B up to 65535.  CVCL_EINVAL (with the reason in
+ * cvcl_last_error) for a null pointer, B <= 0, a size out of range, a window that leaves the resized image, a frame that leaves the
+ * buffer, or a filter whose tables do not fit LDS.                                                                              */
+#define CVCL_PREPROCESS_TABLE_COLS 7
+int cvcl_preprocess_frames(const void* frames, int64_t frames_bytes, const int64_t* table, const void* table_dev, int B,
+                           const float* mean, const float* std3, void* out, int out_h, int out_w, void* out_u8, void* stream);
 int cvcl_token_ce_fwd(const float* logits, const int64_t* labels, float* loss, float* lse, long R, int V, int ignore_index,
                       void* stream);
 int cvcl_token_ce_bwd(const float* logits, const int64_t* labels, const float* lse, const float* d_loss, float* d_logits,

@@ -6,7 +6,8 @@ F.cosine_similarity pair per entry.  Here the frames go through ``neighbors.extr
 through one ``encode_text`` call, and the rest is a handful of launches of csrc/alignment.hip: ``class_means`` (cvcl_class_mean_f32),
 ``cosine_matrix`` (cvcl_cosine_matrix_f32), ``rsa_of_dissim_matrices`` (cvcl_triu_pearson_f32) and ``paired_distances``
 (cvcl_paired_l2_f32).  Inputs are contiguous fp32 device tensors; a CPU tensor raises, nothing falls back to torch arithmetic.
-Frames are encoded at the size they are stored in (the reference resizes to 224 x 224 first)."""
+Frames are encoded at the size they are stored in; with ``--resize`` they go through ``preprocess.DevicePreprocess`` first, the
+reference's Resize((224, 224), BICUBIC) -> ToTensor -> Normalize on the device, and may then be of any and mixed sizes."""
 from __future__ import annotations
 
 import csv
@@ -311,6 +312,15 @@ class ImageTower(torch.nn.Module):
         return self.model.encode_image(x)[0].float()
 
 
+def preprocessed_features(encoder, frames, device, batch=256):
+    """features [N, D] fp32 of a list of uint8 [H, W, 3] frames of any sizes: each batch through the reference's evaluation transform
+    on the device (preprocess.DevicePreprocess), then the encoder"""
+    from .preprocess import DevicePreprocess
+    pre = DevicePreprocess(device=device)
+    feats = [NB.extract_features(encoder, pre(frames[s:s + batch]), batch) for s in range(0, len(frames), batch)]
+    return torch.cat(feats)
+
+
 def parser():
     import argparse
     ap = argparse.ArgumentParser(description="image-text alignment of a CVCL model (analysis_cvcl/alignment.py, embeddings.py:106-118)")
@@ -323,6 +333,8 @@ def parser():
     ap.add_argument("--per_class", type=int, default=200)
     ap.add_argument("--no_replace", action="store_true", help="sample frames without replacement (embeddings.py:72)")
     ap.add_argument("--use_kitty_label", action="store_true", help='the word of category "cat" is "kitty" (alignment.py:119)')
+    ap.add_argument("--resize", action="store_true",
+                    help="resize every frame to 224 x 224 (bicubic, as the reference's transform) on the device; frames may differ in size")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--model_name", default="cvc")
     ap.add_argument("--out", default=os.path.join("results", "alignment"))
@@ -369,7 +381,7 @@ def main(args):
     else:
         if not args.eval_dir:
             raise SystemExit("--eval_dir is required (or --dataset synthetic)")
-        frames, labels, _names = NB.load_folder_u8(args.eval_dir)
+        frames, labels, _names = (NB.load_folder_list_u8 if args.resize else NB.load_folder_u8)(args.eval_dir)
     idx, picked = sample_indices(labels, args.per_class, not args.no_replace, seed=0)
     categories = sorted(set(picked))
     words = category_words(categories, args.use_kitty_label)
@@ -377,7 +389,11 @@ def main(args):
     word_ids(words, vocab)                               # an unknown word fails before the model is built
     (label_ids,) = NB._label_ids(picked)
     lit = build_model(args, dev)
-    feats = NB.extract_features(ImageTower(lit.model), frames[torch.from_numpy(idx)].to(dev), args.batch_size)
+    if args.resize:
+        chosen = [frames[int(i)].permute(1, 2, 0) if torch.is_tensor(frames) else frames[int(i)] for i in idx]     # [H, W, 3] each
+        feats = preprocessed_features(ImageTower(lit.model), chosen, dev, args.batch_size)
+    else:
+        feats = NB.extract_features(ImageTower(lit.model), frames[torch.from_numpy(idx)].to(dev), args.batch_size)
     text = encode_words(lit, words, vocab)
     res = alignment(feats, label_ids, text)
     dist = paired_distances(torch.from_numpy(res["mean_image_features"]).to(dev), text).cpu().numpy()

@@ -265,6 +265,13 @@ def normalize_frames(frames):
     return (frames - mean) / std
 
 
+def clip_preprocess(size=224, device=None):
+    """CLIP's image transform (multimodal_data_module.py:259-266; the ``clip`` package's own) on the device: Resize(size, BICUBIC) ->
+    CenterCrop(size) -> ToTensor -> Normalize(CLIP_MEAN, CLIP_STD) as a ``preprocess.DevicePreprocess``"""
+    from .preprocess import DevicePreprocess
+    return DevicePreprocess(size=size, mode="shorter_side_center_crop", mean=CLIP_MEAN, std=CLIP_STD, device=device)
+
+
 def load(path, device="cuda"):
     """``clip.load`` for a local file: a TorchScript archive (OpenAI's released ``ViT-L-14.pt``) or a plain ``state_dict`` file
     (optionally under a ``state_dict`` key).  -> (model on ``device`` in eval mode, the frame normalisation)."""

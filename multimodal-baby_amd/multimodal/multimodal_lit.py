@@ -149,15 +149,17 @@ class MultiModalLitModel(LightningModule):
     @staticmethod
     def load_model(model_name="cvcl", checkpoint_path=None):
         """Reference :134-149 downloads ``wkvong/cvcl_s_dino_resnext50_embedding`` from the HF hub; without a
-        network the checkpoint path must be given (or $CVCL_CHECKPOINT)."""
+        network the checkpoint path must be given (or $CVCL_CHECKPOINT).  The second value is the reference's ``preprocess``
+        (:143-147: Resize((224, 224), BICUBIC) -> ToTensor -> Normalize) on the device: ``preprocess.DevicePreprocess``."""
         if model_name != "cvcl":
             raise ValueError("Model name not found.")
         path = checkpoint_path or os.environ.get("CVCL_CHECKPOINT")
         if not path or not os.path.isfile(path):
             raise FileNotFoundError("no network access: pass checkpoint_path or set CVCL_CHECKPOINT to a local "
                                     "cvcl_s_dino_resnext50_embedding.ckpt")
+        from .preprocess import DevicePreprocess
         model = MultiModalLitModel.load_from_checkpoint(checkpoint_path=path)
-        return model, None
+        return model, DevicePreprocess()
 
     def encode_image(self, x):
         return self.model.encode_image(x)[0]

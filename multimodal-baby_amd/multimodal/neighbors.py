@@ -293,6 +293,19 @@ def load_folder_u8(root):
     return torch.stack(frames), [ds.classes[t] for t in ds.targets], [p for p, _ in ds.samples]
 
 
+def load_folder_list_u8(root):
+    """class-per-folder frames in ImageFolder's order, of any and mixed sizes -> (list of uint8 [H, W, 3] CPU tensors as decoded,
+    labels, file names): what ``preprocess.DevicePreprocess`` takes"""
+    from PIL import Image
+    from .linear_probe import ImageFolder
+    ds = ImageFolder(root, cache=False)
+    frames = []
+    for path, _ in ds.samples:
+        with open(path, "rb") as f:
+            frames.append(torch.from_numpy(np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8).copy()))
+    return frames, [ds.classes[t] for t in ds.targets], [p for p, _ in ds.samples]
+
+
 def synthetic_sets(seed=0, n_classes=4, train_per_class=12, eval_per_class=4, size=64):
     """A small seeded train / eval pair: blocky colour patterns plus noise.  In every class evaluation frame 0 is an exact copy of a
     training frame of its class and frame 1 a copy with +-1 on a few pixels.  Returns a dict of uint8 CPU tensors, labels, names
