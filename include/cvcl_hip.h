@@ -601,6 +601,18 @@ int cvcl_cbow(const float* x, float* y, int B, int L, int E, int crange, void* s
 int cvcl_augment_frames(const void* frames, int B, int H, int W, const int32_t* crop, const float* blur_sigma, const int32_t* flip,
                         const float* mean, const float* std3, void* out, int out_h, int out_w, void* out_u8, int max_crop_h,
                         void* stream);
+/* The same transform through a frame index (ABI v7, additive): replaces the per-item frame lookup of the reference's dataset
+ * (multimodal_saycam_data_module.py:107-122 -- pick frame_filenames[0] or a random one, Image.open(...).convert("RGB"), transform)
+ * for a dataset whose frames were decoded once into one uint8 array that lives in HBM (multimodal/frame_store.py).
+ *   store     uint8 [n_frames][H][W][3], device memory
+ *   index     int64 [B], DEVICE memory: frame b is read at store + index[b] * H * W * 3, the offset formed in 64 bits (a full
+ *             store is ~90 GB).  Values outside 0..n_frames-1 are clamped into the store on the device, so no index value can
+ *             become a read outside it; reporting a bad index is the caller's job (FrameStore.transform raises IndexError)
+ * Every other argument, the kernel and its arithmetic are cvcl_augment_frames'.  CVCL_EINVAL for what cvcl_augment_frames
+ * refuses, a null store / index, or n_frames < 1; nothing is enqueued then.                                                  */
+int cvcl_augment_frames_indexed(const void* store, int64_t n_frames, const int64_t* index, int B, int H, int W,
+                                const int32_t* crop, const float* blur_sigma, const int32_t* flip, const float* mean,
+                                const float* std3, void* out, int out_h, int out_w, void* out_u8, int max_crop_h, void* stream);
 
 /* ---- evaluation-time frame transform (csrc/preprocess.hip) ------------------------------------------------------------------
  * The PIL transform every evaluation entry point of the reference runs per image, for a ragged batch in one launch:

@@ -22,7 +22,9 @@ namespace {
 constexpr int AUG_PB = 22;                 // Pillow's PRECISION_BITS = 32 - 8 - 2
 
 struct AugDev {
-    const unsigned char* frames;           // [B][H][W][3]
+    const unsigned char* frames;           // [B][H][W][3], or the frame store [n_frames][H][W][3] when index is set
+    const long long* index;                // NULL: frame b is frames[b]; else [B] int64 rows of the store (clamped into it)
+    long long n_frames;                    // frames in the store (used only with index)
     const int* crop;                       // [B][4] top, left, h, w
     const float* sigma;                    // [B]  <= 0: no blur
     const int* flip;                       // [B]
@@ -137,8 +139,17 @@ __global__ __launch_bounds__(1024) void augment_frames_kernel(AugDev p) {
     }
     __syncthreads();
 
+    // the frame this workgroup reads: row b of a contiguous batch, or row index[b] of the store.  The row number stays 64-bit up
+    // to the byte offset (a full store is ~90 GB), and whatever value index[b] holds is clamped into the store before it
+    // becomes an address -- the host reports a bad index (multimodal/frame_store.py); the clamp keeps one from reading outside
+    size_t frame = (size_t)b;
+    if (p.index) {
+        long long ix = p.index[b];
+        ix = ix < 0 ? 0 : (ix > p.n_frames - 1 ? p.n_frames - 1 : ix);
+        frame = (size_t)ix;
+    }
     // horizontal pass: crop rows (global, HWC bytes of plane c) -> T[h][OW]
-    const unsigned char* src = p.frames + ((size_t)b * p.H + top) * p.W * 3 + (size_t)left * 3 + c;
+    const unsigned char* src = p.frames + (frame * p.H + top) * p.W * 3 + (size_t)left * 3 + c;
     const int dy = blockDim.x / OW, dx = blockDim.x - dy * OW;    // (row, column) of element i advanced without divisions
     int y = threadIdx.x / OW, xx = threadIdx.x - y * OW;
     for (int i = threadIdx.x; i < h * OW; i += blockDim.x) {
@@ -201,6 +212,36 @@ static size_t aug_lds_bytes(int t_rows, int OH, int OW, int kmax_v) {
 }
 static int aug_taps(double scale) { return (int)ceil(scale < 1.0 ? 1.0 : scale) * 2 + 1; }   // Pillow: ksize = ceil(support) * 2 + 1
 
+// validation, LDS plan and launch shared by the two entries; index == NULL: frame b is frames[b]
+static int augment_launch(const char* who, const void* frames, const int64_t* index, int64_t n_frames, int B, int H, int W,
+                          const int32_t* crop, const float* blur_sigma, const int32_t* flip, const float* mean, const float* std3,
+                          void* out, int out_h, int out_w, void* out_u8, int max_crop_h, void* stream) {
+    CVCL_CHECK_ARG(frames && crop && blur_sigma && flip && mean && std3 && out, "%s: null operand", who);
+    CVCL_CHECK_ARG(B > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0 && max_crop_h > 0 && max_crop_h <= H,
+                   "%s: bad sizes (B %d, frame %d x %d, output %d x %d, max crop height %d)", who, B, H, W, out_h, out_w, max_crop_h);
+    AugDev d;
+    d.frames = (const unsigned char*)frames; d.index = (const long long*)index; d.n_frames = (long long)n_frames;
+    d.crop = crop; d.sigma = blur_sigma; d.flip = flip;
+    d.out = (float*)out; d.out_u8 = (unsigned char*)out_u8;
+    d.B = B; d.H = H; d.W = W; d.OH = out_h; d.OW = out_w;
+    d.t_rows = max_crop_h > out_h ? max_crop_h : out_h;
+    d.kmax_h = aug_taps((double)W / out_w);                // upper bounds: the widest / tallest crop
+    d.kmax_v = aug_taps((double)max_crop_h / out_h);
+    CVCL_CHECK_ARG((size_t)out_w * (d.kmax_h + 2) * sizeof(int) <= (size_t)out_h * out_w,
+                   "%s: %d-tap horizontal filter table does not fit the plane buffer", who, d.kmax_h);
+    for (int i = 0; i < 3; ++i) { d.mean[i] = mean[i]; d.stdv[i] = std3[i]; }
+    const size_t lds = aug_lds_bytes(d.t_rows, out_h, out_w, d.kmax_v);
+    CVCL_CHECK_ARG(lds <= 160 * 1024,
+                   "%s: a %d-row crop resampled to %d x %d needs %zu bytes of LDS (limit 163840): crop boxes that tall "
+                   "are not supported by the single-pass plan", who, max_crop_h, out_h, out_w, lds);
+    static CvclLdsAttr attr_set;
+    if (const int rc = cvcl_raise_lds_limit(attr_set, (const void*)augment_frames_kernel, 160 * 1024, who)) return rc;
+    attr_set.mark();
+    hipLaunchKernelGGL(augment_frames_kernel, dim3(B * 3), dim3(1024), lds, (hipStream_t)stream, d);   // one workgroup per CU (LDS): 16 waves hide the LDS latency
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
+}
+
 // frames: uint8 [B][H][W][3] (decoded RGB frames, HWC as PIL / the image files hold them); crop: int32 [B][4] = top, left, h, w
 // (torchvision RandomResizedCrop.get_params order); blur_sigma: fp32 [B], <= 0 where RandomApply skipped the blur; flip: int32
 // [B]; mean / std: 3 host floats each; out: fp32 [B][3][out_h][out_w]; out_u8 (optional): the uint8 image before ToTensor.
@@ -208,28 +249,19 @@ static int aug_taps(double scale) { return (int)ceil(scale < 1.0 ? 1.0 : scale) 
 extern "C" int cvcl_augment_frames(const void* frames, int B, int H, int W, const int32_t* crop, const float* blur_sigma,
                                    const int32_t* flip, const float* mean, const float* std3, void* out, int out_h, int out_w,
                                    void* out_u8, int max_crop_h, void* stream) {
-    CVCL_CHECK_ARG(frames && crop && blur_sigma && flip && mean && std3 && out, "cvcl_augment_frames: null operand");
-    CVCL_CHECK_ARG(B > 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0 && max_crop_h > 0 && max_crop_h <= H,
-                   "cvcl_augment_frames: bad sizes (B %d, frame %d x %d, output %d x %d, max crop height %d)", B, H, W, out_h, out_w,
-                   max_crop_h);
-    AugDev d;
-    d.frames = (const unsigned char*)frames; d.crop = crop; d.sigma = blur_sigma; d.flip = flip;
-    d.out = (float*)out; d.out_u8 = (unsigned char*)out_u8;
-    d.B = B; d.H = H; d.W = W; d.OH = out_h; d.OW = out_w;
-    d.t_rows = max_crop_h > out_h ? max_crop_h : out_h;
-    d.kmax_h = aug_taps((double)W / out_w);                // upper bounds: the widest / tallest crop
-    d.kmax_v = aug_taps((double)max_crop_h / out_h);
-    CVCL_CHECK_ARG((size_t)out_w * (d.kmax_h + 2) * sizeof(int) <= (size_t)out_h * out_w,
-                   "cvcl_augment_frames: %d-tap horizontal filter table does not fit the plane buffer", d.kmax_h);
-    for (int i = 0; i < 3; ++i) { d.mean[i] = mean[i]; d.stdv[i] = std3[i]; }
-    const size_t lds = aug_lds_bytes(d.t_rows, out_h, out_w, d.kmax_v);
-    CVCL_CHECK_ARG(lds <= 160 * 1024,
-                   "cvcl_augment_frames: a %d-row crop resampled to %d x %d needs %zu bytes of LDS (limit 163840): crop boxes that tall "
-                   "are not supported by the single-pass plan", max_crop_h, out_h, out_w, lds);
-    static CvclLdsAttr attr_set;
-    if (const int rc = cvcl_raise_lds_limit(attr_set, (const void*)augment_frames_kernel, 160 * 1024, "cvcl_augment_frames")) return rc;
-    attr_set.mark();
-    hipLaunchKernelGGL(augment_frames_kernel, dim3(B * 3), dim3(1024), lds, (hipStream_t)stream, d);   // one workgroup per CU (LDS): 16 waves hide the LDS latency
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
+    return augment_launch("cvcl_augment_frames", frames, nullptr, 0, B, H, W, crop, blur_sigma, flip, mean, std3, out, out_h, out_w,
+                          out_u8, max_crop_h, stream);
+}
+
+// The same launch reading frame b at store + index[b] * H * W * 3: store is the HBM-resident uint8 [n_frames][H][W][3] array of
+// every decoded frame of the dataset (multimodal/frame_store.py), index a DEVICE int64 [B].  Batches travel as indices; no
+// gathered copy of the frames is made.
+extern "C" int cvcl_augment_frames_indexed(const void* store, int64_t n_frames, const int64_t* index, int B, int H, int W,
+                                           const int32_t* crop, const float* blur_sigma, const int32_t* flip, const float* mean,
+                                           const float* std3, void* out, int out_h, int out_w, void* out_u8, int max_crop_h,
+                                           void* stream) {
+    CVCL_CHECK_ARG(store && index, "cvcl_augment_frames_indexed: null store / index");
+    CVCL_CHECK_ARG(n_frames >= 1, "cvcl_augment_frames_indexed: n_frames %lld < 1", (long long)n_frames);
+    return augment_launch("cvcl_augment_frames_indexed", store, index, n_frames, B, H, W, crop, blur_sigma, flip, mean, std3, out,
+                          out_h, out_w, out_u8, max_crop_h, stream);
 }

@@ -166,6 +166,7 @@ SIGNATURES = {
     "cvcl_seq_reverse": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "cvcl_scale_add_f32": (_I, [_P, _P, C.c_float, _P, C.c_long, _P]),
     "cvcl_augment_frames": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P]),
+    "cvcl_augment_frames_indexed": (_I, [_P, C.c_int64, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P]),
     "cvcl_preprocess_frames": (_I, [_P, C.c_int64, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "cvcl_cbow": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "cvcl_token_ce_fwd": (_I, [_P, _P, _P, _P, C.c_long, _I, _I, _P]),

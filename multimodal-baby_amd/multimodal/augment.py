@@ -148,18 +148,23 @@ class DeviceFrameAugment:
             flip.append(1 if torch.rand(1, generator=g).item() < self.flip_p else 0)
         return FrameParams(crop, sigma, flip)
 
+    @staticmethod
+    def check_params(params, n, height, width):
+        """One parameter row per frame and every crop box inside the height x width frame; returns the tallest crop."""
+        if len(params) != n:
+            raise ValueError(f"{len(params)} parameter rows for {n} frames")
+        c = params.crop
+        if bool(((c[:, 2] < 1) | (c[:, 3] < 1) | (c[:, 0] < 0) | (c[:, 1] < 0) | (c[:, 0] + c[:, 2] > height) | (c[:, 1] + c[:, 3] > width)).any()):
+            raise ValueError("crop box outside the frame")
+        return int(c[:, 2].max())
+
     def __call__(self, frames, params=None, return_uint8=False):
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
             raise H.CvclError(f"expected uint8 [B, H, W, 3] frames, got {tuple(frames.shape)} {frames.dtype}")
         B, Hh, Ww, _ = frames.shape
         if params is None:
             params = self.sample_params(B, Hh, Ww)
-        if len(params) != B:
-            raise ValueError(f"{len(params)} parameter rows for {B} frames")
-        c = params.crop
-        if bool(((c[:, 2] < 1) | (c[:, 3] < 1) | (c[:, 0] < 0) | (c[:, 1] < 0) | (c[:, 0] + c[:, 2] > Hh) | (c[:, 1] + c[:, 3] > Ww)).any()):
-            raise ValueError("crop box outside the frame")
-        max_h = int(c[:, 2].max())
+        max_h = self.check_params(params, B, Hh, Ww)
         frames = frames.contiguous()
         dev = frames.device
         crop_d, sigma_d, flip_d = (t.to(dev, non_blocking=True) for t in (params.crop, params.sigma, params.flip))

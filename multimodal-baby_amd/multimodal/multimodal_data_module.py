@@ -1,14 +1,21 @@
-"""Batch contract of the reference data modules + a synthetic data module.
+"""Batch contract of the reference data modules, its evaluation-trial datasets and loaders, + a synthetic data module.
 
-Mirrors the constants, ``multiModalDataset_collate_fn`` and CLI flags of the reference
-(multimodal/multimodal_data_module.py:26-54, 98-109, 283-311; multimodal_saycam_data_module.py:93-124,
-142-150).  The SAYCam / COCO loaders themselves read a private dataset from hard-coded cluster paths and
-are out of scope; ``SyntheticDataModule`` produces batches of the same shape."""
+Mirrors the constants, ``read_vocab`` / ``load_data``, ``multiModalDataset_collate_fn``, the two evaluation datasets, setup, the
+data loaders and the CLI flags of the reference (multimodal/multimodal_data_module.py:26-69, 98-214, 283-427).  The SAYCam
+module on top of it is multimodal_saycam_data_module.py: it reads a dataset directory in the reference's layout, given by
+``--data_dir`` / ``$CVCL_DATA_DIR`` (the reference's data is private, its format is not).  The COCO and object-categories
+modules are not built; ``SyntheticDataModule`` produces batches of the same shape without any files.
+
+A frame reaches the model by one of three paths (``FrameSource``): decoded and transformed in the loader workers (default),
+decoded in the workers and transformed on the device (``--device_frames``), or never decoded at run time at all -- the
+datasets return the frame's row in the HBM-resident frame store and the transform kernel reads it through that index
+(``--frame_store PATH``, multimodal/frame_store.py)."""
 from __future__ import annotations
 
 import json
 import os
 
+import numpy as np
 import torch
 from torch.nn.utils.rnn import pad_sequence
 
@@ -37,6 +44,131 @@ def read_vocab(vocab_filename=VOCAB_FILENAME):
         return json.load(f)
 
 
+def load_data(filename):
+    with open(filename) as f:
+        return json.load(f)["data"]
+
+
+def data_dir_from(args):
+    """The dataset root: ``--data_dir``, else $CVCL_DATA_DIR, else None (there is no built-in path)."""
+    d = args.get("data_dir") if isinstance(args, dict) else getattr(args, "data_dir", None)
+    return d or os.environ.get("CVCL_DATA_DIR") or None
+
+
+class HostFrameTransform:
+    """The reference's per-frame transform on a PIL image in a loader worker (torchvision is not a dependency, so ToTensor and
+    Normalize are spelled out): ``augment_frames`` draws the reference's crop / blur / flip per frame in its order
+    (``DeviceFrameAugment.sample_params_sequential``) and applies them with Pillow, then (u8 / 255 - mean) / std in fp32,
+    CHW.  Without it this is ``base_transform`` (:271-280)."""
+
+    def __init__(self, augment_frames=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, size=(IMAGE_H, IMAGE_W)):
+        self.augment_frames = bool(augment_frames)
+        self.mean = torch.tensor(mean, dtype=torch.float32).view(3, 1, 1)
+        self.std = torch.tensor(std, dtype=torch.float32).view(3, 1, 1)
+        self.size = tuple(size)
+        self._draws = None
+
+    def __call__(self, img):
+        if self.augment_frames:
+            from PIL import Image, ImageFilter
+            if self._draws is None:
+                from .augment import DeviceFrameAugment          # only its host-side draws are used here
+                self._draws = DeviceFrameAugment(augment_frames=True, size=self.size)
+            p = self._draws.sample_params_sequential(1, img.height, img.width)
+            top, left, h, w = (int(v) for v in p.crop[0])
+            img = img.crop((left, top, left + w, top + h)).resize((self.size[1], self.size[0]), Image.BILINEAR)
+            if float(p.sigma[0]) > 0:
+                img = img.filter(ImageFilter.GaussianBlur(radius=float(p.sigma[0])))
+            if int(p.flip[0]):
+                img = img.transpose(Image.FLIP_LEFT_RIGHT)
+        x = torch.from_numpy(np.array(img, dtype=np.uint8)).permute(2, 0, 1).float().div(255.0)
+        return x.sub_(self.mean).div_(self.std)
+
+
+class FrameSource:
+    """How a dataset turns a frame key (frame_store.frame_key) into the image of its item:
+    ``host``  PIL decode + the dataset's transform -> fp32 [3, H, W]
+    ``uint8`` PIL decode -> uint8 [H, W, 3]; the transform runs on the device after the batch transfer
+    ``index`` no decode: the frame's row in the frame store as an int64 scalar (``rows``: key -> row)."""
+
+    def __init__(self, data_dir, mode="host", rows=None):
+        if mode not in ("host", "uint8", "index"):
+            raise ValueError(f"unknown frame mode {mode!r}")
+        if mode == "index" and rows is None:
+            raise ValueError("frame mode 'index' needs the store's key -> row map")
+        self.data_dir, self.mode, self.rows = (str(data_dir) if data_dir is not None else None), mode, rows
+
+    def resolve(self, keys):
+        """Every key of a split, checked once when its dataset is built: under ``index`` a frame that is not in the store stops the
+        run here (KeyError naming it), not in the middle of an epoch."""
+        if self.mode == "index":
+            for k in keys:
+                if k not in self.rows:
+                    raise KeyError(f"frame {k!r} is not in the frame store")
+
+    def path(self, key):
+        return key if os.path.isabs(key) or self.data_dir is None else os.path.join(self.data_dir, key)
+
+    def decode(self, key):
+        from PIL import Image
+        return Image.open(self.path(key)).convert("RGB")
+
+    def __call__(self, key, transform=None):
+        if self.mode == "index":
+            return torch.tensor(int(self.rows[key]), dtype=torch.int64)
+        img = self.decode(key)
+        if self.mode == "uint8":
+            return torch.from_numpy(np.array(img, dtype=np.uint8))
+        return transform(img) if transform is not None else img
+
+
+def _eval_label(vocab, word, sos_eos):
+    label = [vocab[word]]
+    return [SOS_TOKEN_ID] + label + [EOS_TOKEN_ID] if sos_eos else label      # [<sos>, label, <eos>] to match LM training
+
+
+class LabeledSEvalDataset(torch.utils.data.Dataset):
+    """One target word and its referents (reference :112-160): item = (imgs [n, 3, H, W] with the target image first, label ids
+    [L], L, [raw target category]).  Under the ``uint8`` / ``index`` frame modes imgs is uint8 [n, H, W, 3] / int64 [n].  The CLIP
+    branch of the reference is not built."""
+
+    def __init__(self, data, vocab, transform, eval_include_sos_eos=False, frames=None):
+        self.data, self.vocab, self.transform, self.eval_include_sos_eos = data, vocab, transform, eval_include_sos_eos
+        self.frames = frames if frames is not None else FrameSource(None)
+        self.frames.resolve(k for t in data for k in [t["target_img_filename"]] + list(t["foil_img_filenames"]))
+
+    def __getitem__(self, idx):
+        trial = self.data[idx]
+        names = [trial["target_img_filename"]] + list(trial["foil_img_filenames"])
+        imgs = torch.stack([self.frames(n, self.transform) for n in names], 0)
+        raw_label = trial["target_category"]
+        label = _eval_label(self.vocab, raw_label, self.eval_include_sos_eos)
+        return imgs, torch.LongTensor(label), len(label), [raw_label]
+
+    def __len__(self):
+        return len(self.data)
+
+
+class LabeledSTextEvalDataset(torch.utils.data.Dataset):
+    """One referent and several words (reference :163-214): item = (img [1, 3, H, W], label ids [n, L] with the target category
+    first, [n lengths], [raw target category])."""
+
+    def __init__(self, data, vocab, transform, eval_include_sos_eos=False, frames=None):
+        self.data, self.vocab, self.transform, self.eval_include_sos_eos = data, vocab, transform, eval_include_sos_eos
+        self.frames = frames if frames is not None else FrameSource(None)
+        self.frames.resolve(t["target_img_filename"] for t in data)
+
+    def __getitem__(self, idx):
+        trial = self.data[idx]
+        img = self.frames(trial["target_img_filename"], self.transform).unsqueeze(0)
+        raw_target = trial["target_category"]
+        labels = [_eval_label(self.vocab, w, self.eval_include_sos_eos) for w in [raw_target] + list(trial["foil_categories"])]
+        return img, torch.LongTensor(labels), [len(l) for l in labels], [raw_target]
+
+    def __len__(self):
+        return len(self.data)
+
+
 def multiModalDataset_collate_fn(batch):
     """(img, idxs, len, raw) items -> (img [B,3,H,W], idxs [B,Lmax<=25] pad 0, len [B] int64, raw list)."""
     img, idxs, length, raw = zip(*batch)
@@ -62,22 +194,41 @@ class MultiModalDataModule(LightningDataModule):
         # transform) runs on the device after the batch transfer (multimodal/augment.py) instead of per frame in the workers
         self.device_frames = bool(self.args.get("device_frames", False))
         self._frame_transforms = None
+        self.eval_include_sos_eos = self.args.get("eval_include_sos_eos", EVAL_INCLUDE_SOS_EOS)
+        self.test_while_val = self.args.get("test_while_val", TEST_WHILE_VAL)
+        self.eval_type = self.args.get("eval_type", EVAL_TYPE) or EVAL_TYPE
+        self.eval_metadata_filename = self.args.get("eval_metadata_filename", "eval_dev.json")
+        self.data_dir = data_dir_from(self.args)
+        # --frame_store PATH: the datasets yield frame indices; the store itself is loaded into HBM at setup()
+        self.frame_store_path = self.args.get("frame_store") or None
+        self.frame_store = None
+        # the host path's transforms (:244-280): the training one draws the augmentation when asked to, val / test keep the base one
+        self.transform = HostFrameTransform(self.augment_frames)
+        self.base_transform = HostFrameTransform(False)
 
     def on_after_batch_transfer(self, batch, dataloader_idx=0, training=True):
         """Lightning's hook of the same name: uint8 frame batches [B, H, W, 3] (or evaluation trials [B, n, H, W, 3]) become
         normalised fp32 [.., 3, 224, 224] tensors on the device; the training transform only while training (the reference
         keeps ``base_transform`` for val / test, :271-275).  Batches that already hold float images pass through."""
         img = batch[0] if isinstance(batch, (list, tuple)) and len(batch) > 0 else None
-        if not torch.is_tensor(img) or img.dtype != torch.uint8:
+        by_index = torch.is_tensor(img) and img.dtype == torch.int64 and self.frame_store is not None
+        if not by_index and (not torch.is_tensor(img) or img.dtype != torch.uint8):
             return batch
         from .augment import DeviceFrameAugment
         if self._frame_transforms is None:
             self._frame_transforms = {True: DeviceFrameAugment(augment_frames=self.augment_frames),
                                       False: DeviceFrameAugment(augment_frames=False)}
-        tf = self._frame_transforms[bool(training)]
-        lead = img.shape[:-3]
-        out = tf(img.reshape(-1, *img.shape[-3:]))
+        tf = self._frame_transforms[self._uses_training_transform(dataloader_idx, bool(training))]
+        if by_index:                                       # frame rows [B] or trials [B, n]: read through the index, no gathered copy
+            lead = img.shape
+            out = self.frame_store._launch(img.reshape(-1).to(self.frame_store.device, non_blocking=True), tf)
+        else:
+            lead = img.shape[:-3]
+            out = tf(img.reshape(-1, *img.shape[-3:]))
         return type(batch)((out.reshape(*lead, *out.shape[1:]),) + tuple(batch[1:]))
+
+    def _uses_training_transform(self, dataloader_idx, training):
+        return training
 
     @staticmethod
     def add_to_argparse(parser):
@@ -93,6 +244,11 @@ class MultiModalDataModule(LightningDataModule):
         parser.add_argument("--eval_type", type=str, default=EVAL_TYPE, choices=["image", "text"])
         parser.add_argument("--eval_metadata_filename", type=str, default="eval_filtered_dev.json")
         parser.add_argument("--clip_eval", action="store_true")
+        parser.add_argument("--data_dir", type=str, default=None, metavar="DIR",
+                            help="dataset root in the reference's layout (train.json, val.json, test.json, vocab.json, train_5fps/, "
+                                 "eval_*.json); default: $CVCL_DATA_DIR")
+        parser.add_argument("--frame_store", type=str, default=None, metavar="PATH",
+                            help="a store written by tools/pack_frames.py: loaded into HBM at start-up; batches carry frame indices")
         return parser
 
     @staticmethod
@@ -104,6 +260,64 @@ class MultiModalDataModule(LightningDataModule):
 
     def read_vocab(self):
         return read_vocab()
+
+    # ---- the reference's setup and loaders (:318-427), for the modules that read files ----
+    def prepare_data(self, *args, **kwargs):
+        pass                                               # the reference's download / extraction / filtering steps are not built
+
+    def frame_source(self):
+        mode = "index" if self.frame_store_path else ("uint8" if self.device_frames else "host")
+        rows = None
+        if mode == "index":
+            from .frame_store import FrameStore
+            if self.frame_store is None:
+                device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+                self.frame_store = FrameStore.load(self.frame_store_path, device)
+            rows = self.frame_store.index
+        return FrameSource(self.data_dir, mode, rows)
+
+    def setup(self, *args, **kwargs):
+        vocab = self.read_vocab()
+        self.frames = self.frame_source()
+        self.datasets = self.create_datasets(vocab)
+        self.eval_datasets = self.create_eval_datasets(vocab)
+
+    def create_datasets(self, vocab):
+        raise NotImplementedError
+
+    def create_eval_datasets(self, vocab):
+        """:339-360.  The test split's file is the dev file's name with "dev" replaced by "test".  As in the reference the trial
+        datasets get ``self.transform`` -- the TRAINING transform, augmentation included when --augment_frames is on -- not
+        ``self.base_transform`` (eval.py switches augment_frames off before it builds the module)."""
+        eval_datasets = {}
+        for split, name in (("val", self.eval_metadata_filename), ("test", self.eval_metadata_filename.replace("dev", "test"))):
+            data = load_data(os.path.join(self.data_dir, name))
+            cls = LabeledSEvalDataset if self.eval_type == "image" else LabeledSTextEvalDataset
+            eval_datasets[split] = cls(data, vocab, self.transform, self.eval_include_sos_eos, frames=self.frames)
+        return eval_datasets
+
+    def _loader(self, dataset, batch_size, shuffle=False, drop_last=False):
+        workers = 0 if self.frames.mode == "index" else self.num_workers       # an index item is a dictionary lookup: nothing to decode
+        return torch.utils.data.DataLoader(dataset, collate_fn=multiModalDataset_collate_fn, shuffle=shuffle, batch_size=batch_size,
+                                           drop_last=drop_last, num_workers=workers, pin_memory=False)
+
+    def train_dataloader(self, batch_size=None, shuffle=True, drop_last=None):
+        return self._loader(self.datasets["train"], self.batch_size if batch_size is None else batch_size, shuffle,
+                            self.drop_last if drop_last is None else drop_last)
+
+    def val_test_dataloader(self, dataset, eval_dataset, batch_size=None, shuffle=False, drop_last=False):
+        """[pair batches at val_batch_size, one evaluation trial per batch] (:378-403)"""
+        return [self._loader(dataset, self.val_batch_size if batch_size is None else batch_size, shuffle, drop_last),
+                self._loader(eval_dataset, 1, shuffle)]
+
+    def val_dataloader(self, batch_size=None, shuffle=False, drop_last=False):
+        loaders = self.val_test_dataloader(self.datasets["val"], self.eval_datasets["val"], batch_size, shuffle, drop_last)
+        if self.test_while_val:
+            loaders += self.test_dataloader(batch_size=batch_size, shuffle=shuffle, drop_last=drop_last)
+        return loaders
+
+    def test_dataloader(self, batch_size=None, shuffle=False, drop_last=False):
+        return self.val_test_dataloader(self.datasets["test"], self.eval_datasets["test"], batch_size, shuffle, drop_last)
 
 
 class SyntheticPairs(torch.utils.data.Dataset):

@@ -2,6 +2,8 @@
 
     python train.py --dataset synthetic --batch_size=8 --gpus=1 --checkpoint_callback=False --logger=False \
         --fast_dev_run --text_encoder=embedding --lambda_lm 0 --optimize_unused          # = run.sh:12 on synthetic data
+    python train.py --dataset saycam --data_dir DIR [--frame_store PATH] [--multiple_frames] [--shuffle_utterances] \
+        [--augment_frames] ...                    # a dataset directory in the reference's layout (multimodal_saycam_data_module.py)
 
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train.py ... --gpus N`` (one process per GPU,
 RCCL over xGMI; see multimodal/parallel.py)."""
@@ -14,7 +16,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "mul
 
 from multimodal import lightning as pl                                            # noqa: E402
 from multimodal.multimodal import LanguageModel, MultiModalModel, TextEncoder, VisionEncoder   # noqa: E402
-from multimodal.multimodal_data_module import MultiModalDataModule, SyntheticDataModule        # noqa: E402
+from multimodal.multimodal_data_module import MultiModalDataModule, SyntheticDataModule, data_dir_from   # noqa: E402
+from multimodal.multimodal_saycam_data_module import MultiModalSAYCamDataModule   # noqa: E402
 from multimodal.multimodal_lit import MultiModalLitModel                          # noqa: E402
 
 
@@ -47,10 +50,15 @@ def main(argv=None):
     if str(args.resume_ckpt) == "last":
         args.resume_ckpt = ckpt_dir / "last.ckpt"
     pl.seed_everything(args.seed)
-    if args.dataset != "synthetic":
+    if args.dataset == "saycam" and data_dir_from(args):
+        data = MultiModalSAYCamDataModule(args)
+    elif args.dataset != "synthetic":
         raise SystemExit(f"--dataset {args.dataset} reads a private dataset from hard-coded cluster paths in the "
-                         "reference and is not available here; use --dataset synthetic")
-    data = SyntheticDataModule(args)
+                         "reference and is not available here; use --dataset synthetic"
+                         + (", or give --dataset saycam a dataset directory in the reference's layout with --data_dir DIR "
+                            "(or $CVCL_DATA_DIR)" if args.dataset == "saycam" else ""))
+    else:
+        data = SyntheticDataModule(args)
     vocab = data.read_vocab()
     vision_encoder = VisionEncoder(args=args)
     text_encoder = TextEncoder(vocab, image_feature_map_dim=vision_encoder.last_cnn_out_dim, args=args)
