@@ -401,6 +401,46 @@ def ptr(t: torch.Tensor | None, dtype=None) -> int | None:
     return t.data_ptr()
 
 
+def row_strided(t: torch.Tensor) -> bool:
+    """Is ``t`` a 2-D view a kernel can read as (pointer, leading dimension): unit column stride, rows that do not overlap?"""
+    return t.dim() == 2 and (t.is_contiguous() or (t.stride(1) == 1 and t.stride(0) >= t.shape[1]))
+
+
+def _matrix(t: torch.Tensor, dtype=None) -> tuple[int, int, int]:
+    """(pointer, leading dimension, rows) of a matrix operand: a contiguous tensor of any rank is [numel / shape[-1], shape[-1]];
+    anything else must be a row-strided 2-D view.  (One flat function: it runs three times per gemm of a launch-bound loop.)"""
+    if not t.is_cuda:
+        raise CvclError("the CVCL HIP path needs device tensors (got a CPU tensor); there is no CPU fallback")
+    if dtype is not None and t.dtype != dtype:
+        raise CvclError(f"expected dtype {dtype}, got {t.dtype}")
+    shape = t.shape
+    if t.is_contiguous():
+        return t.data_ptr(), shape[-1], t.numel() // shape[-1]
+    stride = t.stride()
+    if len(shape) == 2 and stride[1] == 1 and stride[0] >= shape[1]:
+        return t.data_ptr(), stride[0], shape[0]
+    raise CvclError(f"expected a contiguous tensor or a 2-D view with unit column stride and non-overlapping rows, got shape "
+                    f"{tuple(shape)} strides {stride}")
+
+
+def rows(t: torch.Tensor, dtype=None) -> tuple[int, int]:
+    """(device pointer, leading dimension in elements) of a row-strided 2-D view -- a block of rows and / or columns of a wider
+    matrix, read or written in place.  The pointer is the view's own first element (its storage offset included); a single row
+    counts as shape[1] wide.  Loud failure for anything else, as ``ptr``."""
+    p, ld, _ = _matrix(t, dtype)
+    if t.dim() != 2:
+        raise CvclError(f"expected a 2-D view, got shape {tuple(t.shape)}")
+    return p, ld
+
+
+def _product(t: torch.Tensor, dtype, M: int, N: int, what: str) -> tuple[int, int]:
+    """(pointer, leading dimension) of gemm's ``out`` / ``residual``: ``dtype``, at least M rows, N columns."""
+    p, ld, m = _matrix(t, dtype)
+    if m < M or t.shape[-1] != N:
+        raise CvclError(f"gemm {what}: {tuple(t.shape)} does not hold the [{M}, {N}] product")
+    return p, ld
+
+
 def torch_dtype(dt: int):
     return torch.float32 if dt == F32 else torch.bfloat16
 
@@ -416,38 +456,53 @@ def cvcl_dtype(t: torch.dtype) -> int:
 def gemm(A, W, out=None, *, bias=None, act=ACT_NONE, residual=None, a_scale=None, a_shift=None, a_relu=False,
          exp_scale=None, gather=None, stats=None, M=None, lda=None, pre_out=None, gelu_grad_of=None, centre=None,
          ln_stats=None, ln_colsum=None, row_part=None, query_ln=False, a_trans=False, w_trans=False, a_rowsum=None,
-         split=False, stats_acc=None):
+         split=False, stats_acc=None, stream=None):
     """C = act(A' W^T * exp(*exp_scale) + bias) (+ residual).  A [M,K], W [N,K] row-major, same dtype.
     ``centre`` [N] f32 (convolution epilogues): C = round(A' W^T - centre), statistics of that (cvcl_hip.h "Centred storage").
     fp32 only: ``a_trans`` -- A is given as [K, M]; ``w_trans`` -- W is given as [K, N] (the operands of a gradient GEMM as they
-    lie, no transposed copies); ``a_rowsum`` [M] f32 (with a_trans) receives sum_k A'[m][k] (the bias gradient beside dW)."""
-    dt = cvcl_dtype(A.dtype)
-    if W.dtype != A.dtype:
+    lie, no transposed copies); ``a_rowsum`` [M] f32 (with a_trans) receives sum_k A'[m][k] (the bias gradient beside dW).
+    A (without a_trans), ``residual`` and ``out`` are contiguous tensors of any rank, read as [numel / shape[-1], shape[-1]], or
+    row-strided 2-D views (``rows``: a step's rows of a [B, L, N] sequence, a block of rows of a larger buffer), whose row stride is
+    the leading dimension; W is contiguous.  ``out`` has A's dtype, at least M rows and N columns, ``residual`` likewise.
+    ``stream``: ``stream_ptr()`` resolved by the caller, once for a loop of calls (the current stream otherwise)."""
+    adt = A.dtype
+    dt = cvcl_dtype(adt)
+    if W.dtype != adt:
         raise CvclError("gemm operands must share a dtype")
-    K, N = (W.shape[0], W.shape[1]) if w_trans else (W.shape[1], W.shape[0])
     ldw = W.shape[1]
+    K, N = (W.shape[0], ldw) if w_trans else (ldw, W.shape[0])
     if a_trans:
         if A.dim() != 2 or A.shape[0] != K or M is not None or lda is not None:
             raise CvclError("a_trans: A must be a [K, M] matrix")
-        M, lda = A.shape[1], A.shape[1]
-    if M is None:
-        M = A.numel() // A.shape[-1]
-    lda = lda if lda is not None else A.shape[-1]
+        pA, M, lda = ptr(A), A.shape[1], A.shape[1]
+    else:
+        pA, ld, m = _matrix(A)
+        M, lda = (m if M is None else M), (ld if lda is None else lda)
     if out is None:
-        out = torch.empty((M, N), dtype=A.dtype, device=A.device)
+        out = torch.empty((M, N), dtype=adt, device=A.device)
+    # (a field that is not set stays 0 / NULL: the block is zero-initialised, and only what the call uses is written -- this
+    # function sits in the per-step loops of the LSTM paths, where the host is what bounds the step)
     a = GemmArgs()
-    a.A, a.W, a.C = ptr(A), ptr(W), ptr(out)
-    a.M, a.N, a.K, a.lda, a.ldw, a.ldc = M, N, K, lda, ldw, N
-    a.a_trans, a.w_trans, a.a_rowsum = int(a_trans), int(w_trans), ptr(a_rowsum, torch.float32)
-    a.f32_split = int(bool(split) and dt == F32)           # (fp32 operands on the bf16 MFMA, hi / lo split: cvcl_hip.h)
-    a.a_scale, a.a_shift, a.a_relu = ptr(a_scale, torch.float32), ptr(a_shift, torch.float32), int(a_relu)
+    a.A, a.W, (a.C, a.ldc) = pA, ptr(W), _product(out, adt, M, N, "out")
+    a.M, a.N, a.K, a.lda, a.ldw = M, N, K, lda, ldw
+    if a_trans or w_trans:
+        a.a_trans, a.w_trans = int(a_trans), int(w_trans)
+    if a_rowsum is not None:
+        a.a_rowsum = ptr(a_rowsum, torch.float32)
+    if split and dt == F32:                                # (fp32 operands on the bf16 MFMA, hi / lo split: cvcl_hip.h)
+        a.f32_split = 1
+    if a_scale is not None or a_shift is not None or a_relu:
+        a.a_scale, a.a_shift, a.a_relu = ptr(a_scale, torch.float32), ptr(a_shift, torch.float32), int(a_relu)
     if gather is not None:
         a.gather_ho, a.gather_wo, a.gather_hi, a.gather_wi, a.gather_stride = gather
-    a.exp_scale, a.bias, a.act = ptr(exp_scale, torch.float32), ptr(bias, torch.float32), act
+    if exp_scale is not None:
+        a.exp_scale = ptr(exp_scale, torch.float32)
+    if bias is not None:
+        a.bias = ptr(bias, torch.float32)
+    if act:
+        a.act = act
     if residual is not None:
-        if residual.dtype != A.dtype:
-            raise CvclError("residual dtype mismatch")
-        a.R, a.ldr = ptr(residual), N
+        a.R, a.ldr = _product(residual, adt, M, N, "residual")
     if stats is not None:
         a.stats, a.stats_rows = ptr(stats, torch.float32), stats.shape[0]
     if stats_acc is not None:                             # int64 [8, 2, N], zeroed by the caller: statistics ACCUMULATED (cvcl_hip.h)
@@ -455,15 +510,17 @@ def gemm(A, W, out=None, *, bias=None, act=ACT_NONE, residual=None, a_scale=None
             raise CvclError("stats_acc: a contiguous int64 [8, 2, N] accumulator (and no stats rows)")
         a.stats, a.stats_rows = stats_acc.data_ptr(), STATS_ACCUMULATE
     if pre_out is not None:                               # act = GELU: also keep the pre-activation
-        a.C_pre = ptr(pre_out, A.dtype)
+        a.C_pre = ptr(pre_out, adt)
     if gelu_grad_of is not None:                          # C = (A W^T) * gelu'(gelu_grad_of)
-        a.G, a.ldg = ptr(gelu_grad_of, A.dtype), N
-    a.centre = ptr(centre, torch.float32)
+        a.G, a.ldg = ptr(gelu_grad_of, adt), N
+    if centre is not None:
+        a.centre = ptr(centre, torch.float32)
     # LayerNorm folded into the linear (cvcl_hip.h): consumer (ln_stats [M + (M & 1), 2], ln_colsum [N], bias = folded) / producer (row_part)
-    a.ln_stats, a.ln_colsum, a.row_part = ptr(ln_stats, torch.float32), ptr(ln_colsum, torch.float32), ptr(row_part, torch.float32)
+    if ln_stats is not None or ln_colsum is not None or row_part is not None:
+        a.ln_stats, a.ln_colsum, a.row_part = ptr(ln_stats, torch.float32), ptr(ln_colsum, torch.float32), ptr(row_part, torch.float32)
     if query_ln:                                          # would cvcl_gemm honour ln_stats / row_part for these arguments?
         return bool(lib().cvcl_gemm_ln_supported(C.byref(a)))
-    check(lib().cvcl_gemm(dt, C.byref(a), stream_ptr()), "cvcl_gemm")
+    check(lib().cvcl_gemm(dt, C.byref(a), stream_ptr() if stream is None else stream), "cvcl_gemm")
     return out
 
 

@@ -75,7 +75,8 @@ def gradCAM_with_act_and_grad(act: torch.Tensor, grad: torch.Tensor) -> torch.Te
     N, C, h, w = act.shape
     fa, fg = _nhwc_flag(act), _nhwc_flag(grad)
     cam = torch.empty(N, 1, h, w, dtype=torch.float32, device=act.device)
-    H.check(H.lib().cvcl_gradcam_act_grad(H.cvcl_dtype(act.dtype), act.data_ptr(), fa, H.cvcl_dtype(grad.dtype), grad.data_ptr(), fg,
+    p_act, p_grad = (H.ptr(t.permute(0, 2, 3, 1) if nhwc else t) for t, nhwc in ((act, fa), (grad, fg)))
+    H.check(H.lib().cvcl_gradcam_act_grad(H.cvcl_dtype(act.dtype), p_act, fa, H.cvcl_dtype(grad.dtype), p_grad, fg,
                                           H.ptr(cam), N, C, h * w, H.stream_ptr()), "cvcl_gradcam_act_grad")
     return cam
 
@@ -183,7 +184,7 @@ def gradcam_from_features(fmap, features, fc_weight, targets, normalize_features
         S = H.gemm(y, T)                                       # [N, M] = n^ . t
         Q = H.gemm(y, W, w_trans=True)                         # [N, C] = n^ W
     cam = torch.empty(*prefix, h, w, dtype=torch.float32, device=f.device)
-    H.check(H.lib().cvcl_gradcam_pairs(H.cvcl_dtype(fmap.dtype), rows.data_ptr(), N, h * w, C, H.ptr(P), M, mode, k, H.ptr(Q), H.ptr(S),
+    H.check(H.lib().cvcl_gradcam_pairs(H.cvcl_dtype(fmap.dtype), H.ptr(rows), N, h * w, C, H.ptr(P), M, mode, k, H.ptr(Q), H.ptr(S),
                                        H.ptr(norm), eps, H.ptr(cam), H.stream_ptr()), "cvcl_gradcam_pairs")
     if resize is not False and resize is not None:
         if resize is True:
@@ -262,7 +263,9 @@ def vit_attention_rollout(vision_model, x, size=None, head_fusion="mean", start_
 
 # ---- per-word maps of the captioning language model ----------------------------------------------------------------------
 
-MAX_CAPTION_LEN = 32                                       # the LSTM path's limit (text_train.transformer_text_train, ops.lstm_text)
+# caption_seed_targets' own bound on the caption length: the one text_train.transformer_text_train puts on utterances.  The LSTM
+# functions it runs on (ops.lstm_recurrence, cvcl_lstm_cell_bwd_seeds) take any length.
+MAX_CAPTION_LEN = 32
 
 
 def _captioning_lstm_of(language_model):
@@ -319,26 +322,12 @@ def caption_seed_targets(features, language_model, y, y_len, normalize_features=
     # forward: connector -> (h0, c0), the LSTM over tokens 0 .. L-2 with everything BPTT needs saved, output layer, softmax
     w_conn = te.connector.weight.detach().contiguous()                              # [2 H, E]
     state = H.gemm(n, w_conn, bias=te.connector.bias.detach().contiguous())
-    h, c0 = state[:, :Hd].contiguous(), state[:, Hd:].contiguous()
-    c = c0.clone()
-    tok = y[:, :K].contiguous()
-    x = torch.empty(B * K, E, dtype=F32, device=dev)
-    H.check(lib.cvcl_embed_gather_pos(H.ptr(table, F32), H.ptr(tok), None, H.ptr(x), B, K, E, V, s), "cvcl_embed_gather_pos")
+    c0 = state[:, Hd:].contiguous()
+    x = ops._embed_gather(table, y[:, :K].contiguous())
     w_hh = lstm.weight_hh_l0.detach().contiguous()
     gx = H.gemm(x, lstm.weight_ih_l0.detach().contiguous(), bias=(lstm.bias_ih_l0 + lstm.bias_hh_l0).detach().contiguous())
-    gates = torch.empty(B, 4 * Hd, dtype=F32, device=dev)
-    gact = torch.zeros(B * K, 4 * Hd, dtype=F32, device=dev)
-    csave = torch.empty(B * K, Hd, dtype=F32, device=dev)
-    hprev = torch.empty(B * K, Hd, dtype=F32, device=dev)
-    out = torch.empty(B * K, Hd, dtype=F32, device=dev)
-    for t in range(K):
-        a = H.GemmArgs()
-        a.A, a.W, a.C = H.ptr(h), H.ptr(w_hh), H.ptr(gates)
-        a.M, a.N, a.K, a.lda, a.ldw, a.ldc = B, 4 * Hd, Hd, Hd, Hd, 4 * Hd
-        a.R, a.ldr = gx.data_ptr() + t * 4 * Hd * 4, K * 4 * Hd
-        H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
-        H.check(lib.cvcl_lstm_cell_train(H.ptr(gates), H.ptr(length), t, H.ptr(h), H.ptr(c), H.ptr(out), H.ptr(gact), H.ptr(csave),
-                                         H.ptr(hprev), B, K, Hd, s), "cvcl_lstm_cell_train")
+    hc = ops.lstm_initial_state(state[:, :Hd], c0, B, Hd, dev)
+    out, gact, csave, _ = ops.lstm_recurrence(gx, w_hh, length, hc, B, K, save=True)
     w_out = language_model.output_layer.weight.detach().contiguous()                # [V, H] (the tied table)
     b_out = language_model.output_layer.bias
     logits = H.gemm(out, w_out, bias=None if b_out is None else b_out.detach().contiguous())
@@ -361,29 +350,15 @@ def caption_seed_targets(features, language_model, y, y_len, normalize_features=
     dG = torch.empty(K * B, 4 * Hd, dtype=F32, device=dev)
     carry = torch.empty(K * B, Hd, dtype=F32, device=dev)
     for t in range(K - 1, -1, -1):
-        rows, off = B * (K - t), t * B * Hd * 4
+        rows, alive_h, alive_c = B * (K - t), dh[t * B:], dc[t * B:]
         H.check(lib.cvcl_lstm_cell_bwd_seeds(H.ptr(gact), H.ptr(csave), H.ptr(c0) if t == 0 else None, H.ptr(length), t, H.ptr(d_out),
-                                             dh.data_ptr() + off, dc.data_ptr() + off, H.ptr(dG), H.ptr(carry), B, K, Hd, rows, s),
+                                             H.ptr(alive_h), H.ptr(alive_c), H.ptr(dG), H.ptr(carry), B, K, Hd, rows, s),
                 "cvcl_lstm_cell_bwd_seeds")
-        a = H.GemmArgs()                                                            # dh_{t-1} = dG_t . W_hh + carry
-        a.A, a.W, a.C = H.ptr(dG), H.ptr(w_hh), dh.data_ptr() + off
-        a.M, a.N, a.K, a.lda, a.ldw, a.ldc = rows, Hd, 4 * Hd, 4 * Hd, Hd, Hd
-        a.w_trans = 1
-        a.R, a.ldr = H.ptr(carry), Hd
-        H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
+        H.gemm(dG, w_hh, M=rows, w_trans=True, residual=carry, out=alive_h, stream=s)   # dh_{t-1} = dG_t . W_hh + carry
 
     # connector backward on all rows: d n = dh0 W[:H] + dc0 W[H:], then F.normalize's backward with the image's (n, norm) and the
     # reordering seed-major -> image-major in one launch
-    dn_h = torch.empty(K * B, E, dtype=F32, device=dev)
-    dn = torch.empty(K * B, E, dtype=F32, device=dev)
-    for A, W_off, C, Rr in ((dh, 0, dn_h, None), (dc, Hd * E * 4, dn, dn_h)):
-        a = H.GemmArgs()
-        a.A, a.W, a.C = H.ptr(A), w_conn.data_ptr() + W_off, H.ptr(C)
-        a.M, a.N, a.K, a.lda, a.ldw, a.ldc = K * B, E, Hd, Hd, E, E
-        a.w_trans = 1
-        if Rr is not None:
-            a.R, a.ldr = H.ptr(Rr), E
-        H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
+    dn = H.gemm(dc, w_conn[Hd:], w_trans=True, residual=H.gemm(dh, w_conn[:Hd], w_trans=True))
     targets = torch.empty(B * K, E, dtype=F32, device=dev)
     H.check(lib.cvcl_l2norm_bwd_seeds(H.ptr(n) if normalize_features else None, H.ptr(norm), H.ptr(dn), H.ptr(targets), B, K, E, eps, s),
             "cvcl_l2norm_bwd_seeds")

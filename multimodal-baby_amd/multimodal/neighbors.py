@@ -42,11 +42,7 @@ def _group_ids(query_groups, base_groups, nq, nb, device):
 def _rows_f32(t, what):
     if t.dim() != 2 or t.dtype != torch.float32:
         raise H.CvclError(f"{what}: expected [N, D] fp32 rows, got {tuple(t.shape)} {t.dtype}")
-    if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    elif t.shape[0] <= 1:
-        t = t.contiguous()
-    return t
+    return t if H.row_strided(t) else t.contiguous()
 
 
 def nearest_cosine(query, base, query_groups=None, base_groups=None, chunk=None, eps=COSINE_EPS):
@@ -67,13 +63,11 @@ def nearest_cosine(query, base, query_groups=None, base_groups=None, chunk=None,
         return cos, idx
     lib = H.lib()
     step = Nb if chunk is None else max(1, int(chunk))
-    ldq, ldb = (q.stride(0) if Nq > 1 else D), (b.stride(0) if Nb > 1 else D)
     ws = torch.empty(lib.cvcl_nn_cosine_workspace_bytes(Nq, min(step, Nb), D), dtype=torch.uint8, device=q.device)
     for s in range(0, Nb, step):
         n = min(step, Nb - s)
-        H.check(lib.cvcl_nn_cosine(q.data_ptr(), ldq, b.data_ptr() + 4 * s * ldb, ldb, Nq, n, D, eps, H.ptr(qg),
-                                   None if bg is None else bg.data_ptr() + 4 * s, s, int(s > 0), H.ptr(cos), H.ptr(idx), H.ptr(ws),
-                                   ws.numel(), H.stream_ptr()), "cvcl_nn_cosine")
+        H.check(lib.cvcl_nn_cosine(*H.rows(q), *H.rows(b[s:s + n]), Nq, n, D, eps, H.ptr(qg), None if bg is None else H.ptr(bg[s:]),
+                                   s, int(s > 0), H.ptr(cos), H.ptr(idx), H.ptr(ws), ws.numel(), H.stream_ptr()), "cvcl_nn_cosine")
     return cos, idx
 
 
@@ -129,7 +123,7 @@ def nearest_pixels(query_u8, base_u8, std=IMAGENET_STD, query_groups=None, base_
         if n == 0 or Nq == 0:
             continue
         ws = torch.empty(lib.cvcl_nn_l1_u8_workspace_bytes(Nq, n, Cn), dtype=torch.uint8, device=q.device)
-        H.check(lib.cvcl_nn_l1_u8(H.ptr(q), H.ptr(b), Nq, n, Cn, HW, warr, H.ptr(qg), None if bg is None else bg.data_ptr() + 4 * s,
+        H.check(lib.cvcl_nn_l1_u8(H.ptr(q), H.ptr(b), Nq, n, Cn, HW, warr, H.ptr(qg), None if bg is None else H.ptr(bg[s:]),
                                   seen, int(seen > 0), H.ptr(dist), H.ptr(idx), H.ptr(sums), H.ptr(ws), ws.numel(), H.stream_ptr()),
                 "cvcl_nn_l1_u8")
         seen += n

@@ -313,40 +313,57 @@ def _embed_gather(table, tok, pos=None):
     return x
 
 
+def lstm_initial_state(h0, c0, B, Hd, device):
+    """(h, c) [B, H] fp32 for lstm_recurrence to advance in place: copies of ``h0``, ``c0`` (captioning: the image's state), zeros
+    when both are absent (reference init_hidden, multimodal.py:671-688)."""
+    if (h0 is None) != (c0 is None):
+        raise ValueError("LSTM initial state: give both h0 and c0 or neither")
+    if h0 is None:
+        return torch.zeros(B, Hd, dtype=_F, device=device), torch.zeros(B, Hd, dtype=_F, device=device)
+    return tuple(torch.empty(B, Hd, dtype=_F, device=device).copy_(t.detach().reshape(B, Hd)) for t in (h0, c0))
+
+
+def lstm_recurrence(gx, w_hh, length, state, B, L, save=False):
+    """The forward recurrence of the one-layer LSTM, for the eval encoder, the training forward and the per-word Grad-CAM alike.
+    ``gx`` [B L, 4H] = x W_ih^T + b_ih + b_hh for all steps (one GEMM, the caller's); per step t one recurrent GEMM
+    gates = h W_hh^T + gx[:, t] (the input's gates added through the residual epilogue) and the cell kernel, which advances
+    ``state`` = (h, c) [B, H] in place for the sequences still running at t (``length`` [B] int64).  -> out [B, L, H], or with
+    ``save`` (cvcl_lstm_cell_train) -> (out, gact [B L, 4H], csave [B L, H], hprev [B L, H]): what BPTT reads."""
+    h, c = state
+    Hd = w_hh.shape[1]
+    dev = gx.device
+    lib, s = H.lib(), H.stream_ptr()
+    gx = gx.view(B, L, 4 * Hd).unbind(1)                 # step t's rows of gx: row-strided views (H.rows)
+    out = torch.empty(B, L, Hd, dtype=_F, device=dev)
+    gates = torch.empty(B, 4 * Hd, dtype=_F, device=dev)
+    cell = (H.ptr(h, _F), H.ptr(c, _F), H.ptr(out))
+    if save:
+        gact = torch.zeros(B * L, 4 * Hd, dtype=_F, device=dev)       # (rows of finished sequences stay zero)
+        csave = torch.empty(B * L, Hd, dtype=_F, device=dev)
+        hprev = torch.empty(B * L, Hd, dtype=_F, device=dev)
+        cell += (H.ptr(gact), H.ptr(csave), H.ptr(hprev))
+    step, name = (lib.cvcl_lstm_cell_train, "cvcl_lstm_cell_train") if save else (lib.cvcl_lstm_cell, "cvcl_lstm_cell")
+    p_gates, p_len = H.ptr(gates), H.ptr(length, torch.int64)
+    for t in range(L):
+        H.gemm(h, w_hh, residual=gx[t], out=gates, stream=s)
+        H.check(step(p_gates, p_len, t, *cell, B, L, Hd, s), name)
+    return (out, gact, csave, hprev) if save else out
+
+
 def lstm_text(table, lstm, tok, length, h0=None, c0=None):
     """Embedding + one-layer uni-directional nn.LSTM over variable-length sequences, eval mode
     (reference multimodal/multimodal.py:513-552).  -> (h at each sequence's last step [B,H], outputs [B,Lmax,H]).
-    x W_ih^T for all steps is one GEMM; each step is one recurrent GEMM (gates of the input added through the
-    residual epilogue) plus the cell kernel.  ``h0``, ``c0`` [B, H]: the initial state (captioning, init_hidden :671-688);
-    zeros when absent."""
+    x W_ih^T for all steps is one GEMM; the steps are lstm_recurrence.  ``h0``, ``c0`` [B, H]: the initial state (captioning,
+    init_hidden :671-688); zeros when absent."""
     if lstm.bidirectional or lstm.num_layers != 1:
         raise NotImplementedError("only the one-layer uni-directional LSTM text encoder is on the contrastive path")
     B, L = tok.shape
-    Hd = lstm.hidden_size
-    dev = table.device
     with torch.no_grad():
         x = _embed_gather(table, tok)
         bias = (lstm.bias_ih_l0 + lstm.bias_hh_l0).detach().contiguous()
         gx = H.gemm(x, lstm.weight_ih_l0.detach().contiguous(), bias=bias)             # [B*L, 4H]
-        w_hh = lstm.weight_hh_l0.detach().contiguous()
-        h = torch.zeros(B, Hd, dtype=_F, device=dev)                                   # init_hidden zeros (:671-688)
-        c = torch.zeros(B, Hd, dtype=_F, device=dev)
-        if (h0 is None) != (c0 is None):
-            raise ValueError("lstm_text: give both h0 and c0 or neither")
-        if h0 is not None:
-            h.copy_(h0.detach().reshape(B, Hd))
-            c.copy_(c0.detach().reshape(B, Hd))
-        out = torch.empty(B, L, Hd, dtype=_F, device=dev)
-        gates = torch.empty(B, 4 * Hd, dtype=_F, device=dev)
-        lib, s = H.lib(), H.stream_ptr()
-        for t in range(L):
-            a = H.GemmArgs()
-            a.A, a.W, a.C = H.ptr(h), H.ptr(w_hh), H.ptr(gates)
-            a.M, a.N, a.K, a.lda, a.ldw, a.ldc = B, 4 * Hd, Hd, Hd, Hd, 4 * Hd
-            a.R, a.ldr = gx.data_ptr() + t * 4 * Hd * 4, L * 4 * Hd                   # row b of step t inside gx
-            H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
-            H.check(lib.cvcl_lstm_cell(H.ptr(gates), H.ptr(length, torch.int64), t, H.ptr(h), H.ptr(c), H.ptr(out), B, L, Hd, s),
-                    "cvcl_lstm_cell")
+        h, c = lstm_initial_state(h0, c0, B, lstm.hidden_size, table.device)
+        out = lstm_recurrence(gx, lstm.weight_hh_l0.detach().contiguous(), length, (h, c), B, L)
         lmax = int(length.max())              # pad_packed_sequence trims to the longest sequence (the reference syncs here too)
     return h, out[:, :lmax]
 

@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import _hip as H
-from .ops import LinearF32, _F, linear_backward
+from .ops import LinearF32, _F, linear_backward, lstm_initial_state, lstm_recurrence
 
 
 def _seed() -> int:
@@ -212,34 +212,12 @@ class LstmCore(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, length, B, L, h0=None, c0=None):
         Hd = w_hh.shape[1]
-        dev = x.device
-        lib, s = H.lib(), H.stream_ptr()
         bias = (b_ih + b_hh).contiguous()
         gx = H.gemm(x.contiguous(), w_ih.contiguous(), bias=bias)                       # [B*L, 4H]
         w_hh_c = w_hh.contiguous()
-        if (h0 is None) != (c0 is None):
-            raise ValueError("LstmCore: give both h0 and c0 or neither")
-        if h0 is None:
-            h = torch.zeros(B, Hd, dtype=_F, device=dev)
-            c = torch.zeros(B, Hd, dtype=_F, device=dev)
-            c0_saved = None
-        else:
-            h = h0.detach().reshape(B, Hd).contiguous().clone()
-            c = c0.detach().reshape(B, Hd).contiguous().clone()
-            c0_saved = c.clone()
-        gates = torch.empty(B, 4 * Hd, dtype=_F, device=dev)
-        gact = torch.zeros(B * L, 4 * Hd, dtype=_F, device=dev)
-        csave = torch.empty(B * L, Hd, dtype=_F, device=dev)
-        hprev = torch.empty(B * L, Hd, dtype=_F, device=dev)
-        out = torch.empty(B, L, Hd, dtype=_F, device=dev)
-        for t in range(L):
-            a = H.GemmArgs()
-            a.A, a.W, a.C = H.ptr(h), H.ptr(w_hh_c), H.ptr(gates)
-            a.M, a.N, a.K, a.lda, a.ldw, a.ldc = B, 4 * Hd, Hd, Hd, Hd, 4 * Hd
-            a.R, a.ldr = gx.data_ptr() + t * 4 * Hd * 4, L * 4 * Hd
-            H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
-            H.check(lib.cvcl_lstm_cell_train(H.ptr(gates), H.ptr(length, torch.int64), t, H.ptr(h), H.ptr(c), H.ptr(out), H.ptr(gact),
-                                             H.ptr(csave), H.ptr(hprev), B, L, Hd, s), "cvcl_lstm_cell_train")
+        h, c = lstm_initial_state(h0, c0, B, Hd, x.device)
+        c0_saved = None if c0 is None else c.clone()
+        out, gact, csave, hprev = lstm_recurrence(gx, w_hh_c, length, (h, c), B, L, save=True)
         ctx.save_for_backward(x, w_ih, w_hh_c, length, gact, csave, hprev, c0_saved)
         ctx.dims = (B, L, Hd)
         ctx.set_materialize_grads(False)       # the unused one of (h, out) arrives as None instead of a zero tensor
@@ -254,25 +232,25 @@ class LstmCore(torch.autograd.Function):
         dh = dh_final.contiguous().clone() if dh_final is not None else torch.zeros(B, Hd, dtype=_F, device=dev)
         dc = torch.zeros(B, Hd, dtype=_F, device=dev)
         dG = torch.empty(B * L, 4 * Hd, dtype=_F, device=dev)
+        dG_steps = dG.view(B, L, 4 * Hd).unbind(1)       # step t's rows of dG: row-strided views (H.rows)
         carry = torch.empty(B, Hd, dtype=_F, device=dev)
         dh_next = torch.empty_like(dh)
         if d_out is not None:
             d_out = d_out.contiguous()
+        # (what does not change between the steps is resolved once: the loop is launch-bound)
+        p_out, p_len, p_dc, p_dG, p_carry = H.ptr(d_out, _F), H.ptr(length), H.ptr(dc), H.ptr(dG), H.ptr(carry)
+        p_gact, p_csave = H.ptr(gact), H.ptr(csave)
         for t in range(L - 1, -1, -1):
+            p_dh = H.ptr(dh)
             if d_out is not None:             # per-step outputs feed the language-model branch: out[b,t] = h_t while running
-                H.check(lib.cvcl_lstm_add_dout(H.ptr(dh), H.ptr(d_out, _F), H.ptr(length), t, B, L, Hd, s), "cvcl_lstm_add_dout")
+                H.check(lib.cvcl_lstm_add_dout(p_dh, p_out, p_len, t, B, L, Hd, s), "cvcl_lstm_add_dout")
             if t == 0 and c0 is not None:
-                H.check(lib.cvcl_lstm_cell_bwd_first(H.ptr(gact), H.ptr(csave), H.ptr(c0), H.ptr(length), H.ptr(dh), H.ptr(dc), H.ptr(dG),
-                                                     H.ptr(carry), B, L, Hd, s), "cvcl_lstm_cell_bwd_first")
+                H.check(lib.cvcl_lstm_cell_bwd_first(p_gact, p_csave, H.ptr(c0), p_len, p_dh, p_dc, p_dG, p_carry, B, L, Hd, s),
+                        "cvcl_lstm_cell_bwd_first")
             else:
-                H.check(lib.cvcl_lstm_cell_bwd(H.ptr(gact), H.ptr(csave), H.ptr(length), t, H.ptr(dh), H.ptr(dc), H.ptr(dG),
-                                               H.ptr(carry), B, L, Hd, s), "cvcl_lstm_cell_bwd")
-            a = H.GemmArgs()                                                       # dh_{t-1} = dG_t . W_hh + carry
-            a.A, a.W, a.C = dG.data_ptr() + t * 4 * Hd * 4, H.ptr(w_hh), H.ptr(dh_next)      # W' = W_hh^T: W_hh read K-major in place
-            a.M, a.N, a.K, a.lda, a.ldw, a.ldc = B, Hd, 4 * Hd, L * 4 * Hd, Hd, Hd
-            a.w_trans = 1
-            a.R, a.ldr = H.ptr(carry), Hd
-            H.check(lib.cvcl_gemm(H.F32, a, s), "cvcl_gemm")
+                H.check(lib.cvcl_lstm_cell_bwd(p_gact, p_csave, p_len, t, p_dh, p_dc, p_dG, p_carry, B, L, Hd, s), "cvcl_lstm_cell_bwd")
+            # dh_{t-1} = dG_t . W_hh + carry (W' = W_hh^T: W_hh read K-major in place)
+            H.gemm(dG_steps[t], w_hh, w_trans=True, residual=carry, out=dh_next, stream=s)
             dh, dh_next = dh_next, dh
         needs = ctx.needs_input_grad
         dx = dwi = dwh = db = None
