@@ -1,4 +1,5 @@
-"""ctypes binding of libcvcl_hip.so (the C ABI declared in include/cvcl_hip.h).
+"""ctypes binding of libcvcl_hip.so.  The C ABI is declared once, in include/cvcl_hip.h: the signatures, the argument
+structs and the constants below are read from that header at import, not restated here.
 
 The library is loaded AFTER torch so that its DT_NEEDED ``libamdhip64.so.7`` resolves to the HIP
 runtime torch already mapped (same soname) -- one runtime per process, so torch's stream handles
@@ -9,20 +10,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libcvcl_hip.so")
-
-F32, BF16, F32X3 = 0, 1, 2          # cvcl_hip.h dtypes (F32X3: fp32 storage, split-bf16 trunk products; ABI v7)
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2, 3   # cvcl_hip.h CVCL_ACT_* (QUICK_GELU: CLIP's MLP)
-ABI_VERSION = 7
-PACK_DENSE, PACK_STEM7, PACK_GCONV3 = 0, 1, 2
-GRADCAM_ALL, GRADCAM_BLOCK_IMAGE, GRADCAM_BLOCK_TEXT = 0, 1, 2      # cvcl_hip.h CVCL_GRADCAM_*
-FUSE_MEAN, FUSE_MAX, FUSE_MIN = 0, 1, 2                             # cvcl_hip.h CVCL_FUSE_*
-BEAM_MAX_K, BEAM_MAX_T = 16, 128                                 # cvcl_hip.h CVCL_BEAM_MAX_*
-TOKEN_TOPK_MAX_K = 16                                            # cvcl_hip.h CVCL_TOKEN_TOPK_MAX_K
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "cvcl_hip.h")
+# the names bench.py reports, in the order of cvcl_hip.h's CVCL_K_* enum
 KERNEL_CLASSES = ("gemm", "gconv3x3", "stem7x7", "bn_finalize", "bn_add_relu", "bn_relu_maxpool", "avgpool", "head",
                   "other", "attention", "layernorm", "lstm", "gemm_f32", "bn_relu_apply", "bn_bwd", "wgrad", "gemm8w", "gemm_pro")
 
@@ -31,212 +26,98 @@ class CvclError(RuntimeError):
     pass
 
 
-class GemmArgs(C.Structure):
-    _fields_ = [
-        ("A", C.c_void_p), ("W", C.c_void_p), ("C", C.c_void_p),
-        ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("lda", C.c_int), ("ldw", C.c_int), ("ldc", C.c_int),
-        ("a_scale", C.c_void_p), ("a_shift", C.c_void_p), ("a_relu", C.c_int),
-        ("gather_ho", C.c_int), ("gather_wo", C.c_int), ("gather_hi", C.c_int), ("gather_wi", C.c_int),
-        ("gather_stride", C.c_int),
-        ("exp_scale", C.c_void_p), ("bias", C.c_void_p), ("act", C.c_int),
-        ("R", C.c_void_p), ("ldr", C.c_int),
-        ("stats", C.c_void_p), ("stats_rows", C.c_int),
-        ("c_scale", C.c_void_p), ("c_shift", C.c_void_p), ("r_scale", C.c_void_p), ("r_shift", C.c_void_p),
-        ("C_pre", C.c_void_p), ("G", C.c_void_p), ("ldg", C.c_int),
-        ("centre", C.c_void_p),
-        ("A2", C.c_void_p), ("W2", C.c_void_p), ("K2", C.c_int), ("lda2", C.c_int), ("ldw2", C.c_int), ("centre2", C.c_void_p),
-        ("ln_stats", C.c_void_p), ("ln_colsum", C.c_void_p), ("row_part", C.c_void_p),
-        ("a_trans", C.c_int), ("w_trans", C.c_int), ("a_rowsum", C.c_void_p),
-        ("f32_split", C.c_int),
-    ]
+# ---- the shape of the ABI, read from include/cvcl_hip.h (tests/test_abi.py has the compiler check what this derives) ----
+_SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+            "int64_t": C.c_int64, "unsigned long long": C.c_ulonglong}
+_POINTEES = set(_SCALARS) | {"void", "char", "int32_t", "uint8_t", "uint32_t"}      # (and the header's own structs)
+_TYPE_WORDS = {"void", "char", "short", "int", "long", "float", "double", "signed", "unsigned", "struct", "enum", "union"}
+_INT = r"(-?\d+|\(\s*-?\d+\s*\))"
 
 
-class GemmFp8Args(C.Structure):
-    _fields_ = [
-        ("A8", C.c_void_p), ("a_scale", C.c_void_p), ("a_block_scales", C.c_void_p), ("lda", C.c_int),
-        ("W8", C.c_void_p), ("w_scale", C.c_void_p), ("ldw", C.c_int),
-        ("C", C.c_void_p), ("ldc", C.c_int), ("c8", C.c_void_p), ("c_block_scales", C.c_void_p), ("ldc8", C.c_int),
-        ("bias", C.c_void_p), ("act", C.c_int), ("R", C.c_void_p), ("ldr", C.c_int),
-        ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
-        ("ln_stats", C.c_void_p), ("ln_colsum", C.c_void_p), ("row_part", C.c_void_p),
-    ]
+def _ctype(decl, structs, ret=False):
+    """'const float* x' -> (c_void_p, 'x'): the ctypes type of one argument, field or return type, and its name (None if absent)."""
+    words = [w for w in re.findall(r"\w+|\*", decl) if w != "const"]
+    stars = words.count("*")
+    base = words[:words.index("*")] if stars else words
+    name = [w for w in words[len(base):] if w != "*"]
+    if not stars and " ".join(base) not in _SCALARS and " ".join(base) not in structs:
+        base, name = base[:-1], base[-1:]
+    base = " ".join(base)
+    if (not re.fullmatch(r"(\s*(\*|[A-Za-z_]\w*))*\s*", decl)                          # a function pointer, "...", an array, a bit field
+            or len(name) > 1 or set(name) & _TYPE_WORDS or (name and (ret or words[-1] != name[0]))
+            or not (base in _POINTEES or base in structs if stars else base in _SCALARS)):    # an unknown type, a struct by value
+        raise CvclError(f"cvcl_hip.h: cannot bind {decl.strip()!r}")
+    if not stars:
+        t = _SCALARS[base]
+    elif stars == 1 and base in structs:
+        t = C.POINTER(structs[base])
+    else:
+        t = C.c_char_p if ret and stars == 1 and base == "char" else C.c_void_p
+    return t, (name[0] if name else None)
 
 
-class ConvBnParams(C.Structure):
-    _fields_ = [("w", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
-                ("running_mean", C.c_void_p), ("running_var", C.c_void_p), ("num_batches_tracked", C.c_void_p)]
+def parse_header(text):
+    """-> (constants {name: int}, structs {name: ctypes.Structure class}, signatures {name: (restype, [argtypes])}) of a header in
+    cvcl_hip.h's dialect: integer #defines, anonymous enums, typedef struct blocks of scalars and pointers, prototypes.  Strict: a
+    declaration outside that dialect raises CvclError with its text; nothing is skipped."""
+    consts, structs, sigs, body = {}, {}, {}, []
+    for line in re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S).split("\n"):
+        s = line.strip()
+        m = re.fullmatch(r"#\s*define\s+(\w+)\s+" + _INT, s)
+        if m:
+            consts[m[1]] = int(m[2].strip("() "))
+        elif not s.startswith("#"):
+            body.append(line)
+        elif not re.fullmatch(r"#\s*(include\s*<[\w./]+>|ifn?def\s+\w+|endif|define\s+\w+)", s):
+            raise CvclError(f"cvcl_hip.h: cannot classify the preprocessor line {s!r}")
+    text, wrapped = re.subn(r'extern\s+"C"\s*\{', "", "\n".join(body))
+    statement = re.compile(r"\s*((?:[^;{}]|\{[^{}]*\})+);")
+    pos = 0
+    while (m := statement.match(text, pos)):
+        pos, s = m.end(), " ".join(m[1].split())
+        if (e := re.fullmatch(r"enum ?\{(.*)\}", s)):
+            value = -1
+            for item in filter(None, map(str.strip, e[1].split(","))):
+                if not (i := re.fullmatch(r"(\w+)(?: ?= ?" + _INT + ")?", item)):
+                    raise CvclError(f"cvcl_hip.h: cannot classify the enumerator {item!r}")
+                value = consts[i[1]] = int(i[2].strip("() ")) if i[2] else value + 1
+        elif (t := re.fullmatch(r"typedef struct ?\{(.*)\} ?(\w+)", s)):
+            fields = []
+            for decl in filter(None, map(str.strip, t[1].split(";"))):
+                first, *more = decl.split(",")                 # int M, N, K: the declarators after the first share its base type
+                base = re.fullmatch(r"(.*?)[\s*]*\w*", first)[1]
+                for d in [first] + [base + " " + x for x in more]:
+                    ctype, name = _ctype(d, structs)
+                    if name is None:
+                        raise CvclError(f"cvcl_hip.h: cannot bind the field {d.strip()!r}")
+                    fields.append((name, ctype))
+            structs[t[2]] = type(t[2], (C.Structure,), {"_fields_": fields})
+        elif (f := re.fullmatch(r"([\w *]+?) ?\b(\w+) ?\((.*)\)", s)):
+            args = [] if f[3].strip() == "void" else [_ctype(a, structs)[0] for a in f[3].split(",")]
+            sigs[f[2]] = (_ctype(f[1], structs, ret=True)[0], args)
+        else:
+            raise CvclError(f"cvcl_hip.h: cannot classify the declaration {s!r}")
+    if text[pos:].strip() != "}" * wrapped:                # (the brace that closes extern "C" is all that may be left)
+        raise CvclError(f"cvcl_hip.h: cannot classify {text[pos:].strip()[:80]!r}")
+    return consts, structs, sigs
 
 
-_P, _I, _F, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise CvclError(f"the binding is derived from {HEADER_PATH}, which cannot be read: {e}") from e
 
-# name -> (restype, argtypes); every symbol include/cvcl_hip.h declares
-SIGNATURES = {
-    "cvcl_abi_version": (_I, []),
-    "cvcl_last_error": (C.c_char_p, []),
-    "cvcl_prof_enable": (_I, [_I]),
-    "cvcl_prof_collect": (_I, [_P, _P, _I]),
-    "cvcl_prof_null_bracket_us": (_I, [_P, _I, _P]),
-    "cvcl_embed_meanpool_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_embed_meanpool_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_l2norm_fwd": (_I, [_P, _P, _P, _I, _I, _F, _P]),
-    "cvcl_l2norm_bwd": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
-    "cvcl_sim_logits_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_sim_logits_bwd_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "cvcl_sim_logits_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _SZ, _P]),
-    "cvcl_sim_logits_bwd_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
-    "cvcl_infonce_workspace_bytes": (_SZ, [_I]),
-    "cvcl_infonce_fwd": (_I, [_P, _I, _P, _P, _P, _P, _SZ, _P]),
-    "cvcl_infonce_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P]),
-    "cvcl_row_entropy": (_I, [_P, _P, _I, _I, _P]),
-    "cvcl_gemm_grid_m": (_I, [_I, _I, _I, _I]),
-    "cvcl_gemm": (_I, [_I, C.POINTER(GemmArgs), _P]),
-    "cvcl_transpose_f32": (_I, [_P, _P, _I, _I, _P]),
-    "cvcl_colsum_f32": (_I, [_P, _P, _I, _I, _P]),
-    "cvcl_bn_finalize": (_I, [_P, _I, C.c_long, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _I, _P]),
-    "cvcl_bn_eval_affine": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _I, _P]),
-    "cvcl_col_stats_rows": (_I, [C.c_long]),
-    "cvcl_col_stats": (_I, [_I, _P, C.c_long, _I, _P, _I, _P]),
-    "cvcl_packed_weight_bytes": (_SZ, [_I, _I, _I, _I, _I]),
-    "cvcl_pack_conv_weight": (_I, [_I, _I, _P, _P, _I, _I, _I, _P]),
-    "cvcl_stem_conv_stats_rows": (_I, [_I, _I, _I, _I]),
-    "cvcl_stem_conv7x7": (_I, [_I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
-    "cvcl_stem_pool_supported": (_I, [_I, _I, _I]),
-    "cvcl_stem_pool": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_bn_relu_maxpool": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_gconv3x3_stats_rows": (_I, [_I, _I, _I, _I, _I, _I]),
-    "cvcl_gconv3x3": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cvcl_bn_add_relu": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, C.c_long, _I, _P]),
-    "cvcl_bn_relu_apply": (_I, [_I, _P, _P, _P, _P, C.c_long, _I, _P]),
-    "cvcl_avgpool": (_I, [_I, _P, _P, _I, _I, _I, _P]),
-    "cvcl_im2col_patches": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cvcl_vit_assemble_tokens": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_layernorm": (_I, [_I, _P, C.c_long, _P, _P, _F, _P, _I, C.c_long, _I, _P]),
-    "cvcl_attention": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "cvcl_attention_causal": (_I, [_I, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "cvcl_clip_text_pool": (_I, [_P, _P, _P, _P, _F, _P, _I, _I, _I, _P]),
-    "cvcl_embed_gather_pos": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_seq_sum_div": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_lstm_cell": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_dropout": (_I, [_P, _P, _P, C.c_long, _F, C.c_ulonglong, C.c_long, C.c_long, _P]),
-    "cvcl_layernorm_bwd": (_I, [_P, _P, _P, _F, _P, _P, C.c_long, _I, _P]),
-    "cvcl_relu_bwd": (_I, [_P, _P, _P, C.c_long, _P]),
-    "cvcl_embed_rows_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_seq_sum_div_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_attention_small": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, C.c_ulonglong, _P]),
-    "cvcl_lstm_cell_train": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_lstm_cell_bwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_bn_apply": (_I, [_I, _P, _P, _P, _P, C.c_long, _I, _I, _P]),
-    "cvcl_bn_bwd_partial_rows": (_I, [_I, C.c_long, _I]),
-    "cvcl_bn_bwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_long, _I, _P, _I, _P, _P]),
-    "cvcl_bn_batch_moments": (_I, [_P, _I, C.c_long, C.c_float, _P, _P, _P, _I, _P]),
-    "cvcl_gconv_weight_dgrad": (_I, [_P, _P, _I, _I, _P]),
-    "cvcl_transpose": (_I, [_I, _P, _P, C.c_long, _I, _P]),
-    "cvcl_add": (_I, [_I, _P, _P, _P, C.c_long, _I, _P]),
-    "cvcl_relu_mask": (_I, [_I, _P, _P, _P, C.c_long, _P]),
-    "cvcl_maxpool3x3s2": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_maxpool3x3s2_idx": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_avgpool_bwd": (_I, [_I, _P, _P, _I, _I, _I, _P]),
-    "cvcl_zero_stuff2": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_conv_wgrad_direct": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cvcl_gemm_tn_workspace_bytes": (C.c_size_t, [_I, C.c_long, _I, _I]),
-    "cvcl_gemm_tn": (_I, [_I, _P, _I, _P, _I, C.c_long, _I, _I, _P, _I, _P, C.c_size_t, _P]),
-    "cvcl_gconv3x3_wgrad_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
-    "cvcl_gconv3x3_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
-    "cvcl_stem_im2col": (_I, [_P, _P, _I, _I, _I, _P]),
-    "cvcl_gemm_stats_rows": (_I, [_I, _P]),
-    "cvcl_gemm_pro": (_I, [_P, _P]),
-    "cvcl_gemm_pro_supported": (_I, [_P]),
-    "cvcl_gemm_pro_stats_rows": (_I, [_I, _I]),
-    "cvcl_gemm8w": (_I, [_I, _P, _P]),
-    "cvcl_gemm8w_supported": (_I, [_I, _I, _I, _I, _I, _I]),
-    "cvcl_gemm_ln_supported": (_I, [C.POINTER(GemmArgs)]),
-    "cvcl_set_gemm_cu_share": (_I, [_I]),
-    "cvcl_conv1x1_gram_workspace_bytes": (C.c_size_t, [_I]),
-    "cvcl_conv1x1_gram": (_I, [_P, _I, C.c_long, _I, _P, _P, _I, _P, C.c_size_t, C.POINTER(C.c_void_p), _P]),
-    "cvcl_bn_from_gram": (_I, [_P, _I, C.c_long, _P, _I, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _I, _P, _P]),
-    "cvcl_row_stats": (_I, [_I, _P, C.c_long, _P, C.c_long, _I, _F, _P]),
-    "cvcl_row_stats_finalize": (_I, [_P, _I, _P, C.c_long, _I, _F, _P]),
-    "cvcl_gemm8w_tile_rows": (_I, [_I, _I]),
-    "cvcl_gemm8w_stats_rows": (_I, [_I, _I]),
-    "cvcl_bf16_to_f32": (_I, [_P, _P, C.c_long, _P]),
-    "cvcl_f32_to_bf16": (_I, [_P, _P, C.c_long, _P]),
-    "cvcl_spatial_max_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_spatial_max_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_lstm_add_dout": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_seq_reverse": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_scale_add_f32": (_I, [_P, _P, C.c_float, _P, C.c_long, _P]),
-    "cvcl_augment_frames": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P]),
-    "cvcl_augment_frames_indexed": (_I, [_P, C.c_int64, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P]),
-    "cvcl_preprocess_frames": (_I, [_P, C.c_int64, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
-    "cvcl_cbow": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_token_ce_fwd": (_I, [_P, _P, _P, _P, C.c_long, _I, _I, _P]),
-    "cvcl_token_ce_bwd": (_I, [_P, _P, _P, _P, _P, C.c_long, _I, _I, _P]),
-    "cvcl_lm_loss_summaries": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_quant_rows_fp8": (_I, [_I, _P, C.c_long, _P, _P, C.c_float, _P, _P, C.c_long, _I, _P]),
-    "cvcl_attention_train": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "cvcl_attention_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "cvcl_layernorm_bwd_rows_partials": (_I, [C.c_long]),
-    "cvcl_layernorm_bwd_rows": (_I, [_P, C.c_long, _P, _P, _I, C.c_long, _F, _P, _P, C.c_long, _P, C.c_long, _I, _P]),
-    "cvcl_gelu_bf16": (_I, [_P, _P, _P, C.c_long, _P]),
-    "cvcl_vit_tokens_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_gemm_tn_colsum_workspace_bytes": (C.c_size_t, [C.c_long, _I, _I]),
-    "cvcl_gemm_tn_colsum": (_I, [_P, _I, _P, _I, C.c_long, _I, _I, _P, _I, _P, _P, C.c_size_t, _P]),
-    # fp32 ViT fine-tuning (csrc/vit_f32_train.hip)
-    "cvcl_attention_train_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "cvcl_attention_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "cvcl_layernorm_bwd_rows_f32": (_I, [_P, C.c_long, _P, _P, C.c_long, _F, _P, _P, C.c_long, _P, C.c_long, _I, _P]),
-    "cvcl_gelu_f32": (_I, [_P, _P, _P, C.c_long, _P]),
-    "cvcl_vit_tokens_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "cvcl_gemm_tn_colsum_f32_workspace_bytes": (C.c_size_t, [C.c_long, _I, _I]),
-    "cvcl_gemm_tn_colsum_f32": (_I, [_P, _I, _P, _I, C.c_long, _I, _I, _P, _I, _P, _P, C.c_size_t, _P]),
-    "cvcl_attention_mx": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "cvcl_gemm_fp8_mx": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
-    "cvcl_gemm_fp8_ex": (_I, [C.POINTER(GemmFp8Args), _P]),
-    "cvcl_gemm_fp8_ln_supported": (_I, [_I, _I, _I]),
-    "cvcl_quant_rows_mx": (_I, [_P, C.c_long, _P, _P, C.c_long, _I, _P]),
-    "cvcl_gemm_fp8": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
-    "cvcl_resnext50_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
-    "cvcl_resnext50_centres_floats": (_SZ, []),
-    "cvcl_resnext50_fwd": (_I, [_I, _I, _I, _I, _I, _P, C.POINTER(ConvBnParams), _I, _P, _SZ, _P, _P, _F, _F, _P, _P]),
-    "cvcl_resnext50_block_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
-    "cvcl_resnext50_block_fwd": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, C.POINTER(ConvBnParams), _I, _P, _SZ, _P, _F, _F, _P, _P]),
-    "cvcl_resnext50_moments_floats": (_SZ, []),
-    "cvcl_resnext50_fwd_deferred_stats": (_I, [_I, _I, _I, _I, _P, C.POINTER(ConvBnParams), _I, _P, _SZ, _P, _P, _F, _P, _P, _P]),
-    "cvcl_resnext50_apply_moments": (_I, [C.POINTER(ConvBnParams), _I, _P, _F, _P]),
-    "cvcl_resnext50_fwd_grouped_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
-    "cvcl_resnext50_fwd_grouped": (_I, [_I, _I, _I, _I, _I, _P, C.POINTER(ConvBnParams), _I, _P, _SZ, _P, _P, _F, _P]),
-    "cvcl_gradcam_pairs": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _F, _P, _P]),
-    "cvcl_bicubic_resize": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
-    "cvcl_gradcam_act_grad": (_I, [_I, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P]),
-    # ViT self-attention maps (csrc/vit_maps.hip)
-    "cvcl_attention_probs": (_I, [_I, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
-    "cvcl_cls_attention_maps": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "cvcl_attention_head_fuse": (_I, [_I, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
-    "cvcl_attention_rollout": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
-    # beam-search decoding (csrc/textgen.hip; the decode cell and the first BPTT step of the captioning state: csrc/lstm.hip)
-    "cvcl_beam_step": (_I, [_P, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
-    "cvcl_beam_finalize": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "cvcl_lstm_cell_tok": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P]),
-    "cvcl_lstm_cell_bwd_first": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    # per-word Grad-CAM of the captioning LM (the multi-seed BPTT step: csrc/lstm.hip; the seed-major F.normalize backward: csrc/head.hip)
-    "cvcl_lstm_cell_bwd_seeds": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, C.c_long, _P]),
-    "cvcl_l2norm_bwd_seeds": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
-    # nearest-neighbour searches (csrc/neighbors.hip)
-    "cvcl_nn_cosine_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "cvcl_nn_cosine": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, C.c_int64, _I, _P, _P, _P, _SZ, _P]),
-    "cvcl_nn_l1_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "cvcl_nn_l1_u8": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_double), _P, _P, C.c_int64, _I, _P, _P, _P, _P, _SZ, _P]),
-    # image-text alignment analysis (csrc/alignment.hip)
-    "cvcl_class_mean_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "cvcl_class_mean_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
-    "cvcl_cosine_matrix_f32": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
-    "cvcl_triu_pearson_workspace_bytes": (_SZ, [_I]),
-    "cvcl_triu_pearson_f32": (_I, [_P, _P, _I, _P, _P, _SZ, _P]),
-    "cvcl_paired_l2_f32": (_I, [_P, _P, _I, _I, _F, _P, _P]),
-    # word statistics (csrc/token_items.hip)
-    "cvcl_token_items_accumulate": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
-    "cvcl_token_topk": (_I, [_P, _P, C.c_long, _I, _I, _I, _P, _P, _P, _P, _P]),
-}
+
+# CONSTANTS: every enumerator and integer #define by its header name; SIGNATURES: name -> (restype, argtypes) of every prototype
+CONSTANTS, STRUCTS, SIGNATURES = parse_header(_read_header())
+GemmArgs, GemmFp8Args, ConvBnParams = STRUCTS["cvcl_gemm_args"], STRUCTS["cvcl_gemm_fp8_args"], STRUCTS["cvcl_convbn_params"]
+# the module-level names of the constants are the header's without CVCL_: F32, BF16, F32X3, ACT_GELU, PACK_GCONV3, GRADCAM_ALL,
+# FUSE_MEAN, BEAM_MAX_K, TOKEN_TOPK_MAX_K, PREPROCESS_TABLE_COLS, STATS_ACCUMULATE, ABI_VERSION, EINVAL, K_NCLASSES, ...
+assert not {k[5:] for k in CONSTANTS} & set(globals()), "a cvcl_hip.h constant shadows a name of this module"
+globals().update({k[5:]: v for k, v in CONSTANTS.items()})
+assert len(KERNEL_CLASSES) == K_NCLASSES, "KERNEL_CLASSES must name every CVCL_K_* class of cvcl_hip.h"      # noqa: F821
 
 _lib = None
 
@@ -522,9 +403,6 @@ def gemm(A, W, out=None, *, bias=None, act=ACT_NONE, residual=None, a_scale=None
         return bool(lib().cvcl_gemm_ln_supported(C.byref(a)))
     check(lib().cvcl_gemm(dt, C.byref(a), stream_ptr() if stream is None else stream), "cvcl_gemm")
     return out
-
-
-STATS_ACCUMULATE = -1          # cvcl_hip.h CVCL_STATS_ACCUMULATE
 
 
 def gemm_grid_m(dtype: int, M: int, N: int, has_prologue: bool = False) -> int:

@@ -28,7 +28,7 @@ from . import _hip as H
 from .augment import IMAGENET_MEAN, IMAGENET_STD
 
 MODES = ("stretch", "shorter_side_center_crop")
-TABLE_COLS = 7                                       # cvcl_hip.h CVCL_PREPROCESS_TABLE_COLS: offset, H, W, rh, rw, ct, cl
+TABLE_COLS = H.PREPROCESS_TABLE_COLS                 # offset, H, W, rh, rw, ct, cl
 
 
 def resize_geometry(height, width, size, mode):
