@@ -91,8 +91,9 @@ int cvcl_prof_null_bracket_us(void* stream, int n, double* avg_us);
  *   table [V,E] f32, tok [B,L] i64, len [B] i64
  *   -> ret [B,E] f32 = sum_l table[tok[b,l]] / len[b];  out_ble [B,L,E] f32 = table[tok] (may be NULL)
  * bwd: d_table [V,E] f32 (fully overwritten; row 0 = 0) from d_ret [B,E]; deterministic
- * (b,l)-ordered accumulation, no atomics.  Token ids outside [0,V) are an error the kernel
- * reports by writing NaN into the affected rows (the reference raises an index error).        */
+ * (b,l)-ordered accumulation, no atomics.  Token ids outside [0,V) are an error the forward
+ * reports by writing NaN into the affected rows (the reference raises an index error); the
+ * backward gives such a position to no row (the ids are compared as int64: v + 2^32 is not v). */
 int cvcl_embed_meanpool_fwd(const float* table, const int64_t* tok, const int64_t* len, float* ret,
                             float* out_ble, int B, int L, int E, int V, void* stream);
 int cvcl_embed_meanpool_bwd(const float* d_ret, const int64_t* tok, const int64_t* len, float* d_table,

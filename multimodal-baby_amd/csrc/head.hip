@@ -62,7 +62,10 @@ __global__ __launch_bounds__(512) void embed_meanpool_bwd_kernel(const float* __
             for (int c0 = 0; c0 < total; c0 += EMB_CHUNK) {
                 const int n = min(EMB_CHUNK, total - c0);
                 __syncthreads();
-                for (int i = tid; i < n; i += 512) stok[i] = (int)tok[c0 + i];
+                for (int i = tid; i < n; i += 512) {                    // an id outside [0, V) matches no row (V = gridDim.x); the
+                    const int64_t t = tok[c0 + i];                      // test is made in 64 bits: v + 2^32 must not land in row v
+                    stok[i] = (t >= 0 && t < (int64_t)gridDim.x) ? (int)t : -1;
+                }
                 __syncthreads();
                 int nm = 0;                                             // matches so far (uniform)
                 for (int base = 0; base < n; base += 512) {
