@@ -155,7 +155,9 @@ int cvcl_row_entropy(const float* x, float* out, int R, int N, void* stream);
  *   stats  = per-column sum / sum-of-squares of the stored C (BatchNorm batch statistics of this
  *            conv's output), one partial row per persistent block: stats[grid_m][2][N] f32
  * All matrices row-major with the given leading dimensions (elements).  dtype selects the storage
- * type of A, W, C, R.                                                                            */
+ * type of A, W, C, R.  A bf16 block rounds to bf16 where the unfused modules would store a tensor:
+ * the operand A' after its prologue, the linear's output before the residual is added, and the
+ * stored result, so with a residual C = round(round(act(...)) + R).                               */
 typedef struct {
     const void* A; const void* W; void* C;
     int M, N, K, lda, ldw, ldc;
