@@ -852,6 +852,40 @@ int cvcl_nn_l1_u8(const uint8_t* q, const uint8_t* base, int Nq, int Nb, int C, 
                   uint32_t* best_sums, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * k nearest neighbours and the weighted k-NN vote (csrc/neighbors.hip).  The reference has only the k = 1 case (duplicates.py:805-809,
+ * cvcl_nn_cosine above); the k closest training frames per evaluation frame and the vote over them are the weighted k-NN protocol of
+ * the DINO evaluation (defaults k = 20, T = 0.07).  Both entries validate everything before they enqueue anything (CVCL_EINVAL,
+ * cvcl_last_error names the argument), enqueue on the caller's stream only and use no atomics: two calls give the same bits.
+ *
+ * cvcl_knn_cosine: per query the k eligible base rows of largest cosine, sorted by (cosine descending, index ascending) -> top_cos
+ *   [Nq, k] f32, top_idx [Nq, k] int64 = idx_offset + row; slots beyond the eligible count hold -inf / -1.  q, base, ldq, ldb, eps,
+ *   q_group / base_group, idx_offset as cvcl_nn_cosine.  accumulate = 1: the outputs already hold a valid sorted list (of earlier
+ *   chunks, all of lower index) and are merged with this chunk; chunks in ascending order give the one-shot lists bit for bit.  The
+ *   cosine of a pair is cvcl_nn_cosine's expression on the same tile walk (norms in double, exact fp32 products, chains of 128 k,
+ *   float(double(dot) inv_q inv_b)): it depends neither on k nor on the split nor on the chunking, and k = 1 gives cvcl_nn_cosine's
+ *   result bit for bit.  No queries x base matrix is written: the base tiles are split over workgroups as in cvcl_nn_cosine, and each
+ *   (split, query) keeps ONE sorted list of k (value, row) pairs IN THE CALLER'S WORKSPACE (at k = 256 the 128 lists of a workgroup
+ *   are 256 KiB: they do not fit beside the staging tiles in LDS); only its k-th entry, the threshold, sits in LDS.  A tile's
+ *   cosines go through LDS once; a wave reads the 64 candidates of one query, and only where one of them beats the threshold under
+ *   the tie rule (or the list is not full) it merges them into the list by rank, one read and one write of the list.  A second
+ *   kernel merges the splits' lists, and the previous outputs under accumulate, split by split.  Limits: 1 <= k <= CVCL_KNN_MAX_K.
+ *   Workspace: cvcl_knn_cosine_workspace_bytes (0 = refused sizes) -- the norms and splits x Nq x k pairs.  CVCL_K_HEAD.
+ * cvcl_knn_vote: scores[i][c] = sum over the entries j of list i whose base row has label c of exp(top_cos[i][j] / temperature)
+ *   (temperature == 0: weight 1, the plain majority vote); weights and sums in double, added in list order, one rounding to fp32.
+ *   pred[i] = the arg-max of the double sums, the lowest class on a tie; -1 when no entry counts.  An entry is skipped, never
+ *   dereferenced, if its index is negative or >= Nb, or its label lies outside [0, C).  top_cos / top_idx [Nq, k] as cvcl_knn_cosine
+ *   leaves them, base_label [Nb] int32 -> scores [Nq, C] f32, pred [Nq] int64.  Limits: 1 <= k <= CVCL_KNN_MAX_K,
+ *   1 <= C <= CVCL_KNN_MAX_CLASSES, Nb >= 1, temperature finite and >= 0.  CVCL_K_HEAD. */
+#define CVCL_KNN_MAX_K 256
+#define CVCL_KNN_MAX_CLASSES 4096
+size_t cvcl_knn_cosine_workspace_bytes(int Nq, int Nb, int D, int k);
+int cvcl_knn_cosine(const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, int k, float eps,
+                    const int32_t* q_group, const int32_t* base_group, int64_t idx_offset, int accumulate, float* top_cos,
+                    int64_t* top_idx, void* workspace, size_t workspace_bytes, void* stream);
+int cvcl_knn_vote(const float* top_cos, const int64_t* top_idx, int Nq, int k, const int32_t* base_label, int64_t Nb, int C,
+                  float temperature, float* scores, int64_t* pred, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Image-text alignment analysis (csrc/alignment.hip): the arithmetic of the reference's analysis_cvcl/alignment.py,
  * analysis_cvcl/embeddings.py:106-118 and analysis_tools/representation_similarity.py.  fp32 in and out (the Pearson moments: double),
  * contiguous rows.  Every entry validates everything before it enqueues anything (null pointers, sizes out of range, a workspace that

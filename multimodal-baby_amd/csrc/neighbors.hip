@@ -13,6 +13,8 @@
 //                  than the result, and the rounding of the sum stays at the fp32 class of a pairwise sum (an arg-max among
 //                  near-duplicates needs it: their cosines sit within 1e-3 of 1).  Row norms come from a pass of their own, in
 //                  double; cos = float(double(dot) / (max(|q|, eps) max(|b|, eps))), one rounding.
+// cvcl_knn_cosine  the same tile walk and arithmetic with a sorted list of k per (split, query) in the workspace instead of one running
+//                  best; cvcl_knn_vote sums exp(cos / T) per class over such lists (section "k nearest neighbours" below).
 // cvcl_nn_l1_u8    each WAVE owns TQ x TB (8 x 8) frame pairs: its lanes stride over the pixel dwords of one channel, every lane
 //                  holds TQ + TB loaded 16-byte pieces and TQ TB accumulators, so each loaded dword feeds TB (or TQ) v_sad_u8.
 //                  At the end of a channel a transposing wave reduction (63 exchanges for 64 sums) leaves the total of pair l in
@@ -230,6 +232,356 @@ int cosine_splits(int Nq, int Nb) {
     int s = kCosineTargetWgs / qtiles;
     if (s < 1) s = 1;
     return s < nbt ? s : nbt;
+}
+
+// ================================================================================================================================
+// k nearest neighbours by cosine, and the vote over them
+// ================================================================================================================================
+// cvcl_knn_cosine walks the tiles exactly as nn_cosine_kernel does (the loop below restates it statement for statement, so a pair's
+// cosine has the same bits; nn_cosine_kernel itself is left as it is: its results are pinned bit for bit).  What differs is the
+// epilogue of a tile.  Each (split, query) owns one sorted list of k (value, row) pairs in the workspace, empty slots (-inf, -1) at
+// its end, and its k-th entry -- the threshold -- and its fill count in LDS.  The tile's cosines go to LDS in two halves of 64 base
+// rows (the staging area is free then); wave w takes queries 32 w .. 32 w + 31 of the tile, reads the 64 candidates of one query,
+// one per lane, and where the ballot of "the list is not full, or this beats the threshold" is not empty, merges them BY RANK: a
+// live candidate's new position is the number of list entries and live candidates that beat it, an entry moves down by the number
+// of candidates that beat it, and whatever lands below k is stored.  That is one read and one write of the list per (query, half tile) however many
+// candidates enter: at most 64 wave-uniform steps of at most 5 ballots, which also bounds the worst case (rows arriving in ascending
+// similarity).  A query's list is only ever touched by one wave, and at most once between two barriers of the LDS hand-over.
+constexpr int KNN_PITCH = 68;                    // floats per LDS row of a half tile (64 + 4: 16-byte stores, rows on different banks)
+constexpr int KNN_SLOTS = CVCL_KNN_MAX_K / 64;   // list entries a lane holds during a merge
+static_assert(CT * KNN_PITCH * 4 <= 2 * CT * CROWB, "a half tile of cosines fits in the staging area");
+
+struct KnnDev : CosDev {                         // pval / pidx: the lists, [splits][Nq][k]
+    int k;
+};
+
+template <typename I>
+__device__ __forceinline__ bool knn_better(float v, I i, float bv, I bi) {      // (bitwise: three compares, no branches)
+    return (bool)((int)(v > bv) | ((int)(v == bv) & (int)(i < bi)));
+}
+
+// the value lane `src` (wave-uniform) holds
+__device__ __forceinline__ int knn_lane(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
+__device__ __forceinline__ float knn_lane(float v, int src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
+}
+__device__ __forceinline__ long long knn_lane(long long v, int src) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(unsigned long long)v, src);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), src);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// One wave merges its live candidates (one per lane: `live`, value cv, row ci; `mask` is the ballot of `live`, not empty) into the
+// sorted list lv / li [k], of which *cnt entries are held (the rest are empty and are not read).  Every held entry is read before any
+// is written (the positions depend on all of them).  A step costs one ballot per 64 held entries and one for the candidates, so an
+// empty list is filled at one ballot per candidate.  The pair that lands on position k - 1 is the new threshold.  Rows are distinct,
+// so (value desc, row asc) is a total order and the positions are too.  The caller orders a later merge of the same list behind this
+// one's stores (a barrier, or a fence for a list in LDS).
+template <typename I>
+__device__ __forceinline__ void knn_wave_merge(float* lv, I* li, int k, bool live, float cv, I ci, unsigned long long mask, int lane,
+                                               float* thr_v, I* thr_i, int* cnt) {
+    const int count = __builtin_amdgcn_readfirstlane(*cnt);
+    const int nslots = (count + 63) >> 6, nlive = __popcll(mask);
+    float ev[KNN_SLOTS];
+    I ei[KNN_SLOTS];
+    int er[KNN_SLOTS];
+#pragma unroll
+    for (int j = 0; j < KNN_SLOTS; ++j) {
+        const int p = lane + 64 * j;
+        er[j] = p;
+        ev[j] = p < count ? lv[p] : -INFINITY;
+        ei[j] = p < count ? li[p] : (I)-1;
+    }
+    int cr = 0;
+    while (mask) {
+        const int src = __ffsll(mask) - 1;
+        mask &= mask - 1;
+        const float xv = knn_lane(cv, src);          // (v_readlane: src is wave-uniform)
+        const I xi = knn_lane(ci, src);
+        int ahead = 0;                               // entries and candidates that beat candidate `src`
+#pragma unroll
+        for (int j = 0; j < KNN_SLOTS; ++j) {
+            if (j < nslots) {                        // (wave-uniform)
+                // an empty slot holds -inf and never wins (a live candidate is above -inf); its position is not used
+                const bool wins = knn_better<I>(ev[j], ei[j], xv, xi);
+                ahead += __popcll(__builtin_amdgcn_ballot_w64(wins));
+                er[j] += wins ? 0 : 1;
+            }
+        }
+        // a candidate that is not live is -inf or below the threshold of a full list: it beats no live one
+        ahead += __popcll(__builtin_amdgcn_ballot_w64(knn_better<I>(cv, ci, xv, xi)));
+        cr = lane == src ? ahead : cr;
+    }
+#pragma unroll
+    for (int j = 0; j < KNN_SLOTS; ++j) {
+        if (ei[j] >= 0 && er[j] < k) {
+            if (er[j] != lane + 64 * j) { lv[er[j]] = ev[j]; li[er[j]] = ei[j]; }
+            if (er[j] == k - 1) { *thr_v = ev[j]; *thr_i = ei[j]; }
+        }
+    }
+    if (live && cr < k) {
+        lv[cr] = cv;
+        li[cr] = ci;
+        if (cr == k - 1) { *thr_v = cv; *thr_i = ci; }
+    }
+    if (lane == 0) *cnt = min(k, count + nlive);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
+    __shared__ __attribute__((aligned(16))) char smem[2 * CT * CROWB];
+    __shared__ float s_thr_v[CT];
+    __shared__ int s_thr_i[CT];
+    __shared__ int s_cnt[CT];
+    char* sQ = smem;
+    char* sB = smem + CT * CROWB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave & 1, wn = wave >> 1;
+    const int l31 = lane & 31, h = lane >> 5;
+    const int kc = tid & 7, r0 = tid >> 3;           // staging role: 16-byte chunk kc of rows r0 + 32 j
+    const int m0 = blockIdx.x * CT;
+    const int ktiles = (p.D + CBK - 1) / CBK;
+    const int my_tiles = (int)blockIdx.y < p.nbt ? (p.nbt - 1 - (int)blockIdx.y) / (int)gridDim.y + 1 : 0;
+    const long steps = (long)my_tiles * ktiles;
+
+    // wave w owns the lists of queries m0 + 32 w .. + 31: empty, no threshold
+    if (lane < 32) { s_thr_v[wave * 32 + lane] = -INFINITY; s_thr_i[wave * 32 + lane] = -1; s_cnt[wave * 32 + lane] = 0; }
+    for (int qq = 0; qq < 32; ++qq) {
+        const int m = m0 + wave * 32 + qq;
+        if (m >= p.Nq) break;
+        const long o = ((long)blockIdx.y * p.Nq + m) * p.k;
+        for (int e = lane; e < p.k; e += 64) { p.pval[o + e] = -INFINITY; p.pidx[o + e] = -1; }
+    }
+    __threadfence_block();
+
+    long q_off[4];
+    bool q_ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int m = m0 + r0 + 32 * j;
+        q_ok[j] = m < p.Nq;
+        q_off[j] = (long)m * p.ldq;
+    }
+    f32x4 tq[4], tb[4];
+    auto issue = [&](long s) {                       // global -> registers for step s; rows / k beyond the operands read as 0
+        const int bt = blockIdx.y + (int)(s / ktiles) * gridDim.y, kt = (int)(s % ktiles);
+        const int k = kt * CBK + kc * 4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = bt * CT + r0 + 32 * j;
+            const bool b_ok = n < p.Nb;
+            const float* qr = p.q + q_off[j] + k;
+            const float* br = p.b + (long)n * p.ldb + k;
+            if (VEC) {
+                tq[j] = (q_ok[j] && k < p.D) ? *reinterpret_cast<const f32x4*>(qr) : f32x4{0.f, 0.f, 0.f, 0.f};
+                tb[j] = (b_ok && k < p.D) ? *reinterpret_cast<const f32x4*>(br) : f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    tq[j][e] = (q_ok[j] && k + e < p.D) ? qr[e] : 0.f;
+                    tb[j][e] = (b_ok && k + e < p.D) ? br[e] : 0.f;
+                }
+            }
+        }
+    };
+
+    // this lane's queries: m0 + wm 64 + mt 32 + l31, mt = 0, 1
+    double invq[2];
+    int qg[2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        const int m = m0 + wm * 64 + mt * 32 + l31;
+        invq[mt] = m < p.Nq ? p.invq[m] : 0.0;
+        qg[mt] = (p.qg && m < p.Nq) ? p.qg[m] : 0;
+    }
+
+    if (steps > 0) issue(0);
+    long s = 0;
+    for (int t = 0; t < my_tiles; ++t) {
+        const int nbase = (blockIdx.y + t * gridDim.y) * CT;
+        f32x16 acc[2][2], tot[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; tot[i][j][e] = 0.f; }
+        for (int kt = 0; kt < ktiles; ++kt, ++s) {
+            __syncthreads();                         // the previous step's fragments (or the previous tile's cosines) are read
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                *reinterpret_cast<f32x4*>(sQ + (r0 + 32 * j) * CROWB + kc * 16) = tq[j];
+                *reinterpret_cast<f32x4*>(sB + (r0 + 32 * j) * CROWB + kc * 16) = tb[j];
+            }
+            __syncthreads();
+            if (s + 1 < steps) issue(s + 1);         // the next step's loads fly under the MFMAs
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 fb[2], fq[2];
+#pragma unroll
+                for (int x = 0; x < 2; ++x) {
+                    fb[x] = *reinterpret_cast<const f32x4*>(sB + (wn * 64 + x * 32 + l31) * CROWB + (g * 2 + h) * 16);
+                    fq[x] = *reinterpret_cast<const f32x4*>(sQ + (wm * 64 + x * 32 + l31) * CROWB + (g * 2 + h) * 16);
+                }
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            acc[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[nt][e], fq[mt][e], acc[nt][mt], 0, 0, 0);
+            }
+            if ((kt % CFLUSH) == CFLUSH - 1 || kt == ktiles - 1) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) { tot[i][j][e] += acc[i][j][e]; acc[i][j][e] = 0.f; }
+            }
+        }
+        // epilogue, base rows nbase + wn 64 + nt 32 + .. of both wn at a time: sC[query of the tile][wn 32 + row of the 32]; element
+        // e of tile (nt, mt) is row 8 (e >> 2) + 4 h + (e & 3) against query mt.  A pair that is not eligible goes in as -inf.
+        float* sC = reinterpret_cast<float*>(smem);
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            __syncthreads();                         // the last step's fragments (nt = 1: the first half's candidates) are read
+#pragma unroll
+            for (int eg = 0; eg < 4; ++eg) {
+                double ib[4];
+                int g[4];
+                bool n_ok[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int n = nbase + wn * 64 + nt * 32 + 8 * eg + 4 * h + e;
+                    n_ok[e] = n < p.Nb;
+                    ib[e] = n_ok[e] ? p.invb[n] : 0.0;
+                    g[e] = (p.bg && n_ok[e]) ? p.bg[n] : 0;
+                }
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    f32x4 c4;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float c = (float)((double)tot[nt][mt][eg * 4 + e] * invq[mt] * ib[e]);
+                        c4[e] = (n_ok[e] && g[e] == qg[mt]) ? c : -INFINITY;
+                    }
+                    *reinterpret_cast<f32x4*>(sC + (wm * 64 + mt * 32 + l31) * KNN_PITCH + wn * 32 + 8 * eg + 4 * h) = c4;
+                }
+            }
+            __syncthreads();
+            for (int qq = 0; qq < 32; ++qq) {
+                const int ql = wave * 32 + qq, m = m0 + ql;
+                if (m >= p.Nq) break;
+                const float c = sC[ql * KNN_PITCH + lane];
+                const int n = nbase + (lane >> 5) * 64 + nt * 32 + (lane & 31);
+                const float tv = s_thr_v[ql];
+                const int ti = s_thr_i[ql];
+                const bool live = c > -INFINITY && (ti < 0 || cos_better(c, n, tv, ti));
+                const unsigned long long mask = __ballot(live);
+                if (!mask) continue;
+                const long o = ((long)blockIdx.y * p.Nq + m) * p.k;
+                knn_wave_merge<int>(p.pval + o, p.pidx + o, p.k, live, c, n, mask, lane, s_thr_v + ql, s_thr_i + ql, s_cnt + ql);
+            }
+        }
+    }
+}
+
+// one wave per query: the result list is built in LDS from the previous outputs (accumulate) and the splits' lists, split by split.
+// A split's list is sorted, so its first block of 64 without a live candidate ends it.
+__global__ __launch_bounds__(256) void knn_cosine_merge_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx, int splits,
+                                                               int Nq, int k, long idx_offset, int accumulate, float* top_cos,
+                                                               int64_t* top_idx) {
+    __shared__ float s_v[4][CVCL_KNN_MAX_K];
+    __shared__ long long s_i[4][CVCL_KNN_MAX_K];
+    __shared__ float s_thr_v[4];
+    __shared__ long long s_thr_i[4];
+    __shared__ int s_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = blockIdx.x * 4 + wave;
+    if (m >= Nq) return;                             // (whole waves; no barrier below)
+    float* rv = s_v[wave];
+    long long* ri = s_i[wave];
+    const long o = (long)m * k;
+    int held = 0;
+    for (int e0 = 0; e0 < k; e0 += 64) {             // (whole waves: the ballot counts the held entries of the previous list)
+        const int e = e0 + lane;
+        const float v = (accumulate && e < k) ? top_cos[o + e] : -INFINITY;
+        const long long i = (accumulate && e < k) ? (long long)top_idx[o + e] : -1LL;
+        if (e < k) { rv[e] = v; ri[e] = i; }
+        held += __popcll(__ballot(i >= 0));
+    }
+    __threadfence_block();
+    if (lane == 0) { s_thr_v[wave] = rv[k - 1]; s_thr_i[wave] = ri[k - 1]; s_cnt[wave] = held; }
+    __threadfence_block();
+    for (int s = 0; s < splits; ++s) {
+        const long ps = ((long)s * Nq + m) * k;
+        for (int e0 = 0; e0 < k; e0 += 64) {
+            const int e = e0 + lane;
+            const float c = e < k ? pval[ps + e] : -INFINITY;
+            const int i = e < k ? pidx[ps + e] : -1;
+            const long long gi = idx_offset + i;
+            const float tv = s_thr_v[wave];
+            const long long ti = s_thr_i[wave];
+            const bool live = i >= 0 && (ti < 0 || knn_better<long long>(c, gi, tv, ti));
+            const unsigned long long mask = __ballot(live);
+            if (!mask) break;
+            knn_wave_merge<long long>(rv, ri, k, live, c, gi, mask, lane, s_thr_v + wave, s_thr_i + wave, s_cnt + wave);
+            __threadfence_block();                   // the next merge reads what this one wrote
+        }
+    }
+    for (int e = lane; e < k; e += 64) {
+        top_cos[o + e] = rv[e];
+        top_idx[o + e] = (int64_t)ri[e];
+    }
+}
+
+// one workgroup per query: the first k threads turn the list into (label or -1, weight); every thread then sums its classes over
+// the list in list order
+__global__ __launch_bounds__(256) void knn_vote_kernel(const float* __restrict__ top_cos, const int64_t* __restrict__ top_idx, int k,
+                                                       const int32_t* __restrict__ base_label, long Nb, int C, float temperature,
+                                                       float* __restrict__ scores, int64_t* __restrict__ pred) {
+    __shared__ double s_w[CVCL_KNN_MAX_K];
+    __shared__ int s_l[CVCL_KNN_MAX_K];
+    __shared__ double r_s[256];
+    __shared__ int r_c[256];
+    const int t = threadIdx.x;
+    const long i = blockIdx.x;
+    int lab = -1;
+    if (t < k) {
+        const long idx = (long)top_idx[i * k + t];
+        double w = 0.0;
+        if (idx >= 0 && idx < Nb) {
+            const int l = base_label[idx];
+            if (l >= 0 && l < C) {
+                lab = l;
+                w = temperature > 0.f ? exp((double)top_cos[i * k + t] / (double)temperature) : 1.0;
+            }
+        }
+        s_w[t] = w;
+        s_l[t] = lab;
+    }
+    const int counted = __syncthreads_or(lab >= 0);
+    double bs = -1.0;
+    int bc = -1;
+    for (int c = t; c < C; c += 256) {
+        double sum = 0.0;
+        for (int j = 0; j < k; ++j)
+            if (s_l[j] == c) sum += s_w[j];
+        scores[i * C + c] = (float)sum;
+        if (sum > bs) { bs = sum; bc = c; }
+    }
+    r_s[t] = bs;
+    r_c[t] = bc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o && r_c[t + o] >= 0 && (r_c[t] < 0 || r_s[t + o] > r_s[t] || (r_s[t + o] == r_s[t] && r_c[t + o] < r_c[t]))) {
+            r_s[t] = r_s[t + o];
+            r_c[t] = r_c[t + o];
+        }
+        __syncthreads();
+    }
+    if (t == 0) pred[i] = counted ? (int64_t)r_c[0] : (int64_t)-1;
 }
 
 // ================================================================================================================================
@@ -490,6 +842,71 @@ extern "C" int cvcl_nn_cosine(const float* q, int ldq, const float* base, int ld
     if (p.vec) nn_cosine_kernel<true><<<grid, 256, 0, st>>>(p);
     else nn_cosine_kernel<false><<<grid, 256, 0, st>>>(p);
     nn_cosine_merge_kernel<<<cvcl_div_up(Nq, 256), 256, 0, st>>>(p.pval, p.pidx, splits, Nq, (long)idx_offset, accumulate, best_cos, best_idx);
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
+}
+
+extern "C" size_t cvcl_knn_cosine_workspace_bytes(int Nq, int Nb, int D, int k) {
+    if (Nq < 1 || Nb < 1 || D < 1 || k < 1 || k > CVCL_KNN_MAX_K) return 0;
+    const size_t s = (size_t)cosine_splits(Nq, Nb);
+    return align16((size_t)Nq * 8) + align16((size_t)Nb * 8) + align16(s * Nq * k * 4) + align16(s * Nq * k * 4);
+}
+
+extern "C" int cvcl_knn_cosine(const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, int k, float eps,
+                               const int32_t* q_group, const int32_t* base_group, int64_t idx_offset, int accumulate, float* top_cos,
+                               int64_t* top_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    CVCL_CHECK_ARG(q && base, "cvcl_knn_cosine: null pointer (q / base)");
+    CVCL_CHECK_ARG(top_cos && top_idx, "cvcl_knn_cosine: null pointer (top_cos / top_idx)");
+    CVCL_CHECK_ARG(Nq >= 1, "cvcl_knn_cosine: Nq %d < 1", Nq);
+    CVCL_CHECK_ARG(Nb >= 1, "cvcl_knn_cosine: Nb %d < 1", Nb);
+    CVCL_CHECK_ARG(D >= 1, "cvcl_knn_cosine: D %d < 1", D);
+    CVCL_CHECK_ARG(k >= 1 && k <= CVCL_KNN_MAX_K, "cvcl_knn_cosine: k %d outside 1..%d", k, CVCL_KNN_MAX_K);
+    CVCL_CHECK_ARG(ldq >= D, "cvcl_knn_cosine: ldq %d < D %d", ldq, D);
+    CVCL_CHECK_ARG(ldb >= D, "cvcl_knn_cosine: ldb %d < D %d", ldb, D);
+    CVCL_CHECK_ARG(eps >= 0.f, "cvcl_knn_cosine: eps %g < 0", (double)eps);
+    CVCL_CHECK_ARG((q_group == nullptr) == (base_group == nullptr), "cvcl_knn_cosine: q_group and base_group go together (one is null)");
+    CVCL_CHECK_ARG(idx_offset >= 0, "cvcl_knn_cosine: idx_offset %lld < 0", (long long)idx_offset);
+    CVCL_CHECK_ARG(workspace, "cvcl_knn_cosine: null pointer (workspace)");
+    const size_t need = cvcl_knn_cosine_workspace_bytes(Nq, Nb, D, k);
+    CVCL_CHECK_ARG(workspace_bytes >= need, "cvcl_knn_cosine: workspace_bytes %zu < %zu", workspace_bytes, need);
+    CVCL_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "cvcl_knn_cosine: workspace is not 16-byte aligned");
+
+    const int splits = cosine_splits(Nq, Nb);
+    char* ws = (char*)workspace;
+    KnnDev p;
+    p.q = q; p.b = base; p.ldq = ldq; p.ldb = ldb; p.Nq = Nq; p.Nb = Nb; p.D = D; p.k = k;
+    double* invq = (double*)ws; ws += align16((size_t)Nq * 8);
+    double* invb = (double*)ws; ws += align16((size_t)Nb * 8);
+    p.pval = (float*)ws; ws += align16((size_t)splits * Nq * k * 4);
+    p.pidx = (int32_t*)ws;
+    p.invq = invq; p.invb = invb; p.qg = q_group; p.bg = base_group;
+    p.nbt = cvcl_div_up(Nb, CT);
+    p.vec = (((uintptr_t)q | (uintptr_t)base) & 15) == 0 && ldq % 4 == 0 && ldb % 4 == 0 && D % 4 == 0;
+    hipStream_t st = (hipStream_t)stream;
+    CvclProfScope prof(stream, CVCL_K_HEAD);
+    nn_inv_norm_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(q, ldq, Nq, D, eps, invq);
+    nn_inv_norm_kernel<<<cvcl_div_up(Nb, 4), 256, 0, st>>>(base, ldb, Nb, D, eps, invb);
+    const dim3 grid(cvcl_div_up(Nq, CT), splits);
+    if (p.vec) knn_cosine_kernel<true><<<grid, 256, 0, st>>>(p);
+    else knn_cosine_kernel<false><<<grid, 256, 0, st>>>(p);
+    knn_cosine_merge_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(p.pval, p.pidx, splits, Nq, k, (long)idx_offset, accumulate, top_cos, top_idx);
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
+}
+
+extern "C" int cvcl_knn_vote(const float* top_cos, const int64_t* top_idx, int Nq, int k, const int32_t* base_label, int64_t Nb, int C,
+                             float temperature, float* scores, int64_t* pred, void* stream) {
+    CVCL_CHECK_ARG(top_cos && top_idx, "cvcl_knn_vote: null pointer (top_cos / top_idx)");
+    CVCL_CHECK_ARG(base_label, "cvcl_knn_vote: null pointer (base_label)");
+    CVCL_CHECK_ARG(scores && pred, "cvcl_knn_vote: null pointer (scores / pred)");
+    CVCL_CHECK_ARG(Nq >= 1, "cvcl_knn_vote: Nq %d < 1", Nq);
+    CVCL_CHECK_ARG(k >= 1 && k <= CVCL_KNN_MAX_K, "cvcl_knn_vote: k %d outside 1..%d", k, CVCL_KNN_MAX_K);
+    CVCL_CHECK_ARG(C >= 1 && C <= CVCL_KNN_MAX_CLASSES, "cvcl_knn_vote: C %d outside 1..%d", C, CVCL_KNN_MAX_CLASSES);
+    CVCL_CHECK_ARG(Nb >= 1, "cvcl_knn_vote: Nb %lld < 1", (long long)Nb);
+    CVCL_CHECK_ARG(temperature >= 0.f && temperature <= 3.4028234e38f, "cvcl_knn_vote: temperature %g is negative or not finite",
+                   (double)temperature);
+    CvclProfScope prof(stream, CVCL_K_HEAD);
+    knn_vote_kernel<<<Nq, 256, 0, (hipStream_t)stream>>>(top_cos, top_idx, k, base_label, (long)Nb, C, temperature, scores, pred);
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }

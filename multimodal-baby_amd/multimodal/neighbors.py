@@ -4,7 +4,11 @@ Feature space: ``nearest_cosine`` is F.cosine_similarity on broadcast operands +
 category, :805-809 over all training frames) as one ``cvcl_nn_cosine`` launch sequence that never writes the queries x base
 matrix; ``nn_classify`` and ``same_category_matches`` restate the bookkeeping around it (:795-838, :594-612).  Pixel space:
 ``nearest_pixels`` is the per-frame loop of :988-1002 on 8-bit frames (``cvcl_nn_l1_u8``: exact integer channel sums, the distance
-in double).  ``extract_features`` runs the eval-mode pooled output of the DINO ResNeXt (fc = Identity, utils.py:199-214)."""
+in double).  ``extract_features`` runs the eval-mode pooled output of the DINO ResNeXt (fc = Identity, utils.py:199-214).
+
+Beyond the reference, which has only the nearest frame: ``knn_cosine`` returns the k closest base rows per query (``cvcl_knn_cosine``,
+the same arithmetic), ``knn_vote`` the weighted vote over them (``cvcl_knn_vote``) and ``knn_classify`` the weighted k-NN
+classification that is the training-free evaluation of a DINO encoder (k = 20, T = 0.07)."""
 from __future__ import annotations
 
 import csv
@@ -69,6 +73,60 @@ def nearest_cosine(query, base, query_groups=None, base_groups=None, chunk=None,
         H.check(lib.cvcl_nn_cosine(*H.rows(q), *H.rows(b[s:s + n]), Nq, n, D, eps, H.ptr(qg), None if bg is None else H.ptr(bg[s:]),
                                    s, int(s > 0), H.ptr(cos), H.ptr(idx), H.ptr(ws), ws.numel(), H.stream_ptr()), "cvcl_nn_cosine")
     return cos, idx
+
+
+def knn_cosine(query, base, k, query_groups=None, base_groups=None, chunk=None, eps=COSINE_EPS):
+    """The k base rows of largest cosine per query, sorted by (cosine descending, index ascending): query [Nq, D], base [Nb, D] fp32
+    device rows (a row stride above D is read in place) -> (cos [Nq, k] fp32, idx [Nq, k] int64); slots beyond the number of
+    eligible rows hold -inf and -1.  Groups and ``chunk`` as ``nearest_cosine``; a pair's cosine has ``nearest_cosine``'s bits, so
+    k = 1 is that search.  ``cvcl_knn_cosine``: no queries x base matrix is written."""
+    k = int(k)
+    if not 1 <= k <= H.KNN_MAX_K:
+        raise H.CvclError(f"knn_cosine: k {k} outside 1..{H.KNN_MAX_K}")
+    _device_tensor(query, "knn_cosine(query)")
+    _device_tensor(base, "knn_cosine(base)")
+    q, b = _rows_f32(query, "query"), _rows_f32(base, "base")
+    (Nq, D), Nb = q.shape, b.shape[0]
+    if b.shape[1] != D:
+        raise H.CvclError(f"query rows are {D} wide, base rows {b.shape[1]}")
+    qg, bg = _group_ids(query_groups, base_groups, Nq, Nb, q.device)
+    cos = torch.full((Nq, k), float("-inf"), dtype=torch.float32, device=q.device)
+    idx = torch.full((Nq, k), -1, dtype=torch.int64, device=q.device)
+    if Nq == 0 or Nb == 0:
+        return cos, idx
+    lib = H.lib()
+    step = Nb if chunk is None else max(1, int(chunk))
+    ws = torch.empty(lib.cvcl_knn_cosine_workspace_bytes(Nq, min(step, Nb), D, k), dtype=torch.uint8, device=q.device)
+    for s in range(0, Nb, step):
+        n = min(step, Nb - s)
+        H.check(lib.cvcl_knn_cosine(*H.rows(q), *H.rows(b[s:s + n]), Nq, n, D, k, eps, H.ptr(qg), None if bg is None else H.ptr(bg[s:]),
+                                    s, int(s > 0), H.ptr(cos), H.ptr(idx), H.ptr(ws), ws.numel(), H.stream_ptr()), "cvcl_knn_cosine")
+    return cos, idx
+
+
+def knn_vote(cos, idx, base_labels, n_classes, temperature=0.07):
+    """The weighted k-NN vote of the DINO evaluation over the lists ``knn_cosine`` returns: cos [Nq, k] fp32, idx [Nq, k] int64,
+    base_labels [Nb] integers (all on the device) -> (scores [Nq, n_classes] fp32 = the sum of exp(cos / temperature) over the
+    entries of each class, in double, one rounding; pred [Nq] int64 = its arg-max, the lowest class on a tie, -1 without an entry).
+    ``temperature=0``: every entry weighs 1.  Entries of index -1 (or beyond the labels, or of a label outside the classes) are
+    left out."""
+    _device_tensor(cos, "knn_vote(cos)")
+    _device_tensor(idx, "knn_vote(idx)")
+    _device_tensor(base_labels, "knn_vote(base_labels)")
+    if cos.dim() != 2 or cos.dtype != torch.float32 or idx.shape != cos.shape or idx.dtype != torch.int64:
+        raise H.CvclError(f"knn_vote: expected cos [Nq, k] fp32 and idx [Nq, k] int64, got {tuple(cos.shape)} {cos.dtype} and "
+                          f"{tuple(idx.shape)} {idx.dtype}")
+    if base_labels.dim() != 1:
+        raise H.CvclError(f"knn_vote: base_labels must be [Nb], got {tuple(base_labels.shape)}")
+    Nq, k = cos.shape
+    lab = base_labels.to(torch.int32).contiguous()
+    scores = torch.zeros(Nq, int(n_classes), dtype=torch.float32, device=cos.device)
+    pred = torch.full((Nq,), -1, dtype=torch.int64, device=cos.device)
+    if Nq == 0:
+        return scores, pred
+    H.check(H.lib().cvcl_knn_vote(H.ptr(cos.contiguous()), H.ptr(idx.contiguous()), Nq, k, H.ptr(lab), lab.numel(), int(n_classes),
+                                  float(temperature), H.ptr(scores), H.ptr(pred), H.stream_ptr()), "cvcl_knn_vote")
+    return scores, pred
 
 
 def pixel_weights(std):
@@ -211,6 +269,65 @@ def nn_classify(eval_feats, eval_labels, train_feats, train_labels, eval_filenam
     return res
 
 
+def knn_classify(eval_feats, eval_labels, train_feats, train_labels, k=20, temperature=0.07, eval_filenames=None, train_filenames=None,
+                 neighbours=None, votes=None, chunk=None):
+    """Weighted k-NN classification of every evaluation frame over ALL training frames, the training-free evaluation of a DINO
+    encoder (defaults k = 20, T = 0.07): ``knn_cosine`` + ``knn_vote`` with the bookkeeping of ``nn_classify`` -- categories in
+    sorted order, frames in their given order, accuracies divided by the actual counts.  The classes are the sorted label names of
+    both sets.  ``neighbours`` = a precomputed (cos [Nq, k], idx [Nq, k]) pair replaces the search and ``votes`` = a precomputed
+    (scores [Nq, C], pred [Nq]) pair the vote (with both, the features are not read).  Returns a dict: ``k``, ``temperature``,
+    ``per_category`` {category: accuracy}, ``total``, ``top5_total`` (the true class is among the five classes of largest score
+    that got a vote at all; equal scores go to the lower class) and ``rows`` = [eval_filename, rank (from 1), train_filename,
+    cosine_sim, train_label] for every list entry.  With k = 1 and temperature = 0 ``per_category`` and ``total`` are
+    ``nn_classify``'s."""
+    n_eval = len(eval_labels)
+    eval_filenames = list(eval_filenames) if eval_filenames is not None else [str(i) for i in range(n_eval)]
+    train_filenames = list(train_filenames) if train_filenames is not None else [str(i) for i in range(len(train_labels))]
+    names = sorted({str(x) for labels in (eval_labels, train_labels) for x in labels})
+    eval_ids, train_ids = _label_ids(eval_labels, train_labels)
+    if neighbours is None:
+        neighbours = knn_cosine(eval_feats, train_feats, k, chunk=chunk)
+    if votes is None:
+        cos_d, idx_d = neighbours
+        votes = knn_vote(cos_d, idx_d, torch.from_numpy(train_ids).to(cos_d.device), len(names), temperature)
+    cos, idx = _host_pair(neighbours)
+    scores, pred = _host_pair(votes)
+    res = {"k": int(cos.shape[1]), "temperature": float(temperature), "per_category": {}, "rows": []}
+    total = top5 = 0
+    for cat in sorted({str(x) for x in eval_labels}):
+        members = [j for j in range(n_eval) if str(eval_labels[j]) == cat]
+        hits = 0
+        for j in members:
+            hits += int(pred[j] >= 0 and names[int(pred[j])] == cat)
+            best = np.argsort(-scores[j].astype(np.float64), kind="stable")[:5]
+            top5 += int(any(c == eval_ids[j] and scores[j][c] > 0 for c in best))
+            for r in range(cos.shape[1]):
+                t = int(idx[j][r])
+                if t >= 0:
+                    res["rows"].append([eval_filenames[j], r + 1, train_filenames[t], float(cos[j][r]), str(train_labels[t])])
+        res["per_category"][cat] = hits / len(members)
+        total += hits
+    res["total"] = total / n_eval if n_eval else 0.0
+    res["top5_total"] = top5 / n_eval if n_eval else 0.0
+    return res
+
+
+def knn_summary(res):
+    """the printed lines of a ``knn_classify`` result, in ``classify_summary``'s wording"""
+    lines = [f"{res['k']}-NN accuracy for {cat}: {acc}" for cat, acc in res["per_category"].items()]
+    lines.append(f"{res['k']}-NN total accuracy (T = {res['temperature']}): {res['total']}")
+    lines.append(f"{res['k']}-NN top-5 accuracy: {res['top5_total']}")
+    return lines
+
+
+def write_top_k_matches(rows, path):
+    """top_k_matches.csv, laid out as ``write_matched_results`` does"""
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f, lineterminator="\n")
+        wr.writerow(["eval_filename", "rank", "train_filename", "cosine_sim", "train_label"])
+        wr.writerows(rows)
+
+
 def same_category_matches(eval_feats, eval_labels, train_feats, train_labels, eval_filenames, train_filenames, nearest=None,
                           chunk=None):
     """The top training frame of the SAME category for each evaluation frame (duplicates.py:594-612), as one grouped search:
@@ -346,6 +463,9 @@ def parser():
     ap.add_argument("--precision", default="32", choices=("32", "32-split"))
     ap.add_argument("--batch_size", type=int, default=256)
     ap.add_argument("--chunk", type=int, default=None, help="base frames per search call (default: all at once)")
+    ap.add_argument("--top_k", type=int, default=1, help="above 1: also the k closest training frames per evaluation frame "
+                    "(top_k_matches.csv) and the weighted k-NN classification over them (knn_results.json)")
+    ap.add_argument("--knn_temperature", type=float, default=0.07, help="T of the k-NN vote's weights exp(cos / T); 0: majority vote")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out_dir", default=os.path.join("results", "duplicates"))
     return ap
@@ -394,6 +514,13 @@ def main(args):
             json.dump(matches, f)
         with open(os.path.join(args.out_dir, "nn_features_summary.json"), "w") as f:
             json.dump({"per_category": res["per_category"], "total": res["total"]}, f)
+        if args.top_k > 1:
+            knn = knn_classify(ef, eval_labels, tf, train_labels, args.top_k, args.knn_temperature, eval_names, train_names,
+                               chunk=args.chunk)
+            print("\n".join(knn_summary(knn)))
+            write_top_k_matches(knn["rows"], os.path.join(args.out_dir, "top_k_matches.csv"))
+            with open(os.path.join(args.out_dir, "knn_results.json"), "w") as f:
+                json.dump({key: knn[key] for key in ("k", "temperature", "per_category", "total", "top5_total")}, f)
     if args.space in ("pixels", "both"):
         dist, idx, _ = nearest_pixels(evalf, train, chunk=args.chunk)
         recs = pixel_records(eval_names, eval_labels, train_names, train_labels, dist, idx)
