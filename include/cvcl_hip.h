@@ -947,6 +947,49 @@ int cvcl_token_items_accumulate(const float* outputs, const float* loss, int N, 
 int cvcl_token_topk(const float* logits, const int64_t* labels, long R, int V, int k, int pad_id, float* top_prob, int64_t* top_idx,
                     float* label_prob, float* probs, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * N-gram baseline (csrc/ngram.hip, ABI v7 additive): the back-off n-gram language model of the reference's top-level ngram.py,
+ * which its analysis_tools/processing.py sets beside the LSTM.  All three entries validate everything before they enqueue anything
+ * (CVCL_EINVAL, cvcl_last_error names the argument), enqueue ONE kernel on the caller's stream whatever N, and use no atomics:
+ * two calls on the same inputs give the same bits.  CVCL_K_OTHER.
+ *
+ * Packing: bits = max(1, bit_length(vocab_size - 1)); an (n + 1)-gram is the big-endian concatenation of its token ids in a
+ *   non-negative int64 -- the n context tokens in the high places, the predicted word in the low `bits` -- so the continuations
+ *   of a context are one contiguous run of a sorted table.  1 <= N <= CVCL_NGRAM_MAX_N and N * bits <= 63 (vocab_size 2350: 12
+ *   bits, N <= 5); bit 63 stays free: CVCL_NGRAM_SENTINEL is negative and sorts in front of every key.
+ * y [B, L] int64 token ids (position 0 is <sos>: never predicted, but part of contexts), y_len [B] int64, clamped to [0, L] as the
+ *   reference's slice y[b, :y_len[b]] does.  bad [1] int on the device receives the number of ids outside [0, vocab_size) found
+ *   inside the utterance lengths (ids are read through the bit mask, so such an id cannot reach another key's bits; the caller
+ *   decides what a non-zero count means).  B >= 0, L >= 1, B * L < 2^31.
+ * cvcl_ngram_keys: ngram.py:28-36.  keys [N, B, L] int64: keys[n, b, i] = the packed gram y[b, i - n .. i] where
+ *   max(1, n) <= i < len_b -- the (context, word) pairs NGramModel.update counts at order n -- and CVCL_NGRAM_SENTINEL elsewhere.
+ *   Sorting a [n] slice and run-length counting it gives order n's table; a context's total is the sum over its run.
+ * Tables (the next two entries): order n's grams are gram_key / gram_cnt [gram_off[n], gram_off[n + 1]) (device, int64, keys
+ *   ascending and distinct), its contexts ctx_key (the gram keys >> bits) / ctx_tot [ctx_off[n], ctx_off[n + 1]).  gram_off and
+ *   ctx_off are HOST arrays of N + 1 int64: they start at 0, do not decrease and end at n_gram / n_ctx; an order has contexts
+ *   exactly when it has grams, no more contexts than grams, and order 0 at most one (the empty context, key 0).
+ *   log_alpha = log(alpha), log_1m_alpha = log(1 - alpha), both <= 0.
+ * cvcl_ngram_ce_loss: ngram.py:54-74 (calculate_ce_loss, tokenwise).  loss [B, L - 1] f32, fully written: loss[b, i - 1] =
+ *   -logprob(b, i, y[b, i]) for 1 <= i < len_b, 0 elsewhere.  logprob walks n = min(N - 1, i) .. 0: at n >= 1, if the context
+ *   y[b, i - n .. i) has been counted and the word seen after it, log c(ctx, w) - log c(ctx) + log_1m_alpha ends the walk; at
+ *   n = 0, log(c(w) + 1) - log(total + vocab_size) ends it; every order left behind adds log_alpha.  Two lower-bound binary
+ *   searches per step; log and the sum in double, in the reference's order of additions; one rounding to f32.  One thread per
+ *   position.  With empty tables every scored position gets -(min(N - 1, i) + 1) log_alpha (the reference raises instead).
+ * cvcl_ngram_probs: probs [B, L - 1, vocab_size] f32 = exp(logprob(b, i, w)) for EVERY candidate w, zero rows where the loss is 0;
+ *   the same device function over a grid of (position, word).  B >= 1, L >= 2.  The values are the reference's back-off scores:
+ *   they are NOT normalised over w (the mass alpha leaves for the lower orders is given to every word, seen or not).  The reference
+ *   has no such output (its run_model(..., return_all=True) fails for an n-gram model). */
+enum { CVCL_NGRAM_MAX_N = 8 };
+#define CVCL_NGRAM_SENTINEL (-1)
+int cvcl_ngram_keys(const int64_t* y, const int64_t* y_len, int B, int L, int N, int vocab_size, int64_t* keys, int* bad, void* stream);
+int cvcl_ngram_ce_loss(const int64_t* gram_key, const int64_t* gram_cnt, const int64_t* gram_off, int64_t n_gram,
+                       const int64_t* ctx_key, const int64_t* ctx_tot, const int64_t* ctx_off, int64_t n_ctx, int N, int vocab_size,
+                       double log_alpha, double log_1m_alpha, const int64_t* y, const int64_t* y_len, int B, int L, float* loss,
+                       int* bad, void* stream);
+int cvcl_ngram_probs(const int64_t* gram_key, const int64_t* gram_cnt, const int64_t* gram_off, int64_t n_gram, const int64_t* ctx_key,
+                     const int64_t* ctx_tot, const int64_t* ctx_off, int64_t n_ctx, int N, int vocab_size, double log_alpha,
+                     double log_1m_alpha, const int64_t* y, const int64_t* y_len, int B, int L, float* probs, int* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,15 @@ The reference visits every token in Python -- an ``.item()``, a ``SumData.__add_
 the vocabulary per position.  Here a batch is one LM forward (HIP already), one host CSR build over the (word, tag) keys present
 in it (the tags are host strings) and one cvcl_token_items_accumulate launch; the key tables stay on the device until the end.
 The predictions are one cvcl_token_topk launch per batch.  Items are plain dicts in sorted key order; ``build_series`` turns
-them into the reference's pandas Series.  Attention language models, n-gram models and ``model is None`` are outside the
-implemented path (NotImplementedError), and there is no CPU fallback."""
+them into the reference's pandas Series.
+
+The baseline the reference sets beside the language model, its back-off n-gram model, runs through the same functions: an
+``ngram.NGramModel`` (``build_ngram_model``) is regressional, has ``outputs`` of width 0, takes its token losses from one
+cvcl_ngram_ce_loss launch per batch and its predictions from cvcl_ngram_probs (the back-off score of every word; the reference
+has no predictions for an n-gram).  The smoothing weight is the model's ``alpha`` attribute.
+
+Attention language models and ``model is None`` are outside the implemented path (NotImplementedError), and so is an object
+that only carries the name NGramModel; there is no CPU fallback."""
 import itertools
 from collections import namedtuple
 
@@ -14,6 +21,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import ngram
 from multimodal import _hip as H
 from multimodal import ops
 from multimodal.multimodal_data_module import PAD_TOKEN_ID
@@ -41,7 +49,29 @@ def _language_model_of(model):
 
 def is_regressional(model):
     """Whether the model predicts token l + 1 at position l, so that its loss, logits and labels are shifted by one."""
-    return model is not None and _language_model_of(model).text_encoder.regressional
+    return model is not None and (isinstance(model, ngram.NGramModel) or _language_model_of(model).text_encoder.regressional)
+
+
+def build_ngram_model(N, vocab_size, train_dataloader, device=None):
+    """The n-gram baseline counted over a training set (reference :17-23): one ``update`` per batch."""
+    ngram_model = ngram.NGramModel(N, vocab_size, device=device)
+    for batch in train_dataloader:
+        ngram_model.update(*_tokens_of(batch))
+    return ngram_model
+
+
+def _run_ngram(model, y, y_len, single_example, return_all):
+    """run_model for an n-gram model (reference :165-196): no hidden vectors, the loss of calculate_ce_loss; with ``return_all``
+    logits = log(calculate_probs), no attention maps, labels = y[:, 1:]."""
+    if single_example:
+        y, y_len = y.unsqueeze(0), y_len.unsqueeze(0)
+    loss = F.pad(model.calculate_ce_loss(y, y_len, alpha=model.alpha, tokenwise=True), (1, 0))
+    ret = (torch.zeros(*y.shape, 0, dtype=torch.float32, device=model.device), loss)
+    if return_all:
+        ret = ret + (model.calculate_probs(y, y_len, alpha=model.alpha).log(), None, y[:, 1:].to(device=model.device, dtype=torch.int64))
+    if single_example:
+        ret = map_structure(lambda t: t.squeeze(0) if t is not None else None, ret)
+    return ret
 
 
 def examples_from_batches(batches):
@@ -50,7 +80,10 @@ def examples_from_batches(batches):
 
 def run_model(model, y, y_len, x=None, image_features=None, image_feature_map=None, single_example=False, return_all=False):
     """-> (outputs [B, L, H], loss [B, L]) and, with ``return_all``, (logits, attns, labels) (reference :158-205).  The loss of
-    a regressional model is padded with a leading 0 so that column l belongs to token l."""
+    a regressional model is padded with a leading 0 so that column l belongs to token l.  An n-gram model has H = 0 and takes
+    only ``y`` and ``y_len``."""
+    if isinstance(model, ngram.NGramModel):
+        return _run_ngram(model, y, y_len, single_example, return_all)
     lm = _language_model_of(model)
     if image_feature_map is not None:
         raise NotImplementedError("attention language models are outside the implemented path")
@@ -172,11 +205,14 @@ def get_model_items(model, dataloader, pos_tags, ignore_all_token_items=True):
     -> ModelItems(losses: per utterance its token losses (numpy, trimmed to its length); all_token_items: None;
     token_pos_items: {Key(token_id, pos): SumData}; token_items: {Key(token_id, majority pos): SumData} with the word's embedding
     row when the model has a ``text_encoder``).  Only ``ignore_all_token_items=True`` is supported: keeping every token's hidden
-    vector on the host is what this path exists to avoid."""
+    vector on the host is what this path exists to avoid.  For an n-gram model the vectors have shape (0,) (the reference's
+    hidden_dim = 0; its own n-gram branch reads ``y`` before assigning it, :306) and there is no embedding."""
     if not ignore_all_token_items:
         raise NotImplementedError("all_token_items (one SumData per token on the host) is not kept on the HIP path")
-    _language_model_of(model)
-    device = get_model_device(model)
+    is_ngram = isinstance(model, ngram.NGramModel)
+    if not is_ngram:
+        _language_model_of(model)
+    device = model.device if is_ngram else get_model_device(model)
     tables = None
     key_slots = {}
     losses_dev, lengths = [], []
@@ -184,6 +220,8 @@ def get_model_items(model, dataloader, pos_tags, ignore_all_token_items=True):
     for (y, y_len, outputs, loss), tags in _tagged_batches(runs, pos_tags):
         n_cols = min(outputs.shape[1], loss.shape[1])        # the LSTM trims its outputs to the batch's longest utterance
         B = len(tags)                                        # (fewer than the batch when the tag lists run out)
+        if is_ngram:                                         # cvcl_token_items_accumulate wants H >= 1: one zero column, cut off below
+            outputs = outputs.new_zeros(outputs.shape[0], n_cols, 1)
         outputs = outputs[:B, :n_cols].contiguous()
         loss = loss[:B, :n_cols].contiguous()
         if tables is None:
@@ -202,6 +240,8 @@ def get_model_items(model, dataloader, pos_tags, ignore_all_token_items=True):
     if key_slots:
         n = len(key_slots)
         vector, loss_sum, cnt = tables.vector[:n].cpu().numpy(), tables.loss[:n].cpu().numpy(), tables.cnt[:n].cpu().numpy()
+        if is_ngram:
+            vector = vector[:, :0]
         for key in sorted(key_slots):
             s = key_slots[key]
             token_pos_items[key] = SumData(cnt=np.array(cnt[s]), loss=np.array(loss_sum[s]), vector=vector[s], embedding=None)
@@ -243,6 +283,9 @@ def build_series_from_pairs(pairs):
 def _predictions(model, dataloader, pos_tags, top_k, want_probs):
     """Per batch: (index of its first utterance, y host [B, L], tags, label_prob, top_prob, top_idx, probs or None), each
     row-aligned with y (leading zero row for regressional models included)."""
+    if isinstance(model, ngram.NGramModel):
+        yield from _ngram_predictions(model, dataloader, pos_tags, top_k, want_probs)
+        return
     regressional = is_regressional(model)
     runs = ((_tokens_of(batch)[0], ret) for batch, *ret in run_model_on_batches(model, dataloader, return_all=True))
     first = 0
@@ -262,6 +305,24 @@ def _predictions(model, dataloader, pos_tags, top_k, want_probs):
         yield (first, y.cpu().numpy(), tags, label_prob.cpu().numpy(), top_prob.cpu().numpy(), top_idx.cpu().numpy(),
                None if probs is None else probs.cpu().numpy())
         first += len(tags)
+
+
+def _ngram_predictions(model, dataloader, pos_tags, top_k, want_probs):
+    """_predictions for an n-gram model: the rows are calculate_probs' back-off scores (not normalised over the words), with
+    the leading zero row.  The ``top_k`` best come from a stable descending sort on the device, which keeps equal scores in
+    index order -- torch.topk promises no order among equal values, and words an order has not seen share one score."""
+    if not 1 <= top_k <= model.vocab_size:
+        raise ValueError(f"top_k {top_k} outside [1, vocab_size = {model.vocab_size}]")
+    first = 0
+    with torch.no_grad():
+        for (y, y_len), tags in _tagged_batches((_tokens_of(batch) for batch in dataloader), pos_tags):
+            probs = F.pad(model.calculate_probs(y, y_len, alpha=model.alpha), (0, 0, 1, 0))
+            order = torch.sort(probs, dim=-1, descending=True, stable=True)
+            labels = y.to(device=probs.device, dtype=torch.int64).clamp(0, model.vocab_size - 1)     # (padding may hold anything)
+            label_prob = probs.gather(2, labels.unsqueeze(-1)).squeeze(-1)
+            yield (first, torch.as_tensor(y).cpu().numpy(), tags, label_prob.cpu().numpy(), order.values[..., :top_k].cpu().numpy(),
+                   order.indices[..., :top_k].cpu().numpy(), probs.cpu().numpy() if want_probs else None)
+            first += len(tags)
 
 
 def _tagged_positions(y, tags, n_cols):

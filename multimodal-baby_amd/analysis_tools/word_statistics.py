@@ -6,7 +6,12 @@ over a data split (analysis_tools.processing on the HIP path).
 Writes into --out: ``token_items.csv`` (token, pos, cnt, mean_loss, ppl; one row per word under its majority tag, sorted by token id),
 ``token_vectors.npy`` (the words' mean hidden vectors, in the row order of the csv), ``losses.npy`` (per utterance its token losses,
 zero-padded to the longest) and ``top_predictions.csv`` (per tagged position: utterance, position, token, pos, label_prob and the
-top_k predicted words with their probabilities)."""
+top_k predicted words with their probabilities).
+
+``--ngram N [--ngram_alpha 0.1]`` sets the reference's baseline beside them: a back-off N-gram model (ngram.NGramModel) counted on
+the TRAIN split of the same data module and run over --split, written as ``ngram_token_items.csv`` (the columns of
+token_items.csv), ``ngram_losses.npy`` and ``ngram_top_predictions.csv`` (its "probabilities" are back-off scores, not normalised
+over the words).  Without --ngram the outputs are the four files above and nothing else."""
 import argparse
 import csv
 import json
@@ -33,6 +38,8 @@ def parser():
     ap.add_argument("--top_k", type=int, default=5)
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--ngram", type=int, default=0, metavar="N", help="also run a back-off N-gram baseline counted on the train split")
+    ap.add_argument("--ngram_alpha", type=float, default=0.1, help="the share of probability the n-gram leaves to the lower orders")
     ap.add_argument("--out", default=os.path.join("results", "word_statistics"))
     return ap
 
@@ -61,29 +68,35 @@ def build_model(args, device):
     return lit
 
 
-def split_batches(args):
+def data_module(args):
     from multimodal.multimodal_data_module import SyntheticDataModule
     data = SyntheticDataModule(argparse.Namespace(batch_size=args.batch_size, val_batch_size=args.batch_size, num_workers=0,
                                                   seed=args.seed))
     data.setup()
+    return data
+
+
+def split_batches(args):
+    data = data_module(args)
     loader = (data.val_dataloader() if args.split == "val" else data.test_dataloader())[0]       # the pair batches, not the trials
     return list(loader)
 
 
-def write_results(out_dir, items, predictions, idx2word, top_k):
+def write_results(out_dir, items, predictions, idx2word, top_k, prefix="", with_vectors=True):
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "token_items.csv"), "w", newline="") as f:
+    with open(os.path.join(out_dir, prefix + "token_items.csv"), "w", newline="") as f:
         wr = csv.writer(f)
         wr.writerow(["token", "pos", "cnt", "mean_loss", "ppl"])
         for key, value in items.token_items.items():
             wr.writerow([idx2word[key.token_id], key.pos, int(value.cnt), repr(float(value.mean_loss)), repr(float(value.ppl))])
-    vectors = [value.mean_vector for value in items.token_items.values()]
-    np.save(os.path.join(out_dir, "token_vectors.npy"), np.stack(vectors) if vectors else np.zeros((0, 0), dtype=np.float32))
+    if with_vectors:
+        vectors = [value.mean_vector for value in items.token_items.values()]
+        np.save(os.path.join(out_dir, prefix + "token_vectors.npy"), np.stack(vectors) if vectors else np.zeros((0, 0), dtype=np.float32))
     losses = np.zeros((len(items.losses), max((len(l) for l in items.losses), default=0)), dtype=np.float32)
     for r, l in enumerate(items.losses):
         losses[r, :len(l)] = l
-    np.save(os.path.join(out_dir, "losses.npy"), losses)
-    with open(os.path.join(out_dir, "top_predictions.csv"), "w", newline="") as f:
+    np.save(os.path.join(out_dir, prefix + "losses.npy"), losses)
+    with open(os.path.join(out_dir, prefix + "top_predictions.csv"), "w", newline="") as f:
         wr = csv.writer(f)
         wr.writerow(["utterance", "position", "token", "pos", "label_prob"] +
                     [c for j in range(top_k) for c in (f"top{j + 1}", f"top{j + 1}_prob")])
@@ -110,4 +123,13 @@ def main(args):
     n_tok = sum(int(v.cnt) for v in items.token_items.values())
     print(f"{len(items.losses)} utterances, {n_tok} tagged positions, {len(items.token_pos_items)} (word, tag) keys, "
           f"{len(items.token_items)} words -> {args.out}")
+    if args.ngram:
+        baseline = P.build_ngram_model(args.ngram, len(idx2word), data_module(args).train_dataloader(), device=dev)
+        baseline.alpha = args.ngram_alpha
+        ngram_items = P.get_model_items(baseline, batches, pos_tags)
+        ngram_top = list(P.iter_top_predictions(baseline, batches, pos_tags, top_k=args.top_k))
+        write_results(args.out, ngram_items, ngram_top, idx2word, args.top_k, prefix="ngram_", with_vectors=False)
+        n_tok = sum(len(l) - 1 for l in ngram_items.losses if len(l))
+        mean = sum(float(l.sum()) for l in ngram_items.losses) / max(n_tok, 1)
+        print(f"{args.ngram}-gram baseline (alpha {args.ngram_alpha}): mean token loss {mean:.4f} over {n_tok} tokens -> {args.out}")
     return items

@@ -5,6 +5,8 @@ path is a libcvcl_hip kernel.  Functions raise if handed CPU tensors (no fallbac
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import _hip as H
@@ -493,3 +495,58 @@ def token_topk(logits, labels, k, pad_id=0, want_probs=False):
     H.check(H.lib().cvcl_token_topk(H.ptr(logits, _F), H.ptr(labels, torch.int64), R, V, int(k), int(pad_id), H.ptr(top_prob),
                                     H.ptr(top_idx), H.ptr(label_prob), H.ptr(probs), H.stream_ptr()), "cvcl_token_topk")
     return top_prob, top_idx, label_prob, probs
+
+
+def ngram_keys(y, y_len, N, vocab_size):
+    """The packed (n + 1)-grams NGramModel.update counts (reference ngram.py:28-36), every order in one launch -> (keys [N, B, L]
+    int64 with CVCL_NGRAM_SENTINEL where nothing is counted, bad [1] int32: the ids outside [0, vocab_size) inside the lengths).
+    ``y`` [B, L] and ``y_len`` [B] are contiguous int64 device tensors."""
+    B, L = y.shape
+    if y_len.numel() != B:
+        raise ValueError("ngram_keys: one length per utterance")
+    H.ptr(y, torch.int64)                                   # refuses CPU tensors before anything is allocated beside them
+    keys = torch.empty(N, B, L, dtype=torch.int64, device=y.device)
+    bad = torch.empty(1, dtype=torch.int32, device=y.device)
+    H.check(H.lib().cvcl_ngram_keys(H.ptr(y, torch.int64), H.ptr(y_len, torch.int64), B, L, int(N), int(vocab_size), H.ptr(keys),
+                                    H.ptr(bad), H.stream_ptr()), "cvcl_ngram_keys")
+    return keys, bad
+
+
+def _ngram_score(entry, tables, N, vocab_size, log_alpha, log_1m_alpha, y, y_len, out):
+    gram_key, gram_cnt, gram_off, ctx_key, ctx_tot, ctx_off = tables
+    if len(gram_off) != N + 1 or len(ctx_off) != N + 1:
+        raise ValueError(f"{entry}: N + 1 offsets per table")
+    B, L = y.shape
+    if y_len.numel() != B:
+        raise ValueError(f"{entry}: one length per utterance")
+    i64 = torch.int64
+    bad = torch.empty(1, dtype=torch.int32, device=y.device)
+    H.check(getattr(H.lib(), entry)(
+        H.ptr(gram_key, i64), H.ptr(gram_cnt, i64), (C.c_int64 * (N + 1))(*gram_off), gram_key.numel(), H.ptr(ctx_key, i64),
+        H.ptr(ctx_tot, i64), (C.c_int64 * (N + 1))(*ctx_off), ctx_key.numel(), int(N), int(vocab_size), float(log_alpha),
+        float(log_1m_alpha), H.ptr(y, i64), H.ptr(y_len, i64), B, L, H.ptr(out, _F), H.ptr(bad), H.stream_ptr()), entry)
+    return out, bad
+
+
+def ngram_ce_loss(tables, N, vocab_size, log_alpha, log_1m_alpha, y, y_len, out=None):
+    """The token losses of the back-off n-gram model (reference ngram.py:54-74) -> (loss [B, L - 1] f32, zeros outside the
+    utterances; bad [1] int32).  ``tables`` = (gram_key, gram_cnt, gram_off, ctx_key, ctx_tot, ctx_off): the sorted tables of all
+    orders concatenated (int64, on the device) and their N + 1 offsets each (host ints), as cvcl_hip.h "N-gram baseline" lays
+    them out.  ``out``: the [B, L - 1] f32 buffer to write (every element is written)."""
+    B, L = y.shape
+    H.ptr(y, torch.int64)
+    loss = torch.empty(B, L - 1, dtype=_F, device=y.device) if out is None else out
+    if tuple(loss.shape) != (B, L - 1):
+        raise ValueError("ngram_ce_loss: out must be [B, L - 1]")
+    return _ngram_score("cvcl_ngram_ce_loss", tables, N, vocab_size, log_alpha, log_1m_alpha, y, y_len, loss)
+
+
+def ngram_probs(tables, N, vocab_size, log_alpha, log_1m_alpha, y, y_len, out=None):
+    """exp of the same back-off score for every candidate word -> (probs [B, L - 1, vocab_size] f32, zero rows outside the
+    utterances; bad [1] int32).  Not normalised over the words."""
+    B, L = y.shape
+    H.ptr(y, torch.int64)
+    probs = torch.empty(B, L - 1, vocab_size, dtype=_F, device=y.device) if out is None else out
+    if tuple(probs.shape) != (B, L - 1, vocab_size):
+        raise ValueError("ngram_probs: out must be [B, L - 1, vocab_size]")
+    return _ngram_score("cvcl_ngram_probs", tables, N, vocab_size, log_alpha, log_1m_alpha, y, y_len, probs)
