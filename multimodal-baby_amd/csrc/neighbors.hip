@@ -13,8 +13,9 @@
 //                  than the result, and the rounding of the sum stays at the fp32 class of a pairwise sum (an arg-max among
 //                  near-duplicates needs it: their cosines sit within 1e-3 of 1).  Row norms come from a pass of their own, in
 //                  double; cos = float(double(dot) / (max(|q|, eps) max(|b|, eps))), one rounding.
-// cvcl_knn_cosine  the same tile walk and arithmetic with a sorted list of k per (split, query) in the workspace instead of one running
-//                  best; cvcl_knn_vote sums exp(cos / T) per class over such lists (section "k nearest neighbours" below).
+// cvcl_knn_cosine  the same device function (cosine_tile_walk) with another tile epilogue: a sorted list of k per (split, query) in the
+//                  workspace instead of one running best, so a pair's cosine has cvcl_nn_cosine's bits by construction;
+//                  cvcl_knn_vote sums exp(cos / T) per class over such lists (section "k nearest neighbours" below).
 // cvcl_nn_l1_u8    each WAVE owns TQ x TB (8 x 8) frame pairs: its lanes stride over the pixel dwords of one channel, every lane
 //                  holds TQ + TB loaded 16-byte pieces and TQ TB accumulators, so each loaded dword feeds TB (or TQ) v_sad_u8.
 //                  At the end of a channel a transposing wave reduction (63 exchanges for 64 sums) leaves the total of pair l in
@@ -57,157 +58,6 @@ __global__ __launch_bounds__(256) void nn_inv_norm_kernel(const float* __restric
     if (lane == 0) out[row] = 1.0 / fmax(sqrt(s), (double)eps);
 }
 
-__device__ __forceinline__ bool cos_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
-template <bool VEC>
-__global__ __launch_bounds__(256, 2) void nn_cosine_kernel(CosDev p) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * CT * CROWB];
-    char* sQ = smem;
-    char* sB = smem + CT * CROWB;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int kc = tid & 7, r0 = tid >> 3;           // staging role: 16-byte chunk kc of rows r0 + 32 j
-    const int m0 = blockIdx.x * CT;
-    const int ktiles = (p.D + CBK - 1) / CBK;
-    const int my_tiles = (int)blockIdx.y < p.nbt ? (p.nbt - 1 - (int)blockIdx.y) / (int)gridDim.y + 1 : 0;
-    const long steps = (long)my_tiles * ktiles;
-
-    long q_off[4];
-    bool q_ok[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int m = m0 + r0 + 32 * j;
-        q_ok[j] = m < p.Nq;
-        q_off[j] = (long)m * p.ldq;
-    }
-    f32x4 tq[4], tb[4];
-    auto issue = [&](long s) {                       // global -> registers for step s; rows / k beyond the operands read as 0
-        const int bt = blockIdx.y + (int)(s / ktiles) * gridDim.y, kt = (int)(s % ktiles);
-        const int k = kt * CBK + kc * 4;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = bt * CT + r0 + 32 * j;
-            const bool b_ok = n < p.Nb;
-            const float* qr = p.q + q_off[j] + k;
-            const float* br = p.b + (long)n * p.ldb + k;
-            if (VEC) {
-                tq[j] = (q_ok[j] && k < p.D) ? *reinterpret_cast<const f32x4*>(qr) : f32x4{0.f, 0.f, 0.f, 0.f};
-                tb[j] = (b_ok && k < p.D) ? *reinterpret_cast<const f32x4*>(br) : f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    tq[j][e] = (q_ok[j] && k + e < p.D) ? qr[e] : 0.f;
-                    tb[j][e] = (b_ok && k + e < p.D) ? br[e] : 0.f;
-                }
-            }
-        }
-    };
-
-    // this lane's queries: m0 + wm 64 + mt 32 + l31, mt = 0, 1
-    float best_v[2] = {-INFINITY, -INFINITY};
-    int best_i[2] = {-1, -1};
-    double invq[2];
-    int qg[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const int m = m0 + wm * 64 + mt * 32 + l31;
-        invq[mt] = m < p.Nq ? p.invq[m] : 0.0;
-        qg[mt] = (p.qg && m < p.Nq) ? p.qg[m] : 0;
-    }
-
-    if (steps > 0) issue(0);
-    long s = 0;
-    for (int t = 0; t < my_tiles; ++t) {
-        const int nbase = (blockIdx.y + t * gridDim.y) * CT;
-        f32x16 acc[2][2], tot[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; tot[i][j][e] = 0.f; }
-        for (int kt = 0; kt < ktiles; ++kt, ++s) {
-            __syncthreads();                         // the previous step's fragments are read
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                *reinterpret_cast<f32x4*>(sQ + (r0 + 32 * j) * CROWB + kc * 16) = tq[j];
-                *reinterpret_cast<f32x4*>(sB + (r0 + 32 * j) * CROWB + kc * 16) = tb[j];
-            }
-            __syncthreads();
-            if (s + 1 < steps) issue(s + 1);         // the next step's loads fly under the MFMAs
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                // lane half h owns k = 4 (2 g + h) .. + 3 of the step and feeds element e to the e-th 32x32x2 product: the
-                // contraction index may be permuted freely as long as both operands agree
-                f32x4 fb[2], fq[2];
-#pragma unroll
-                for (int x = 0; x < 2; ++x) {
-                    fb[x] = *reinterpret_cast<const f32x4*>(sB + (wn * 64 + x * 32 + l31) * CROWB + (g * 2 + h) * 16);
-                    fq[x] = *reinterpret_cast<const f32x4*>(sQ + (wm * 64 + x * 32 + l31) * CROWB + (g * 2 + h) * 16);
-                }
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            acc[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(fb[nt][e], fq[mt][e], acc[nt][mt], 0, 0, 0);
-            }
-            if ((kt % CFLUSH) == CFLUSH - 1 || kt == ktiles - 1) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) { tot[i][j][e] += acc[i][j][e]; acc[i][j][e] = 0.f; }
-            }
-        }
-        // epilogue: element e of tile (nt, mt) is base row nbase + wn 64 + nt 32 + 8 (e >> 2) + 4 h + (e & 3) against query mt
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int n = nbase + wn * 64 + nt * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
-                const bool n_ok = n < p.Nb;
-                const double ib = n_ok ? p.invb[n] : 0.0;
-                const int g = (p.bg && n_ok) ? p.bg[n] : 0;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const float c = (float)((double)tot[nt][mt][e] * invq[mt] * ib);
-                    if (n_ok && g == qg[mt] && cos_better(c, n, best_v[mt], best_i[mt])) { best_v[mt] = c; best_i[mt] = n; }
-                }
-            }
-    }
-    // lane halves, then the two waves of a query half (through LDS), then one partial per query and split
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const float ov = __shfl_xor(best_v[mt], 32, 64);
-        const int oi = __shfl_xor(best_i[mt], 32, 64);
-        if (oi >= 0 && cos_better(ov, oi, best_v[mt], best_i[mt])) { best_v[mt] = ov; best_i[mt] = oi; }
-    }
-    __syncthreads();
-    float* rv = reinterpret_cast<float*>(smem);                  // [2][128]
-    int* ri = reinterpret_cast<int*>(smem + 2 * CT * 4);
-    if (h == 0) {
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            rv[wn * CT + wm * 64 + mt * 32 + l31] = best_v[mt];
-            ri[wn * CT + wm * 64 + mt * 32 + l31] = best_i[mt];
-        }
-    }
-    __syncthreads();
-    if (tid < CT && m0 + tid < p.Nq) {
-        float v = rv[tid];
-        int i = ri[tid];
-        const float v1 = rv[CT + tid];
-        const int i1 = ri[CT + tid];
-        if (i1 >= 0 && cos_better(v1, i1, v, i)) { v = v1; i = i1; }
-        p.pval[(long)blockIdx.y * p.Nq + m0 + tid] = v;
-        p.pidx[(long)blockIdx.y * p.Nq + m0 + tid] = i;
-    }
-}
-
 __global__ __launch_bounds__(256) void nn_cosine_merge_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx, int splits,
                                                               int Nq, long idx_offset, int accumulate, float* __restrict__ best_cos,
                                                               int64_t* __restrict__ best_idx) {
@@ -235,11 +85,11 @@ int cosine_splits(int Nq, int Nb) {
 }
 
 // ================================================================================================================================
-// k nearest neighbours by cosine, and the vote over them
+// the tile walk of both cosine searches, the lists of the k nearest, and the vote over them
 // ================================================================================================================================
-// cvcl_knn_cosine walks the tiles exactly as nn_cosine_kernel does (the loop below restates it statement for statement, so a pair's
-// cosine has the same bits; nn_cosine_kernel itself is left as it is: its results are pinned bit for bit).  What differs is the
-// epilogue of a tile.  Each (split, query) owns one sorted list of k (value, row) pairs in the workspace, empty slots (-inf, -1) at
+// nn_cosine_kernel and knn_cosine_kernel are one tile walk (cosine_tile_walk below: staging, MFMA products, chains, scaling), so a
+// pair's cosine has the same bits in both, and k = 1 of cvcl_knn_cosine is cvcl_nn_cosine's result.  What differs is the epilogue
+// of a tile.  Each (split, query) owns one sorted list of k (value, row) pairs in the workspace, empty slots (-inf, -1) at
 // its end, and its k-th entry -- the threshold -- and its fill count in LDS.  The tile's cosines go to LDS in two halves of 64 base
 // rows (the staging area is free then); wave w takes queries 32 w .. 32 w + 31 of the tile, reads the 64 candidates of one query,
 // one per lane, and where the ballot of "the list is not full, or this beats the threshold" is not empty, merges them BY RANK: a
@@ -327,12 +177,14 @@ __device__ __forceinline__ void knn_wave_merge(float* lv, I* li, int k, bool liv
     if (lane == 0) *cnt = min(k, count + nlive);
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
+// The tile walk of both cosine searches: this workgroup's query tile against the base tiles blockIdx.y, + gridDim.y, ...  TOPK
+// chooses what becomes of a finished tile: the running best per lane (cvcl_nn_cosine; reduced over lane halves and waves and written
+// per split at the end), or the sorted lists of `topk` entries (cvcl_knn_cosine; s_thr_v / s_thr_i / s_cnt [CT] in LDS are the lists'
+// thresholds and fill counts, null for the arg-max).  Everything up to tot[][] is one piece of code for both, which is why a pair's
+// cosine has the same bits in either search, whatever k, split or chunk.
+template <bool VEC, bool TOPK>
+__device__ __forceinline__ void cosine_tile_walk(const CosDev& p, int topk, float* s_thr_v, int* s_thr_i, int* s_cnt) {
     __shared__ __attribute__((aligned(16))) char smem[2 * CT * CROWB];
-    __shared__ float s_thr_v[CT];
-    __shared__ int s_thr_i[CT];
-    __shared__ int s_cnt[CT];
     char* sQ = smem;
     char* sB = smem + CT * CROWB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -344,15 +196,17 @@ __global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
     const int my_tiles = (int)blockIdx.y < p.nbt ? (p.nbt - 1 - (int)blockIdx.y) / (int)gridDim.y + 1 : 0;
     const long steps = (long)my_tiles * ktiles;
 
-    // wave w owns the lists of queries m0 + 32 w .. + 31: empty, no threshold
-    if (lane < 32) { s_thr_v[wave * 32 + lane] = -INFINITY; s_thr_i[wave * 32 + lane] = -1; s_cnt[wave * 32 + lane] = 0; }
-    for (int qq = 0; qq < 32; ++qq) {
-        const int m = m0 + wave * 32 + qq;
-        if (m >= p.Nq) break;
-        const long o = ((long)blockIdx.y * p.Nq + m) * p.k;
-        for (int e = lane; e < p.k; e += 64) { p.pval[o + e] = -INFINITY; p.pidx[o + e] = -1; }
+    if constexpr (TOPK) {
+        // wave w owns the lists of queries m0 + 32 w .. + 31: empty, no threshold
+        if (lane < 32) { s_thr_v[wave * 32 + lane] = -INFINITY; s_thr_i[wave * 32 + lane] = -1; s_cnt[wave * 32 + lane] = 0; }
+        for (int qq = 0; qq < 32; ++qq) {
+            const int m = m0 + wave * 32 + qq;
+            if (m >= p.Nq) break;
+            const long o = ((long)blockIdx.y * p.Nq + m) * topk;
+            for (int e = lane; e < topk; e += 64) { p.pval[o + e] = -INFINITY; p.pidx[o + e] = -1; }
+        }
+        __threadfence_block();
     }
-    __threadfence_block();
 
     long q_off[4];
     bool q_ok[4];
@@ -386,6 +240,8 @@ __global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
     };
 
     // this lane's queries: m0 + wm 64 + mt 32 + l31, mt = 0, 1
+    float best_v[2] = {-INFINITY, -INFINITY};        // (arg-max only)
+    int best_i[2] = {-1, -1};
     double invq[2];
     int qg[2];
 #pragma unroll
@@ -407,7 +263,7 @@ __global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; tot[i][j][e] = 0.f; }
         for (int kt = 0; kt < ktiles; ++kt, ++s) {
-            __syncthreads();                         // the previous step's fragments (or the previous tile's cosines) are read
+            __syncthreads();                         // the previous step's fragments (top-k: or the previous tile's cosines) are read
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 *reinterpret_cast<f32x4*>(sQ + (r0 + 32 * j) * CROWB + kc * 16) = tq[j];
@@ -417,6 +273,8 @@ __global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
             if (s + 1 < steps) issue(s + 1);         // the next step's loads fly under the MFMAs
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
+                // lane half h owns k = 4 (2 g + h) .. + 3 of the step and feeds element e to the e-th 32x32x2 product: the
+                // contraction index may be permuted freely as long as both operands agree
                 f32x4 fb[2], fq[2];
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
@@ -440,51 +298,112 @@ __global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
                         for (int e = 0; e < 16; ++e) { tot[i][j][e] += acc[i][j][e]; acc[i][j][e] = 0.f; }
             }
         }
-        // epilogue, base rows nbase + wn 64 + nt 32 + .. of both wn at a time: sC[query of the tile][wn 32 + row of the 32]; element
-        // e of tile (nt, mt) is row 8 (e >> 2) + 4 h + (e & 3) against query mt.  A pair that is not eligible goes in as -inf.
-        float* sC = reinterpret_cast<float*>(smem);
+        if constexpr (!TOPK) {
+            // epilogue: element e of tile (nt, mt) is base row nbase + wn 64 + nt 32 + 8 (e >> 2) + 4 h + (e & 3) against query mt
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            __syncthreads();                         // the last step's fragments (nt = 1: the first half's candidates) are read
+            for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-            for (int eg = 0; eg < 4; ++eg) {
-                double ib[4];
-                int g[4];
-                bool n_ok[4];
+                for (int e = 0; e < 16; ++e) {
+                    const int n = nbase + wn * 64 + nt * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
+                    const bool n_ok = n < p.Nb;
+                    const double ib = n_ok ? p.invb[n] : 0.0;
+                    const int g = (p.bg && n_ok) ? p.bg[n] : 0;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int n = nbase + wn * 64 + nt * 32 + 8 * eg + 4 * h + e;
-                    n_ok[e] = n < p.Nb;
-                    ib[e] = n_ok[e] ? p.invb[n] : 0.0;
-                    g[e] = (p.bg && n_ok[e]) ? p.bg[n] : 0;
+                    for (int mt = 0; mt < 2; ++mt) {
+                        const float c = (float)((double)tot[nt][mt][e] * invq[mt] * ib);
+                        if (n_ok && g == qg[mt] && cvcl_better(c, n, best_v[mt], best_i[mt])) { best_v[mt] = c; best_i[mt] = n; }
+                    }
                 }
+        } else {
+            // epilogue, base rows nbase + wn 64 + nt 32 + .. of both wn at a time: sC[query of the tile][wn 32 + row of the 32];
+            // element e of tile (nt, mt) is row 8 (e >> 2) + 4 h + (e & 3) against query mt.  A pair that is not eligible goes in as
+            // -inf.
+            float* sC = reinterpret_cast<float*>(smem);
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    f32x4 c4;
+            for (int nt = 0; nt < 2; ++nt) {
+                __syncthreads();                     // the last step's fragments (nt = 1: the first half's candidates) are read
+#pragma unroll
+                for (int eg = 0; eg < 4; ++eg) {
+                    double ib[4];
+                    int g[4];
+                    bool n_ok[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float c = (float)((double)tot[nt][mt][eg * 4 + e] * invq[mt] * ib[e]);
-                        c4[e] = (n_ok[e] && g[e] == qg[mt]) ? c : -INFINITY;
+                        const int n = nbase + wn * 64 + nt * 32 + 8 * eg + 4 * h + e;
+                        n_ok[e] = n < p.Nb;
+                        ib[e] = n_ok[e] ? p.invb[n] : 0.0;
+                        g[e] = (p.bg && n_ok[e]) ? p.bg[n] : 0;
                     }
-                    *reinterpret_cast<f32x4*>(sC + (wm * 64 + mt * 32 + l31) * KNN_PITCH + wn * 32 + 8 * eg + 4 * h) = c4;
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt) {
+                        f32x4 c4;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float c = (float)((double)tot[nt][mt][eg * 4 + e] * invq[mt] * ib[e]);
+                            c4[e] = (n_ok[e] && g[e] == qg[mt]) ? c : -INFINITY;
+                        }
+                        *reinterpret_cast<f32x4*>(sC + (wm * 64 + mt * 32 + l31) * KNN_PITCH + wn * 32 + 8 * eg + 4 * h) = c4;
+                    }
                 }
-            }
-            __syncthreads();
-            for (int qq = 0; qq < 32; ++qq) {
-                const int ql = wave * 32 + qq, m = m0 + ql;
-                if (m >= p.Nq) break;
-                const float c = sC[ql * KNN_PITCH + lane];
-                const int n = nbase + (lane >> 5) * 64 + nt * 32 + (lane & 31);
-                const float tv = s_thr_v[ql];
-                const int ti = s_thr_i[ql];
-                const bool live = c > -INFINITY && (ti < 0 || cos_better(c, n, tv, ti));
-                const unsigned long long mask = __ballot(live);
-                if (!mask) continue;
-                const long o = ((long)blockIdx.y * p.Nq + m) * p.k;
-                knn_wave_merge<int>(p.pval + o, p.pidx + o, p.k, live, c, n, mask, lane, s_thr_v + ql, s_thr_i + ql, s_cnt + ql);
+                __syncthreads();
+                for (int qq = 0; qq < 32; ++qq) {
+                    const int ql = wave * 32 + qq, m = m0 + ql;
+                    if (m >= p.Nq) break;
+                    const float c = sC[ql * KNN_PITCH + lane];
+                    const int n = nbase + (lane >> 5) * 64 + nt * 32 + (lane & 31);
+                    const float tv = s_thr_v[ql];
+                    const int ti = s_thr_i[ql];
+                    const bool live = c > -INFINITY && (ti < 0 || cvcl_better(c, n, tv, ti));
+                    const unsigned long long mask = __ballot(live);
+                    if (!mask) continue;
+                    const long o = ((long)blockIdx.y * p.Nq + m) * topk;
+                    knn_wave_merge<int>(p.pval + o, p.pidx + o, topk, live, c, n, mask, lane, s_thr_v + ql, s_thr_i + ql, s_cnt + ql);
+                }
             }
         }
     }
+    if constexpr (!TOPK) {
+        // lane halves, then the two waves of a query half (through LDS), then one partial per query and split
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const float ov = __shfl_xor(best_v[mt], 32, 64);
+            const int oi = __shfl_xor(best_i[mt], 32, 64);
+            if (oi >= 0 && cvcl_better(ov, oi, best_v[mt], best_i[mt])) { best_v[mt] = ov; best_i[mt] = oi; }
+        }
+        __syncthreads();
+        float* rv = reinterpret_cast<float*>(smem);              // [2][128]
+        int* ri = reinterpret_cast<int*>(smem + 2 * CT * 4);
+        if (h == 0) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                rv[wn * CT + wm * 64 + mt * 32 + l31] = best_v[mt];
+                ri[wn * CT + wm * 64 + mt * 32 + l31] = best_i[mt];
+            }
+        }
+        __syncthreads();
+        if (tid < CT && m0 + tid < p.Nq) {
+            float v = rv[tid];
+            int i = ri[tid];
+            const float v1 = rv[CT + tid];
+            const int i1 = ri[CT + tid];
+            if (i1 >= 0 && cvcl_better(v1, i1, v, i)) { v = v1; i = i1; }
+            p.pval[(long)blockIdx.y * p.Nq + m0 + tid] = v;
+            p.pidx[(long)blockIdx.y * p.Nq + m0 + tid] = i;
+        }
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256, 2) void nn_cosine_kernel(CosDev p) {
+    cosine_tile_walk<VEC, false>(p, 1, nullptr, nullptr, nullptr);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
+    __shared__ float s_thr_v[CT];                    // per query of the tile: its list's k-th entry (the threshold) and fill count
+    __shared__ int s_thr_i[CT];
+    __shared__ int s_cnt[CT];
+    cosine_tile_walk<VEC, true>(p, p.k, s_thr_v, s_thr_i, s_cnt);
 }
 
 // one wave per query: the result list is built in LDS from the previous outputs (accumulate) and the splits' lists, split by split.
@@ -797,101 +716,93 @@ int pixel_splits(int Nq, int Nb) {
     return s < nbt ? s : nbt;
 }
 
+// ================================================================================================================================
+// host side of the two cosine searches
+// ================================================================================================================================
+// the workspace: 1 / |row| of both sides (double), then the splits' partial results, `per_query` (value, row) pairs per
+// (split, query): 1 for the arg-max, k for the lists.  Byte offsets of 16-byte aligned pieces.
+struct CosineWs { size_t invq, invb, pval, pidx, bytes; };
+
+CosineWs cosine_workspace(int Nq, int Nb, int per_query) {
+    const size_t nq = align16((size_t)Nq * 8), nb = align16((size_t)Nb * 8);
+    const size_t part = align16((size_t)cosine_splits(Nq, Nb) * Nq * per_query * 4);
+    return {0, nq, nq + nb, nq + nb + part, nq + nb + 2 * part};
+}
+
+// cvcl_nn_cosine (topk false; k is not read) and cvcl_knn_cosine (topk true) under the entry's own name and output names
+int cosine_search(const char* name, bool topk, const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, int k, float eps,
+                  const int32_t* q_group, const int32_t* base_group, int64_t idx_offset, int accumulate, float* out_cos,
+                  int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    CVCL_CHECK_ARG(q && base, "%s: null pointer (q / base)", name);
+    CVCL_CHECK_ARG(out_cos && out_idx, "%s: null pointer (%s)", name, topk ? "top_cos / top_idx" : "best_cos / best_idx");
+    CVCL_CHECK_ARG(Nq >= 1, "%s: Nq %d < 1", name, Nq);
+    CVCL_CHECK_ARG(Nb >= 1, "%s: Nb %d < 1", name, Nb);
+    CVCL_CHECK_ARG(D >= 1, "%s: D %d < 1", name, D);
+    CVCL_CHECK_ARG(!topk || (k >= 1 && k <= CVCL_KNN_MAX_K), "%s: k %d outside 1..%d", name, k, CVCL_KNN_MAX_K);
+    CVCL_CHECK_ARG(ldq >= D, "%s: ldq %d < D %d", name, ldq, D);
+    CVCL_CHECK_ARG(ldb >= D, "%s: ldb %d < D %d", name, ldb, D);
+    CVCL_CHECK_ARG(eps >= 0.f, "%s: eps %g < 0", name, (double)eps);
+    CVCL_CHECK_ARG((q_group == nullptr) == (base_group == nullptr), "%s: q_group and base_group go together (one is null)", name);
+    CVCL_CHECK_ARG(idx_offset >= 0, "%s: idx_offset %lld < 0", name, (long long)idx_offset);
+    CVCL_CHECK_ARG(workspace, "%s: null pointer (workspace)", name);
+    const CosineWs w = cosine_workspace(Nq, Nb, topk ? k : 1);
+    CVCL_CHECK_ARG(workspace_bytes >= w.bytes, "%s: workspace_bytes %zu < %zu", name, workspace_bytes, w.bytes);
+    CVCL_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace is not 16-byte aligned", name);
+
+    const int splits = cosine_splits(Nq, Nb);
+    char* ws = (char*)workspace;
+    double* invq = (double*)(ws + w.invq);
+    double* invb = (double*)(ws + w.invb);
+    KnnDev p;
+    p.q = q; p.b = base; p.ldq = ldq; p.ldb = ldb; p.Nq = Nq; p.Nb = Nb; p.D = D; p.k = k;
+    p.invq = invq; p.invb = invb; p.qg = q_group; p.bg = base_group;
+    p.pval = (float*)(ws + w.pval); p.pidx = (int32_t*)(ws + w.pidx);
+    p.nbt = cvcl_div_up(Nb, CT);
+    p.vec = (((uintptr_t)q | (uintptr_t)base) & 15) == 0 && ldq % 4 == 0 && ldb % 4 == 0 && D % 4 == 0;
+    hipStream_t st = (hipStream_t)stream;
+    CvclProfScope prof(stream, CVCL_K_HEAD);
+    nn_inv_norm_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(q, ldq, Nq, D, eps, invq);
+    nn_inv_norm_kernel<<<cvcl_div_up(Nb, 4), 256, 0, st>>>(base, ldb, Nb, D, eps, invb);
+    const dim3 grid(cvcl_div_up(Nq, CT), splits);
+    if (topk) {
+        if (p.vec) knn_cosine_kernel<true><<<grid, 256, 0, st>>>(p);
+        else knn_cosine_kernel<false><<<grid, 256, 0, st>>>(p);
+        knn_cosine_merge_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(p.pval, p.pidx, splits, Nq, k, (long)idx_offset, accumulate, out_cos,
+                                                                    out_idx);
+    } else {
+        if (p.vec) nn_cosine_kernel<true><<<grid, 256, 0, st>>>(p);
+        else nn_cosine_kernel<false><<<grid, 256, 0, st>>>(p);
+        nn_cosine_merge_kernel<<<cvcl_div_up(Nq, 256), 256, 0, st>>>(p.pval, p.pidx, splits, Nq, (long)idx_offset, accumulate, out_cos,
+                                                                     out_idx);
+    }
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
+}
+
 }  // namespace
 
 extern "C" size_t cvcl_nn_cosine_workspace_bytes(int Nq, int Nb, int D) {
     if (Nq < 1 || Nb < 1 || D < 1) return 0;
-    const size_t s = (size_t)cosine_splits(Nq, Nb);
-    return align16((size_t)Nq * 8) + align16((size_t)Nb * 8) + align16(s * Nq * 4) + align16(s * Nq * 4);
+    return cosine_workspace(Nq, Nb, 1).bytes;
 }
 
 extern "C" int cvcl_nn_cosine(const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, float eps,
                               const int32_t* q_group, const int32_t* base_group, int64_t idx_offset, int accumulate, float* best_cos,
                               int64_t* best_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    CVCL_CHECK_ARG(q && base, "cvcl_nn_cosine: null pointer (q / base)");
-    CVCL_CHECK_ARG(best_cos && best_idx, "cvcl_nn_cosine: null pointer (best_cos / best_idx)");
-    CVCL_CHECK_ARG(Nq >= 1, "cvcl_nn_cosine: Nq %d < 1", Nq);
-    CVCL_CHECK_ARG(Nb >= 1, "cvcl_nn_cosine: Nb %d < 1", Nb);
-    CVCL_CHECK_ARG(D >= 1, "cvcl_nn_cosine: D %d < 1", D);
-    CVCL_CHECK_ARG(ldq >= D, "cvcl_nn_cosine: ldq %d < D %d", ldq, D);
-    CVCL_CHECK_ARG(ldb >= D, "cvcl_nn_cosine: ldb %d < D %d", ldb, D);
-    CVCL_CHECK_ARG(eps >= 0.f, "cvcl_nn_cosine: eps %g < 0", (double)eps);
-    CVCL_CHECK_ARG((q_group == nullptr) == (base_group == nullptr), "cvcl_nn_cosine: q_group and base_group go together (one is null)");
-    CVCL_CHECK_ARG(idx_offset >= 0, "cvcl_nn_cosine: idx_offset %lld < 0", (long long)idx_offset);
-    CVCL_CHECK_ARG(workspace, "cvcl_nn_cosine: null pointer (workspace)");
-    const size_t need = cvcl_nn_cosine_workspace_bytes(Nq, Nb, D);
-    CVCL_CHECK_ARG(workspace_bytes >= need, "cvcl_nn_cosine: workspace_bytes %zu < %zu", workspace_bytes, need);
-    CVCL_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "cvcl_nn_cosine: workspace is not 16-byte aligned");
-
-    const int splits = cosine_splits(Nq, Nb);
-    char* ws = (char*)workspace;
-    CosDev p;
-    p.q = q; p.b = base; p.ldq = ldq; p.ldb = ldb; p.Nq = Nq; p.Nb = Nb; p.D = D;
-    double* invq = (double*)ws; ws += align16((size_t)Nq * 8);
-    double* invb = (double*)ws; ws += align16((size_t)Nb * 8);
-    p.pval = (float*)ws; ws += align16((size_t)splits * Nq * 4);
-    p.pidx = (int32_t*)ws;
-    p.invq = invq; p.invb = invb; p.qg = q_group; p.bg = base_group;
-    p.nbt = cvcl_div_up(Nb, CT);
-    p.vec = (((uintptr_t)q | (uintptr_t)base) & 15) == 0 && ldq % 4 == 0 && ldb % 4 == 0 && D % 4 == 0;
-    hipStream_t st = (hipStream_t)stream;
-    CvclProfScope prof(stream, CVCL_K_HEAD);
-    nn_inv_norm_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(q, ldq, Nq, D, eps, invq);
-    nn_inv_norm_kernel<<<cvcl_div_up(Nb, 4), 256, 0, st>>>(base, ldb, Nb, D, eps, invb);
-    const dim3 grid(cvcl_div_up(Nq, CT), splits);
-    if (p.vec) nn_cosine_kernel<true><<<grid, 256, 0, st>>>(p);
-    else nn_cosine_kernel<false><<<grid, 256, 0, st>>>(p);
-    nn_cosine_merge_kernel<<<cvcl_div_up(Nq, 256), 256, 0, st>>>(p.pval, p.pidx, splits, Nq, (long)idx_offset, accumulate, best_cos, best_idx);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
+    return cosine_search("cvcl_nn_cosine", false, q, ldq, base, ldb, Nq, Nb, D, 0, eps, q_group, base_group, idx_offset, accumulate,
+                         best_cos, best_idx, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t cvcl_knn_cosine_workspace_bytes(int Nq, int Nb, int D, int k) {
     if (Nq < 1 || Nb < 1 || D < 1 || k < 1 || k > CVCL_KNN_MAX_K) return 0;
-    const size_t s = (size_t)cosine_splits(Nq, Nb);
-    return align16((size_t)Nq * 8) + align16((size_t)Nb * 8) + align16(s * Nq * k * 4) + align16(s * Nq * k * 4);
+    return cosine_workspace(Nq, Nb, k).bytes;
 }
 
 extern "C" int cvcl_knn_cosine(const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, int k, float eps,
                                const int32_t* q_group, const int32_t* base_group, int64_t idx_offset, int accumulate, float* top_cos,
                                int64_t* top_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    CVCL_CHECK_ARG(q && base, "cvcl_knn_cosine: null pointer (q / base)");
-    CVCL_CHECK_ARG(top_cos && top_idx, "cvcl_knn_cosine: null pointer (top_cos / top_idx)");
-    CVCL_CHECK_ARG(Nq >= 1, "cvcl_knn_cosine: Nq %d < 1", Nq);
-    CVCL_CHECK_ARG(Nb >= 1, "cvcl_knn_cosine: Nb %d < 1", Nb);
-    CVCL_CHECK_ARG(D >= 1, "cvcl_knn_cosine: D %d < 1", D);
-    CVCL_CHECK_ARG(k >= 1 && k <= CVCL_KNN_MAX_K, "cvcl_knn_cosine: k %d outside 1..%d", k, CVCL_KNN_MAX_K);
-    CVCL_CHECK_ARG(ldq >= D, "cvcl_knn_cosine: ldq %d < D %d", ldq, D);
-    CVCL_CHECK_ARG(ldb >= D, "cvcl_knn_cosine: ldb %d < D %d", ldb, D);
-    CVCL_CHECK_ARG(eps >= 0.f, "cvcl_knn_cosine: eps %g < 0", (double)eps);
-    CVCL_CHECK_ARG((q_group == nullptr) == (base_group == nullptr), "cvcl_knn_cosine: q_group and base_group go together (one is null)");
-    CVCL_CHECK_ARG(idx_offset >= 0, "cvcl_knn_cosine: idx_offset %lld < 0", (long long)idx_offset);
-    CVCL_CHECK_ARG(workspace, "cvcl_knn_cosine: null pointer (workspace)");
-    const size_t need = cvcl_knn_cosine_workspace_bytes(Nq, Nb, D, k);
-    CVCL_CHECK_ARG(workspace_bytes >= need, "cvcl_knn_cosine: workspace_bytes %zu < %zu", workspace_bytes, need);
-    CVCL_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "cvcl_knn_cosine: workspace is not 16-byte aligned");
-
-    const int splits = cosine_splits(Nq, Nb);
-    char* ws = (char*)workspace;
-    KnnDev p;
-    p.q = q; p.b = base; p.ldq = ldq; p.ldb = ldb; p.Nq = Nq; p.Nb = Nb; p.D = D; p.k = k;
-    double* invq = (double*)ws; ws += align16((size_t)Nq * 8);
-    double* invb = (double*)ws; ws += align16((size_t)Nb * 8);
-    p.pval = (float*)ws; ws += align16((size_t)splits * Nq * k * 4);
-    p.pidx = (int32_t*)ws;
-    p.invq = invq; p.invb = invb; p.qg = q_group; p.bg = base_group;
-    p.nbt = cvcl_div_up(Nb, CT);
-    p.vec = (((uintptr_t)q | (uintptr_t)base) & 15) == 0 && ldq % 4 == 0 && ldb % 4 == 0 && D % 4 == 0;
-    hipStream_t st = (hipStream_t)stream;
-    CvclProfScope prof(stream, CVCL_K_HEAD);
-    nn_inv_norm_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(q, ldq, Nq, D, eps, invq);
-    nn_inv_norm_kernel<<<cvcl_div_up(Nb, 4), 256, 0, st>>>(base, ldb, Nb, D, eps, invb);
-    const dim3 grid(cvcl_div_up(Nq, CT), splits);
-    if (p.vec) knn_cosine_kernel<true><<<grid, 256, 0, st>>>(p);
-    else knn_cosine_kernel<false><<<grid, 256, 0, st>>>(p);
-    knn_cosine_merge_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(p.pval, p.pidx, splits, Nq, k, (long)idx_offset, accumulate, top_cos, top_idx);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
+    return cosine_search("cvcl_knn_cosine", true, q, ldq, base, ldb, Nq, Nb, D, k, eps, q_group, base_group, idx_offset, accumulate,
+                         top_cos, top_idx, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cvcl_knn_vote(const float* top_cos, const int64_t* top_idx, int Nq, int k, const int32_t* base_label, int64_t Nb, int C,

@@ -49,30 +49,38 @@ def _rows_f32(t, what):
     return t if H.row_strided(t) else t.contiguous()
 
 
-def nearest_cosine(query, base, query_groups=None, base_groups=None, chunk=None, eps=COSINE_EPS):
-    """max_j / argmax_j of F.cosine_similarity(query[:, None, :], base[None, :, :], dim=-1): query [Nq, D], base [Nb, D] fp32 device
-    rows (a row stride above D is read in place) -> (cos [Nq] fp32, idx [Nq] int64).  With groups (one integer per row on both
-    sides) only pairs of equal group compete; a query without an eligible base row gets -inf and -1.  Ties go to the lower index.
-    ``chunk``: base rows per launch sequence; the running best is merged on the device, bit for bit the one-shot result."""
-    _device_tensor(query, "nearest_cosine(query)")
-    _device_tensor(base, "nearest_cosine(base)")
+def _cosine_search(name, query, base, k, query_groups, base_groups, chunk, eps):
+    """``nearest_cosine`` (k None: outputs [Nq], ``cvcl_nn_cosine``) and ``knn_cosine`` (outputs [Nq, k], ``cvcl_knn_cosine``)"""
+    _device_tensor(query, f"{name}(query)")
+    _device_tensor(base, f"{name}(base)")
     q, b = _rows_f32(query, "query"), _rows_f32(base, "base")
     (Nq, D), Nb = q.shape, b.shape[0]
     if b.shape[1] != D:
         raise H.CvclError(f"query rows are {D} wide, base rows {b.shape[1]}")
     qg, bg = _group_ids(query_groups, base_groups, Nq, Nb, q.device)
-    cos = torch.full((Nq,), float("-inf"), dtype=torch.float32, device=q.device)
-    idx = torch.full((Nq,), -1, dtype=torch.int64, device=q.device)
+    shape, ks = ((Nq,), ()) if k is None else ((Nq, k), (k,))
+    cos = torch.full(shape, float("-inf"), dtype=torch.float32, device=q.device)
+    idx = torch.full(shape, -1, dtype=torch.int64, device=q.device)
     if Nq == 0 or Nb == 0:
         return cos, idx
     lib = H.lib()
+    entry = "cvcl_nn_cosine" if k is None else "cvcl_knn_cosine"
+    search, workspace_bytes = getattr(lib, entry), getattr(lib, entry + "_workspace_bytes")
     step = Nb if chunk is None else max(1, int(chunk))
-    ws = torch.empty(lib.cvcl_nn_cosine_workspace_bytes(Nq, min(step, Nb), D), dtype=torch.uint8, device=q.device)
+    ws = torch.empty(workspace_bytes(Nq, min(step, Nb), D, *ks), dtype=torch.uint8, device=q.device)
     for s in range(0, Nb, step):
         n = min(step, Nb - s)
-        H.check(lib.cvcl_nn_cosine(*H.rows(q), *H.rows(b[s:s + n]), Nq, n, D, eps, H.ptr(qg), None if bg is None else H.ptr(bg[s:]),
-                                   s, int(s > 0), H.ptr(cos), H.ptr(idx), H.ptr(ws), ws.numel(), H.stream_ptr()), "cvcl_nn_cosine")
+        H.check(search(*H.rows(q), *H.rows(b[s:s + n]), Nq, n, D, *ks, eps, H.ptr(qg), None if bg is None else H.ptr(bg[s:]),
+                       s, int(s > 0), H.ptr(cos), H.ptr(idx), H.ptr(ws), ws.numel(), H.stream_ptr()), entry)
     return cos, idx
+
+
+def nearest_cosine(query, base, query_groups=None, base_groups=None, chunk=None, eps=COSINE_EPS):
+    """max_j / argmax_j of F.cosine_similarity(query[:, None, :], base[None, :, :], dim=-1): query [Nq, D], base [Nb, D] fp32 device
+    rows (a row stride above D is read in place) -> (cos [Nq] fp32, idx [Nq] int64).  With groups (one integer per row on both
+    sides) only pairs of equal group compete; a query without an eligible base row gets -inf and -1.  Ties go to the lower index.
+    ``chunk``: base rows per launch sequence; the running best is merged on the device, bit for bit the one-shot result."""
+    return _cosine_search("nearest_cosine", query, base, None, query_groups, base_groups, chunk, eps)
 
 
 def knn_cosine(query, base, k, query_groups=None, base_groups=None, chunk=None, eps=COSINE_EPS):
@@ -83,25 +91,7 @@ def knn_cosine(query, base, k, query_groups=None, base_groups=None, chunk=None, 
     k = int(k)
     if not 1 <= k <= H.KNN_MAX_K:
         raise H.CvclError(f"knn_cosine: k {k} outside 1..{H.KNN_MAX_K}")
-    _device_tensor(query, "knn_cosine(query)")
-    _device_tensor(base, "knn_cosine(base)")
-    q, b = _rows_f32(query, "query"), _rows_f32(base, "base")
-    (Nq, D), Nb = q.shape, b.shape[0]
-    if b.shape[1] != D:
-        raise H.CvclError(f"query rows are {D} wide, base rows {b.shape[1]}")
-    qg, bg = _group_ids(query_groups, base_groups, Nq, Nb, q.device)
-    cos = torch.full((Nq, k), float("-inf"), dtype=torch.float32, device=q.device)
-    idx = torch.full((Nq, k), -1, dtype=torch.int64, device=q.device)
-    if Nq == 0 or Nb == 0:
-        return cos, idx
-    lib = H.lib()
-    step = Nb if chunk is None else max(1, int(chunk))
-    ws = torch.empty(lib.cvcl_knn_cosine_workspace_bytes(Nq, min(step, Nb), D, k), dtype=torch.uint8, device=q.device)
-    for s in range(0, Nb, step):
-        n = min(step, Nb - s)
-        H.check(lib.cvcl_knn_cosine(*H.rows(q), *H.rows(b[s:s + n]), Nq, n, D, k, eps, H.ptr(qg), None if bg is None else H.ptr(bg[s:]),
-                                    s, int(s > 0), H.ptr(cos), H.ptr(idx), H.ptr(ws), ws.numel(), H.stream_ptr()), "cvcl_knn_cosine")
-    return cos, idx
+    return _cosine_search("knn_cosine", query, base, k, query_groups, base_groups, chunk, eps)
 
 
 def knn_vote(cos, idx, base_labels, n_classes, temperature=0.07):

@@ -8,7 +8,7 @@ evaluations; tau is measured against the reference arithmetic, not against the k
 figures before asserting.  Per query: the list is sorted by (cos desc, idx asc) and holds no index twice; every value is within tau
 of cos64 at its index; the set is right -- (the k-th largest cos64 of the row) - (the smallest cos64 among the returned indices) <=
 tau; slots beyond the eligible count hold -inf / -1.  Beside that, bit-exact anchors: k = 1 and the first column at k = 20 against
-nearest_cosine, strided against contiguous inputs, chunked against one-shot, grouped against the ungrouped search per group.
+nearest_cosine (and at k = 5 on the scalar-load path, with ragged tiles and groups), strided against contiguous inputs, chunked against one-shot, grouped against the ungrouped search per group.
 
 Vote.  scores are compared against numpy float64 sums of exp(cos / T) over the same lists, T being the fp32 value the entry
 receives.  Bound on the relative error, 2^-22: the kernel forms the weights and the sum in double and rounds ONCE to fp32.  One
@@ -140,6 +140,35 @@ def test_k1_and_first_column_equal_the_argmax_search():
     cos20, idx20 = _knn(q, b, 20)
     assert torch.equal(cos20[:, 0], want_cos) and torch.equal(idx20[:, 0], want_idx)
     _check_knn("anchor k 20", q, b, 20, cos20, idx20)
+
+
+def test_k1_and_first_column_equal_the_argmax_search_on_the_scalar_path():
+    """the anchor above on the kernels' scalar-load instantiation, with ragged tiles and groups: 130 and 257 rows are a full tile and
+    a ragged one on both sides, D = 33 is two k steps (the second nearly empty) and rules out 16-byte loads; then the same rows
+    through a row stride that is no multiple of 4"""
+    g = torch.Generator().manual_seed(18)
+    Nq, Nb, D = 130, 257, 33
+    q, b = torch.randn(Nq, D, generator=g), torch.randn(Nb, D, generator=g)
+    qg, bg = (torch.arange(Nq) % 3).int(), ((torch.arange(Nb) * 7) % 3).int()
+    qg, bg = qg[torch.randperm(Nq, generator=g)], bg[torch.randperm(Nb, generator=g)]
+    assert sorted(set(qg.tolist())) == sorted(set(bg.tolist())) == [0, 1, 2]
+    kw = dict(query_groups=qg, base_groups=bg)
+    want_cos, want_idx = _nearest(q, b, **kw)
+    assert bool((want_idx >= 0).all())
+    cos1, idx1 = _knn(q, b, 1, **kw)
+    assert torch.equal(cos1[:, 0], want_cos) and torch.equal(idx1[:, 0], want_idx)
+    cos5, idx5 = _knn(q, b, 5, **kw)
+    assert torch.equal(cos5[:, 0], want_cos) and torch.equal(idx5[:, 0], want_idx)
+    _check_knn("scalar path k 5", q, b, 5, cos5, idx5, eligible=qg[:, None] == bg[None, :])
+    qs, bs = torch.zeros(Nq, 35), torch.zeros(Nb, 35)                      # 35-wide storage, the first 33 columns are the rows
+    qs[:, :D], bs[:, :D] = q, b
+    qv, bv = qs.to(DEV)[:, :D], bs.to(DEV)[:, :D]
+    assert qv.stride(0) == 35 and bv.stride(0) == 35
+    N = _N()
+    got = [N.nearest_cosine(qv, bv, **kw), N.knn_cosine(qv, bv, 1, **kw), N.knn_cosine(qv, bv, 5, **kw)]
+    torch.cuda.synchronize()
+    for (gc, gi), (wc, wi) in zip(got, [(want_cos, want_idx), (cos1, idx1), (cos5, idx5)]):
+        assert torch.equal(gc.cpu(), wc) and torch.equal(gi.cpu(), wi)
 
 
 def test_strided_inputs_equal_contiguous_inputs():
