@@ -68,6 +68,13 @@ def _gemm_tn(a2d: torch.Tensor, b2d: torch.Tensor, k_keep: int | None = None) ->
     return out
 
 
+def _check_even_map(who: str, Hh: int, Ww: int, stride: int):
+    """_zero_stuff returns [B, 2 Ho, 2 Wo, C], which is the saved map's own shape for even Hh, Ww only: a stride-2 backward of an
+    odd map is refused before anything is launched (the data-gradient kernels would read that buffer at the pitch of Ww)."""
+    if stride > 1 and (Hh % 2 or Ww % 2):
+        raise H.CvclError(f"{who}: the stride-2 backward needs an even map, got {Hh} x {Ww} (image H, W must be multiples of 32)")
+
+
 def _zero_stuff(dy: torch.Tensor) -> torch.Tensor:
     B, Ho, Wo, Cn = dy.shape
     z = torch.empty(B, 2 * Ho, 2 * Wo, Cn, dtype=dy.dtype, device=dy.device)
@@ -164,8 +171,9 @@ class Conv1x1(torch.autograd.Function):
         x, wq = ctx.saved_tensors
         B, Hh, Ww, K = x.shape
         N = wq.shape[0]
+        _check_even_map("Conv1x1.backward", Hh, Ww, ctx.stride)
         dy = dy.contiguous()
-        if ctx.stride > 1:                               # rows of the skipped pixels get zero gradient / contribute nothing
+        if ctx.stride > 1:                             # rows of the skipped pixels get zero gradient / contribute nothing
             dy = _zero_stuff(dy)
         M = B * Hh * Ww
         dy2, x2 = dy.view(M, N), x.view(M, K)
@@ -246,6 +254,7 @@ class GroupedConv3x3(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         B, Hh, Ww, Cn = x.shape
         cg = weight.shape[1]
+        _check_even_map("GroupedConv3x3.backward", Hh, Ww, ctx.stride)
         dy = dy.contiguous()
         dx = dw = None
         lib, s = H.lib(), H.stream_ptr()
@@ -480,6 +489,8 @@ def trunk_train(model, x: torch.Tensor):
                                   "(the reference fine-tunes in train mode); eval-mode runs use the no-grad fast path")
     if x.dtype != _F or x.dim() != 4 or x.shape[1] != 3:
         raise H.CvclError(f"expected NCHW fp32 images, got {tuple(x.shape)} {x.dtype}")
+    if x.shape[2] % 32 or x.shape[3] % 32:       # (the frozen trunk's rule: every stride-2 layer then sees an even map, see _zero_stuff)
+        raise H.CvclError(f"trunk_train: H, W must be multiples of 32, got {x.shape[2]} x {x.shape[3]}")
     x = x.contiguous()
     cdt = model.compute_dtype
     _WGRAD_PENDING.clear()                  # leftovers of a backward pass that died half way must not reach the next one

@@ -153,6 +153,7 @@ def test_gconv3x3_grads_exact_fullsize(dev, name, C, S, stride):
     """GroupedConv3x3 (32 groups) backward on operands in {-2..2}:
       dW (cvcl_gconv3x3_wgrad, band kernel): sums over B Ho Wo <= 802 816 pixels of products <= 4: <= 3 211 264 < 2^24 -> exact fp32;
       dX (cvcl_gconv_weight_dgrad + cvcl_gconv3x3 on the zero-stuffed dY): <= 9 taps x 32 channels x 4 = 1152 -> bf16 of the exact sum.
+      out (the forward cvcl_gconv3x3 itself, no prologue, at its full-batch schedule): the same bound, bf16 of the exact sum.
     The weight-gradient kernel must be in its multi-item regime: fewer workgroups per slab than (image, band) items."""
     from multimodal.trunk_train import GroupedConv3x3
     G, min_items = _gw_groups_and_min_items(S, C, stride)
@@ -171,15 +172,19 @@ def test_gconv3x3_grads_exact_fullsize(dev, name, C, S, stride):
     dw_ref = torch.empty(C, cg, 3, 3, dtype=F64, device=dev)
     wg = w.detach().double().view(32, cg, cg, 3, 3)                          # [group][co][ci][ky][kx]
     dxp = torch.zeros(B, S + 2, S + 2, C, dtype=F64, device=dev)
+    out_ref = torch.zeros(32, M, cg, dtype=F64, device=dev)                  # [group][pixel][co]
     for ky in range(3):
         for kx in range(3):
             rows = slice(ky, ky + stride * (So - 1) + 1, stride)
             cols = slice(kx, kx + stride * (So - 1) + 1, stride)
             xt = xp[:, rows, cols].reshape(M, 32, cg).double().permute(1, 0, 2)     # [group][pixel][ci]: the tap's input pixels
             dw_ref[:, :, ky, kx] = torch.bmm(dyg, xt).reshape(C, cg)
+            out_ref += torch.bmm(xt, wg[:, :, :, ky, kx].transpose(1, 2))    # out[.., g, co] += X[tap pixel, g, ci] W[g, co, ci, tap]
             del xt
             # dX at the tap's input pixels += dY[.., g, co] W[g, co, ci, tap]
             dxp[:, rows, cols] += torch.bmm(dyg.transpose(1, 2), wg[:, :, :, ky, kx]).permute(1, 0, 2).reshape(B, So, So, C)
+    assert _same(out.detach(), _exact_bf16(out_ref.permute(1, 0, 2).reshape(B, So, So, C))), name
+    del out_ref
     assert torch.equal(w.grad, dw_ref.float()), name
     del dw_ref, dyg
     assert _same(x.grad, _exact_bf16(dxp[:, 1:S + 1, 1:S + 1])), name

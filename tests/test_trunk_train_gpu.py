@@ -345,6 +345,39 @@ def test_weight_gradient_stream_is_bit_identical(dev, monkeypatch, cdt):
     assert gw.shape == w.shape and torch.isfinite(gw).all()
 
 
+def test_trunk_train_refuses_sizes_that_are_no_multiple_of_32(dev):
+    """A 200 x 200 batch would reach layer3.0 as a 25 x 25 map, whose stride-2 backward reads the zero-stuffed gradient (always
+    [B, 2 Ho, 2 Wo, C]) at the wrong pitch: the fine-tuning trunk refuses it like the frozen one does, before any kernel runs --
+    no BatchNorm buffer has moved."""
+    from multimodal import _hip as H
+    from multimodal.resnext import ResNet
+    model = ResNet().to(dev).train()
+    before = {k: v.clone() for k, v in model.state_dict().items()}
+    for shape in ((2, 3, 200, 200), (2, 3, 224, 200), (2, 3, 200, 224)):
+        with pytest.raises(H.CvclError, match="multiples of 32"):
+            model.trunk(torch.zeros(shape, device=dev))
+    torch.cuda.synchronize()
+    assert all(torch.equal(v, before[k]) for k, v in model.state_dict().items())
+
+
+@pytest.mark.parametrize("op", ["gconv", "conv1x1"])
+def test_stride2_backward_refuses_an_odd_map(dev, op):
+    """the two stride-2 backward passes themselves refuse an odd saved map (forward is fine: 25 -> 13) before they launch anything"""
+    from multimodal import _hip as H
+    from multimodal.trunk_train import Conv1x1, GroupedConv3x3
+    x = torch.ones(2, 25, 25, 128, dtype=torch.bfloat16, device=dev).requires_grad_()
+    if op == "gconv":
+        w = torch.ones(128, 4, 3, 3, device=dev).requires_grad_()
+        y, _st = GroupedConv3x3.apply(x, w, 2)
+    else:
+        w = torch.ones(256, 128, 1, 1, device=dev).requires_grad_()
+        y, _st = Conv1x1.apply(x, w, 2)
+    assert y.shape[1:3] == (13, 13)
+    with pytest.raises(H.CvclError, match="even map"):
+        y.backward(torch.ones_like(y))
+    assert x.grad is None and w.grad is None
+
+
 def test_finetune_cnn_training_step(dev):
     """reference config with --finetune_cnn (multimodal.py:175-179): the trunk's parameters receive gradients and an
     AdamW step changes them; the default (frozen) configuration leaves them untouched."""
