@@ -886,6 +886,56 @@ int cvcl_knn_vote(const float* top_cos, const int64_t* top_idx, int Nq, int k, c
                   float temperature, float* scores, int64_t* pred, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Perceptual-hash duplicates (csrc/phash.hip, ABI v7 additive): the first half of the reference's analysis_cvcl/duplicates.py, "exact
+ * and approximate duplicates" -- the 16 x 16 average hash of a frame, and per evaluation hash the closest training hash, by Hamming
+ * distance and by the reference's own measure, fuzz.ratio of the two hashes written as decimal strings.  All three entries validate
+ * everything before they enqueue anything (null pointers, counts, sizes and strides out of range, one group array without the other, a
+ * workspace that is too small or not 16-byte aligned: CVCL_EINVAL, cvcl_last_error starts with the entry's name and names the
+ * argument), enqueue on the caller's stream only, use no atomics (the base rows are split over workgroups, whose partial results go
+ * through the caller's workspace to a merge kernel that walks them in a fixed order: two calls give the same bits) and send ties to
+ * the LOWER index.  Everything is integer arithmetic: the results are exact.  CVCL_K_OTHER.
+ *
+ * cvcl_ahash_u8: ahash (duplicates.py:28-41) in the project's integer definition.  frames: N 8-bit RGB frames of H x W, addressed as
+ *   frames[n stride_n + c stride_c + y stride_y + x stride_x] (element strides: planar [N, 3, H, W] is (3 H W, H W, W, 1),
+ *   interleaved [N, H, W, 3] is (H W 3, 1, 3 W, 3), a crop of a larger tensor keeps its parent's strides).  Grey g = (19595 R +
+ *   38470 G + 7471 B + 32768) >> 16 (ITU-R 601, Pillow's convert("L")).  Resize to 16 x 16, bilinear at half-pixel centres without
+ *   antialiasing (cv2.resize's default): per axis of n source pixels and cell d, num = (2 d + 1) n - 16, i0 = num >> 5, w1 = num - 32 i0,
+ *   w0 = 32 - w1, i1 = min(i0 + 1, n - 1); v = sum over the 2 x 2 taps of wy wx g (an exact integer, scaled by 1024), the cell value
+ *   r = (v + 512) >> 10.  Bit i = 16 y + x is set when 256 r_i >= sum_j r_j (the reference's `resized >= resized.mean()`).
+ *   -> hash [N, 4] int64 bit patterns, word w holding bits 64 w .. 64 w + 63 (bit 255 is the sign bit of word 3); cells [N, 256]
+ *   int32 = the r (may be NULL).  One 256-thread workgroup per frame, one thread per cell, 12 byte loads per thread (3 072 bytes
+ *   of a frame are read, whatever its size), the sum through LDS, one ballot per wave is one output word.  Limits: N >= 1, H, W >= 16,
+ *   strides >= 1.  The reference decodes to grey inside libjpeg and rounds inside OpenCV: a grey level or a rare cell may differ by
+ *   one from cv2's; this definition has not been compared with cv2.
+ * cvcl_hamming_nn: q [Nq, 4], base [Nb, 4] int64 bit patterns -> best_dist [Nq] int32 = min_j popcount(q_i xor b_j), best_idx [Nq]
+ *   int64 = the lowest j attaining it.  q_group / base_group (int32 per row, both or neither): only pairs of equal group are
+ *   eligible; a query without an eligible base row gets index -1 and distance 257.  A lane owns one query in registers and walks
+ *   the base hashes of its workgroup's range, which every lane reads at the same address.  Workspace:
+ *   cvcl_hamming_nn_workspace_bytes (0 = refused sizes) -- splits x Nq (distance, row) pairs.
+ * cvcl_digit_ratio_nn: the scan of duplicates.py:333-342.  q [Nq, ld], base [Nb, ld] uint8 strings over the alphabet 0..9 (digit
+ *   values, not characters), q_len [Nq], base_len [Nb] int32 lengths, groups as above -> best_ratio [Nq] int32 = max_j ratio(q_i, b_j),
+ *   best_idx [Nq] int64 = the lowest j attaining it, where ratio = round_half_even(200 LCS / (la + lb)) is thefuzz's fuzz.ratio
+ *   (the normalised indel similarity), formed in integers by quotient and remainder.  A maximum of 0, or no eligible row, gives
+ *   index -1 and ratio 0 (the reference scans from max_distance = 0 with a strict >).  LCS is the bit-parallel recurrence
+ *   V = (V + (V & M)) | (V & ~M) over two 64-bit words with carry, M the query's match mask of the base string's digit (built once
+ *   per query, in LDS); LCS = the zero bits among the low la bits of V.  Limits: 1 <= ld <= CVCL_DIGITS_MAX; lengths are device
+ *   data and are clamped to [0, ld] where they are read (a length of 0 matches nothing); bytes above 9 are not supported (they
+ *   match nothing).  A 256-bit hash has at most 78 digits.  Workspace: cvcl_digit_ratio_nn_workspace_bytes (0 = refused sizes).
+ *   This definition has not been compared with thefuzz. */
+#define CVCL_AHASH_SIDE 16
+#define CVCL_AHASH_WORDS 4
+#define CVCL_DIGITS_MAX 128
+int cvcl_ahash_u8(const uint8_t* frames, int N, int H, int W, long stride_n, long stride_c, long stride_y, long stride_x, int64_t* hash,
+                  int32_t* cells, void* stream);
+size_t cvcl_hamming_nn_workspace_bytes(int Nq, int Nb);
+int cvcl_hamming_nn(const int64_t* q, const int64_t* base, int Nq, int Nb, const int32_t* q_group, const int32_t* base_group,
+                    int32_t* best_dist, int64_t* best_idx, void* workspace, size_t workspace_bytes, void* stream);
+size_t cvcl_digit_ratio_nn_workspace_bytes(int Nq, int Nb);
+int cvcl_digit_ratio_nn(const uint8_t* q, const int32_t* q_len, const uint8_t* base, const int32_t* base_len, int Nq, int Nb, int ld,
+                        const int32_t* q_group, const int32_t* base_group, int32_t* best_ratio, int64_t* best_idx, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Image-text alignment analysis (csrc/alignment.hip): the arithmetic of the reference's analysis_cvcl/alignment.py,
  * analysis_cvcl/embeddings.py:106-118 and analysis_tools/representation_similarity.py.  fp32 in and out (the Pearson moments: double),
  * contiguous rows.  Every entry validates everything before it enqueues anything (null pointers, sizes out of range, a workspace that

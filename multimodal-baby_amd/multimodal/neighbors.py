@@ -8,7 +8,13 @@ in double).  ``extract_features`` runs the eval-mode pooled output of the DINO R
 
 Beyond the reference, which has only the nearest frame: ``knn_cosine`` returns the k closest base rows per query (``cvcl_knn_cosine``,
 the same arithmetic), ``knn_vote`` the weighted vote over them (``cvcl_knn_vote``) and ``knn_classify`` the weighted k-NN
-classification that is the training-free evaluation of a DINO encoder (k = 20, T = 0.07)."""
+classification that is the training-free evaluation of a DINO encoder (k = 20, T = 0.07).
+
+Perceptual hash, the check the reference names first ("exact and approximate duplicates"): ``average_hash`` is ahash (:28-41) in an
+integer definition of the project's own (``cvcl_ahash_u8``), ``nearest_hamming`` the closest hash by differing bits
+(``cvcl_hamming_nn``), ``nearest_digit_ratio`` the nested fuzz.ratio loops of :333-342 as one grouped search
+(``cvcl_digit_ratio_nn``), and ``hash_duplicates`` the bookkeeping of :81-105 and :316-349.  cv2 and thefuzz are not used, and the
+definitions have not been compared with them (DESIGN.md section 9 "Perceptual-hash duplicates" names the departures)."""
 from __future__ import annotations
 
 import csv
@@ -176,6 +182,123 @@ def nearest_pixels(query_u8, base_u8, std=IMAGENET_STD, query_groups=None, base_
                 "cvcl_nn_l1_u8")
         seen += n
     return dist, idx, sums.to(torch.int64) & 0xFFFFFFFF
+
+
+# ---- perceptual hash (duplicates.py:28-41, :333-342) ------------------------------------------------------------------------------
+HASH_NO_MATCH = 64 * H.AHASH_WORDS + 1               # the Hamming distance of a query without an eligible base row: 257
+
+
+def average_hash(frames_u8, layout="NCHW", return_cells=False):
+    """ahash (duplicates.py:28-41) of 8-bit RGB device frames, in the project's integer definition (cvcl_hip.h ``cvcl_ahash_u8``:
+    ITU-R 601 grey as Pillow's convert("L"), bilinear 16 x 16 at half-pixel centres without antialiasing, bit i = 16 y + x set where
+    the cell is >= the mean): uint8 [N, 3, H, W] (``layout="NCHW"``) or [N, H, W, 3] (``"NHWC"``), H, W >= 16, read in place
+    through its strides (a crop or a permuted view is not copied) -> int64 [N, 4] on the device, word w = bits 64 w .. 64 w + 63.
+    ``return_cells``: also the 16 x 16 rounded cell values, int32 [N, 256]."""
+    _device_tensor(frames_u8, "average_hash(frames)")
+    if layout not in ("NCHW", "NHWC"):
+        raise H.CvclError(f"average_hash: layout {layout!r} (NCHW or NHWC)")
+    t = frames_u8
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[1 if layout == "NCHW" else 3] != 3:
+        raise H.CvclError(f"average_hash: expected uint8 RGB frames in {layout}, got {tuple(t.shape)} {t.dtype}")
+    if layout == "NHWC":
+        t = t.permute(0, 3, 1, 2)
+    N, _, Hh, Ww = t.shape
+    if Hh < H.AHASH_SIDE or Ww < H.AHASH_SIDE:
+        raise H.CvclError(f"average_hash: frames of {Hh} x {Ww} are below {H.AHASH_SIDE} x {H.AHASH_SIDE}")
+    if min(t.stride()) < 1:                              # (an expanded view)
+        t = t.contiguous()
+    out = torch.zeros(N, H.AHASH_WORDS, dtype=torch.int64, device=t.device)
+    cells = torch.zeros(N, H.AHASH_SIDE * H.AHASH_SIDE, dtype=torch.int32, device=t.device) if return_cells else None
+    if N:
+        sn, sc, sy, sx = t.stride()
+        H.check(H.lib().cvcl_ahash_u8(t.data_ptr(), N, Hh, Ww, sn, sc, sy, sx, H.ptr(out), H.ptr(cells), H.stream_ptr()), "cvcl_ahash_u8")
+    return (out, cells) if return_cells else out
+
+
+def _hash_words(hashes):
+    a = hashes.detach().cpu().numpy() if torch.is_tensor(hashes) else np.asarray(hashes)
+    if a.ndim != 2 or a.shape[1] != H.AHASH_WORDS or a.dtype != np.int64:
+        raise H.CvclError(f"expected int64 [N, {H.AHASH_WORDS}] hash words, got {a.shape} {a.dtype}")
+    return a.view(np.uint64)
+
+
+def hash_ints(hashes):
+    """the reference's ``hash_value`` (duplicates.py:40) of each row of ``average_hash``'s output, as Python ints: the words are
+    taken as unsigned, word w weighs 2^(64 w)"""
+    return [sum(int(w) << (64 * k) for k, w in enumerate(row)) for row in _hash_words(hashes)]
+
+
+def hash_digits(hashes):
+    """str(hash_value) per row, on the host, as ``cvcl_digit_ratio_nn`` reads it -> (uint8 [N, 128] numpy array of digit values
+    0..9, zero beyond the length; int32 [N] lengths).  The zero hash is "0", length 1; a 256-bit hash has at most 78 digits."""
+    ints = hash_ints(hashes)
+    digits = np.zeros((len(ints), H.DIGITS_MAX), dtype=np.uint8)
+    lens = np.zeros(len(ints), dtype=np.int32)
+    for i, v in enumerate(ints):
+        s = str(v)
+        lens[i] = len(s)
+        digits[i, :len(s)] = np.frombuffer(s.encode(), dtype=np.uint8) - ord("0")
+    return digits, lens
+
+
+def nearest_hamming(query, base, query_groups=None, base_groups=None):
+    """min_j / the lowest argmin_j of popcount(query_i xor base_j) over int64 [N, 4] device hashes (``cvcl_hamming_nn``) ->
+    (dist [Nq] int32, idx [Nq] int64).  Groups as ``nearest_cosine``; a query without an eligible base row gets 257 and -1."""
+    _device_tensor(query, "nearest_hamming(query)")
+    _device_tensor(base, "nearest_hamming(base)")
+    for t, what in ((query, "query"), (base, "base")):
+        if t.dim() != 2 or t.shape[1] != H.AHASH_WORDS or t.dtype != torch.int64:
+            raise H.CvclError(f"nearest_hamming: {what} must be int64 [N, {H.AHASH_WORDS}], got {tuple(t.shape)} {t.dtype}")
+    q, b = query.contiguous(), base.contiguous()
+    Nq, Nb = q.shape[0], b.shape[0]
+    qg, bg = _group_ids(query_groups, base_groups, Nq, Nb, q.device)
+    dist = torch.full((Nq,), HASH_NO_MATCH, dtype=torch.int32, device=q.device)
+    idx = torch.full((Nq,), -1, dtype=torch.int64, device=q.device)
+    if Nq == 0 or Nb == 0:
+        return dist, idx
+    lib = H.lib()
+    ws = torch.empty(lib.cvcl_hamming_nn_workspace_bytes(Nq, Nb), dtype=torch.uint8, device=q.device)
+    H.check(lib.cvcl_hamming_nn(H.ptr(q), H.ptr(b), Nq, Nb, H.ptr(qg), H.ptr(bg), H.ptr(dist), H.ptr(idx), H.ptr(ws), ws.numel(),
+                                H.stream_ptr()), "cvcl_hamming_nn")
+    return dist, idx
+
+
+def nearest_digit_strings(query_digits, query_len, base_digits, base_len, query_groups=None, base_groups=None):
+    """max_j / the lowest argmax_j of fuzz.ratio between digit strings (``cvcl_digit_ratio_nn``): uint8 [N, ld] device rows of digit
+    VALUES 0..9 with ld <= 128 on both sides and int32 [N] lengths in 1..ld -> (ratio [Nq] int32, idx [Nq] int64);
+    ratio = round_half_even(200 LCS / (la + lb)).  A maximum of 0, or no eligible row, gives 0 and -1.  Groups as ``nearest_cosine``."""
+    for t, what in ((query_digits, "query_digits"), (query_len, "query_len"), (base_digits, "base_digits"), (base_len, "base_len")):
+        _device_tensor(t, f"nearest_digit_strings({what})")
+    q, b = query_digits.contiguous(), base_digits.contiguous()
+    if q.dim() != 2 or b.dim() != 2 or q.dtype != torch.uint8 or b.dtype != torch.uint8 or q.shape[1] != b.shape[1]:
+        raise H.CvclError(f"nearest_digit_strings: expected uint8 [N, ld] rows of one width, got {tuple(q.shape)} {q.dtype} and "
+                          f"{tuple(b.shape)} {b.dtype}")
+    (Nq, ld), Nb = q.shape, b.shape[0]
+    ql, bl = query_len.to(torch.int32).contiguous(), base_len.to(torch.int32).contiguous()
+    if ql.shape != (Nq,) or bl.shape != (Nb,):
+        raise H.CvclError(f"nearest_digit_strings: lengths must be [{Nq}] and [{Nb}], got {tuple(ql.shape)} and {tuple(bl.shape)}")
+    qg, bg = _group_ids(query_groups, base_groups, Nq, Nb, q.device)
+    ratio = torch.zeros(Nq, dtype=torch.int32, device=q.device)
+    idx = torch.full((Nq,), -1, dtype=torch.int64, device=q.device)
+    if Nq == 0 or Nb == 0:
+        return ratio, idx
+    lib = H.lib()
+    ws = torch.empty(lib.cvcl_digit_ratio_nn_workspace_bytes(Nq, Nb), dtype=torch.uint8, device=q.device)
+    H.check(lib.cvcl_digit_ratio_nn(H.ptr(q), H.ptr(ql), H.ptr(b), H.ptr(bl), Nq, Nb, ld, H.ptr(qg), H.ptr(bg), H.ptr(ratio), H.ptr(idx),
+                                    H.ptr(ws), ws.numel(), H.stream_ptr()), "cvcl_digit_ratio_nn")
+    return ratio, idx
+
+
+def nearest_digit_ratio(query_hashes, base_hashes, query_groups=None, base_groups=None):
+    """The reference's scan of duplicates.py:333-342 as one search: per query hash the base hash of largest
+    fuzz.ratio(str(hash), str(hash)), the lowest index on a tie -> (ratio [Nq] int32, idx [Nq] int64; 0 and -1 where nothing
+    scores above 0).  int64 [N, 4] device hashes; the decimal strings are written on the host (``hash_digits``)."""
+    _device_tensor(query_hashes, "nearest_digit_ratio(query)")
+    _device_tensor(base_hashes, "nearest_digit_ratio(base)")
+    dev = query_hashes.device
+    (qd, ql), (bd, bl) = hash_digits(query_hashes), hash_digits(base_hashes)
+    return nearest_digit_strings(torch.from_numpy(qd).to(dev), torch.from_numpy(ql).to(dev), torch.from_numpy(bd).to(dev),
+                                 torch.from_numpy(bl).to(dev), query_groups, base_groups)
 
 
 def normalize_u8(frames_u8):
@@ -350,6 +473,58 @@ def pixel_records(eval_frames, eval_labels, train_frames, train_labels, dist, id
     return out
 
 
+def hash_duplicates(eval_frames, eval_labels, train_frames, train_labels, eval_names, train_names, layout="NCHW", hashes=None,
+                    nearest_ratio=None, nearest_distance=None):
+    """The perceptual-hash half of the leakage check: ``average_hash`` of both sets, then the bookkeeping of duplicates.py:81-105
+    (calculate_exact_duplicates) and :316-349 (calculate_indirect_duplicates_with_hash), with one grouped search in place of the
+    nested loops.  ``hashes`` = a precomputed (eval [Ne, 4], train [Nt, 4]) int64 pair replaces the hashing (the frames are then
+    not read); ``nearest_ratio`` / ``nearest_distance`` = precomputed grouped (value, index) pairs replace the two searches.
+    Returns a dict:
+    ``hashed_eval_frames`` / ``hashed_train_frames`` {str(hash): file name}, a later frame overwriting an earlier one of the same
+    hash as in the reference; ``exact_duplicates`` = the hashes in both (ascending) and ``n_exact_duplicates``;
+    ``n_category_duplicates`` = the sum over the evaluation categories of the hashes that occur on both sides of the category;
+    ``indirect_duplicates`` = [{"eval_frame", "train_frame", "distance"}] with the reference's keys: the same-category training
+    frame of largest fuzz.ratio and that ratio ("" and 0 where nothing scores above 0), categories in sorted order, frames in their
+    given order; ``hamming_duplicates`` = the same records with the same-category training frame of smallest Hamming distance
+    ("" and 257 where the category has no training frame)."""
+    if hashes is None:
+        hashes = average_hash(eval_frames, layout), average_hash(train_frames, layout)
+    eh, th = hashes
+    ei, ti = hash_ints(eh), hash_ints(th)
+    if len(ei) != len(eval_labels) or len(ti) != len(train_labels):
+        raise H.CvclError(f"{len(ei)} / {len(ti)} hashes but {len(eval_labels)} / {len(train_labels)} labels")
+    qg, bg = _label_ids(eval_labels, train_labels)
+    if nearest_ratio is None:
+        nearest_ratio = nearest_digit_ratio(eh, th, qg, bg)
+    if nearest_distance is None:
+        nearest_distance = nearest_hamming(eh, th, qg, bg)
+    (ratio, ridx), (dist, didx) = _host_pair(nearest_ratio), _host_pair(nearest_distance)
+    res = {"hashed_eval_frames": {str(h): n for h, n in zip(ei, eval_names)},
+           "hashed_train_frames": {str(h): n for h, n in zip(ti, train_names)}}
+    res["exact_duplicates"] = [str(h) for h in sorted(set(ei) & set(ti))]
+    res["n_exact_duplicates"] = len(res["exact_duplicates"])
+    res["n_category_duplicates"] = 0
+    res["indirect_duplicates"], res["hamming_duplicates"] = [], []
+    for cat in sorted({str(x) for x in eval_labels}):
+        res["n_category_duplicates"] += len({h for h, l in zip(ei, eval_labels) if str(l) == cat}
+                                            & {h for h, l in zip(ti, train_labels) if str(l) == cat})
+        for j in range(len(eval_labels)):
+            if str(eval_labels[j]) != cat:
+                continue
+            r, d = int(ridx[j]), int(didx[j])
+            res["indirect_duplicates"].append({"eval_frame": eval_names[j], "train_frame": train_names[r] if r >= 0 else "",
+                                               "distance": int(ratio[j]) if r >= 0 else 0})
+            res["hamming_duplicates"].append({"eval_frame": eval_names[j], "train_frame": train_names[d] if d >= 0 else "",
+                                              "distance": int(dist[j])})
+    return res
+
+
+def hash_summary(res):
+    """the printed lines of duplicates.py:105 and :324"""
+    return [f"total number of duplicates (using perceptual hash): {res['n_exact_duplicates']}",
+            f"Total number of duplicates: {res['n_category_duplicates']}"]
+
+
 def classify_summary(res):
     """the printed lines of duplicates.py:835-846"""
     lines = [f"Accuracy for {cat}: {acc}" for cat, acc in res["per_category"].items()]
@@ -447,7 +622,8 @@ def parser():
     ap.add_argument("--train_dir", default=None, help="class-per-folder training frames")
     ap.add_argument("--eval_dir", default=None, help="class-per-folder evaluation frames")
     ap.add_argument("--dataset", default="folders", choices=("folders", "synthetic"))
-    ap.add_argument("--space", default="both", choices=("features", "pixels", "both"))
+    ap.add_argument("--space", default="both", choices=("features", "pixels", "both", "hash"),
+                    help="both: features and pixels; hash: the perceptual-hash duplicates")
     ap.add_argument("--random_init", action="store_true")
     ap.add_argument("--checkpoint", default=None, help="DINO checkpoint of the ResNeXt (default: $CVCL_PRETRAINED_DIR)")
     ap.add_argument("--precision", default="32", choices=("32", "32-split"))
@@ -517,3 +693,10 @@ def main(args):
         print(f"Accuracy: {sum(r['correct'] for r in recs) / len(recs)}")
         with open(os.path.join(args.out_dir, "nn_pixel_space_results.json"), "w") as f:
             json.dump(recs, f)
+    if args.space == "hash":
+        res = hash_duplicates(evalf, eval_labels, train, train_labels, eval_names, train_names)
+        print("\n".join(hash_summary(res)))
+        for name, key in (("hashed_eval_frames.json", "hashed_eval_frames"), ("hashed_train_frames.json", "hashed_train_frames"),
+                          ("indirect_duplicates.json", "indirect_duplicates"), ("hash_duplicates.json", "hamming_duplicates")):
+            with open(os.path.join(args.out_dir, name), "w") as f:
+                json.dump(res[key], f)

@@ -1,0 +1,166 @@
+"""Perceptual-hash duplicates (multimodal/neighbors.py: ``average_hash``, ``nearest_hamming``, ``nearest_digit_strings``) at the
+leakage check's sizes: 50 000 frames of 3 x 224 x 224 to hash, 2 200 evaluation hashes against 50 000 training hashes to search.
+
+    python tools/bench_hash.py [--nq 2200] [--nb 50000] [--frames 50000] [--size 224] [--iters 5]
+    python tools/bench_hash.py --kernels-only      # the run to put under `rocprofv3 --kernel-trace --stats`
+
+Yardsticks (nothing earlier exists to compare with):
+- hash: an eager torch composition on the same GPU -- the four taps gathered by index, grey by integer ops on them, the weighted sum,
+  the threshold, the bits packed into int64 words -- in chunks of ``--eager-chunk`` frames; its words must equal the kernel's.
+- Hamming: the hashes unpacked to 0 / 1 fp32 rows on the GPU, distance = |q| + |b| - 2 q b^T by one matmul, min / argmin; its
+  result must equal the kernel's.
+- ratio: the plain LCS dynamic programme in numpy on ONE host core (a row of the table per query digit, all base strings of the
+  slice at once), timed on ``--ratio-slice`` queries x ``--ratio-base-slice`` base strings and scaled to Nq x Nb; the reference
+  calls fuzz.ratio once per pair from nested Python loops.
+Device events after warm-up, one process; prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nq", type=int, default=2200)
+    ap.add_argument("--nb", type=int, default=50000)
+    ap.add_argument("--frames", type=int, default=50000)
+    ap.add_argument("--size", type=int, default=224)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--eager-chunk", type=int, default=5000)
+    ap.add_argument("--ratio-slice", type=int, default=4)
+    ap.add_argument("--ratio-base-slice", type=int, default=5000)
+    ap.add_argument("--kernels-only", action="store_true", help="no yardsticks (the profiled run)")
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from multimodal import neighbors as N
+    if not torch.cuda.is_available():
+        sys.exit("bench_hash: no GPU")
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    Nq, Nb, F, S = a.nq, a.nb, a.frames, a.size
+    res = {"nq": Nq, "nb": Nb, "frames": F, "size": S, "iters": a.iters}
+
+    def timed(fn, iters=a.iters):
+        fn()                                   # warm-up: loads code objects, allocates
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(iters):
+            fn()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) / iters
+
+    # ---- the hash -----------------------------------------------------------------------------------------------------------------
+    frames = torch.empty(F, 3, S, S, dtype=torch.uint8, device=dev)
+    for s in range(0, F, 4096):
+        frames[s:s + 4096] = torch.randint(0, 256, frames[s:s + 4096].shape, device=dev, generator=g, dtype=torch.uint8)
+    ms = timed(lambda: N.average_hash(frames))
+    # the taps lie in 32 of a channel's rows; their cache lines are what the memory system moves: about those rows in full
+    r = {"ms": ms, "frames_per_s": F / ms * 1e3, "tap_bytes_per_s": F * 3072 / (ms * 1e-3),
+         "tap_row_bytes_per_s": F * 3 * 32 * float(S) / (ms * 1e-3)}
+    rows = frames.permute(0, 2, 3, 1).contiguous()
+    r["nhwc_ms"] = timed(lambda: N.average_hash(rows, "NHWC"))
+    del rows
+    if not a.kernels_only:
+        d = torch.arange(16, device=dev)
+        num = (2 * d + 1) * S - 16
+        i0 = num // 32
+        w1 = (num - 32 * i0).int()
+        i1, w0 = torch.clamp(i0 + 1, max=S - 1), 32 - w1
+        shifts = torch.arange(64, device=dev)
+
+        def eager_hash(x):
+            def grey(ys, xs):
+                t = x[:, :, ys][:, :, :, xs].int()
+                return (19595 * t[:, 0] + 38470 * t[:, 1] + 7471 * t[:, 2] + 32768) >> 16
+            v = w0[:, None] * (w0 * grey(i0, i0) + w1 * grey(i0, i1)) + w1[:, None] * (w0 * grey(i1, i0) + w1 * grey(i1, i1))
+            c = ((v + 512) >> 10).reshape(x.shape[0], 256)
+            bits = (256 * c >= c.sum(dim=1, keepdim=True)).long()
+            return (bits.view(-1, 4, 64) << shifts).sum(dim=2)
+
+        def eager_all():
+            return torch.cat([eager_hash(frames[s:s + a.eager_chunk]) for s in range(0, F, a.eager_chunk)])
+
+        e = timed(eager_all, max(1, a.iters // 2))
+        r["eager_ms"] = e
+        r["speedup_vs_eager"] = e / ms
+        r["equals_eager"] = bool(torch.equal(eager_all(), N.average_hash(frames)))
+    res["hash"] = r
+    del frames
+    torch.cuda.empty_cache()
+
+    # ---- the searches ---------------------------------------------------------------------------------------------------------------
+    q = torch.randint(0, 256, (Nq, 32), device=dev, generator=g, dtype=torch.uint8).view(torch.int64)          # [Nq, 4]: all 256 bits random
+    b = torch.randint(0, 256, (Nb, 32), device=dev, generator=g, dtype=torch.uint8).view(torch.int64)
+    qg = (torch.arange(Nq, device=dev) % 22).int()
+    bg = (torch.arange(Nb, device=dev) % 22).int()
+    ms = timed(lambda: N.nearest_hamming(q, b), 20 * a.iters)
+    r = {"ms": ms, "pairs_per_s": Nq * Nb / (ms * 1e-3), "grouped22_ms": timed(lambda: N.nearest_hamming(q, b, qg, bg), 20 * a.iters)}
+    if not a.kernels_only:
+        def unpack(h):
+            return ((h[:, :, None] >> shifts) & 1).reshape(h.shape[0], 256).float()
+
+        def eager_hamming():
+            qb, bb = unpack(q), unpack(b)
+            dist = qb.sum(dim=1)[:, None] + bb.sum(dim=1)[None, :] - 2.0 * (qb @ bb.T)
+            return dist.min(dim=1)
+
+        e = timed(eager_hamming)
+        r["eager_ms"] = e
+        r["speedup_vs_eager"] = e / ms
+        ev = eager_hamming()
+        hd, hi = N.nearest_hamming(q, b)
+        # (random 256-bit hashes: the minimum is attained once; torch's argmin does not promise the first index on a tie)
+        r["equals_eager"] = bool(torch.equal(ev.values.int(), hd)) and bool(torch.equal(ev.indices, hi))
+    res["hamming"] = r
+
+    t0 = time.perf_counter()
+    (qd, ql), (bd, bl) = N.hash_digits(q), N.hash_digits(b)
+    res["hash_digits_host_ms"] = (time.perf_counter() - t0) * 1e3
+    dq, dql, db, dbl = (torch.from_numpy(x).to(dev) for x in (qd, ql, bd, bl))
+    ms = timed(lambda: N.nearest_digit_strings(dq, dql, db, dbl))
+    r = {"ms": ms, "pairs_per_s": Nq * Nb / (ms * 1e-3), "lcs_steps_per_s": Nq * float(bl.sum()) / (ms * 1e-3),
+         "grouped22_ms": timed(lambda: N.nearest_digit_strings(dq, dql, db, dbl, qg, bg))}
+    # the reference's order: frames sorted by category on both sides, so a wave's 64 queries share a category
+    qs, bs = torch.sort(qg.long()).indices, torch.sort(bg.long()).indices
+    sq, sql, sb, sbl, sqg, sbg = dq[qs].contiguous(), dql[qs].contiguous(), db[bs].contiguous(), dbl[bs].contiguous(), qg[qs], bg[bs]
+    r["grouped22_sorted_ms"] = timed(lambda: N.nearest_digit_strings(sq, sql, sb, sbl, sqg, sbg))
+    if not a.kernels_only:
+        nqs, nbs = min(a.ratio_slice, Nq), min(a.ratio_base_slice, Nb)
+        base, base_len = bd[:nbs], bl[:nbs].astype(np.int64)
+
+        def host_dp():
+            best = []
+            for i in range(nqs):
+                row = np.zeros((nbs, base.shape[1] + 1), dtype=np.int64)
+                for ca in qd[i, :ql[i]]:
+                    row[:, 1:] = np.maximum.accumulate(np.maximum(row[:, 1:], row[:, :-1] + (base == ca)), axis=1)
+                lcs = row[np.arange(nbs), base_len]
+                num, den = 200 * lcs, int(ql[i]) + base_len
+                qv, rem = num // den, num % den
+                ratio = qv + ((2 * rem > den) | ((2 * rem == den) & (qv % 2 == 1)))
+                best.append((int(ratio.max()), int(ratio.argmax())))
+            return best
+
+        torch.set_num_threads(1)
+        t0 = time.perf_counter()
+        want = host_dp()
+        e = (time.perf_counter() - t0) * 1e3
+        r["host_dp_slice"] = [nqs, nbs]
+        r["host_dp_slice_ms"] = e
+        r["host_dp_scaled_ms"] = e * (Nq / nqs) * (Nb / nbs)
+        r["speedup_vs_host_dp"] = r["host_dp_scaled_ms"] / ms
+        gr, gi = N.nearest_digit_strings(dq[:nqs], dql[:nqs], db[:nbs], dbl[:nbs])
+        r["equals_host_dp"] = [(int(x), int(y)) for x, y in zip(gr.cpu(), gi.cpu())] == want
+    res["digit_ratio"] = r
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
