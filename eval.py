@@ -87,14 +87,16 @@ def results_filename(args, cfg):
 
 
 @torch.no_grad()
-def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention_maps=False, rollout=False, clip=False):
+def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention_maps=False, rollout=False, clip=False,
+                    discard_ratio=0.0):
     """trials: list of collated batch-1 items (img, label, label_len, raw_label).  Returns per trial (soft-max list, pred).
     All trials of the list are encoded in one pass; trial t's logits are the t-th diagonal block.
     ``attention_maps``: returns (per-trial results, Grad-CAM maps [T, 4, h, w]) -- per trial the maps of its 4 images w.r.t. its
     label (``image``) or of its image w.r.t. its 4 labels (``text``), from the same encoder pass as the logits.  A ViT encoder has
     no Grad-CAM: its maps are the CLS token's last-block self-attention [T, 4, gh, gw], which do not depend on the label (``text``:
     the one image's map repeated 4 times, so the array keeps its shape); with ``rollout`` they are the CLS token's attention rollout
-    over all blocks instead, same shape.
+    over all blocks instead, same shape; a non-zero ``discard_ratio`` zeroes that share of every block's weakest attentions before
+    the chain (attention_maps.vit_attention_rollout_discard).
     ``clip``: the labels are CLIP token rows ([1, 1, 77] / [1, 4, 77] per trial, reference eval.py:205-207, 224-226): stacked to
     [T, 77] / [4T, 77] and scored by ``model(imgs, tokens)``."""
     T = len(trials)
@@ -124,7 +126,12 @@ def evaluate_trials(model, trials, eval_type, device, datamodule=None, attention
     if clip:
         logits_per_image, logits_per_text = model(imgs, tokens)
     elif attention_maps and getattr(getattr(model, "vision_encoder", None), "vit_dino", False):
-        logits_per_image, logits_per_text, maps = model.self_attention_maps(imgs, labels.to(device), lens.to(device), rollout=rollout)
+        if rollout and discard_ratio:
+            from multimodal.attention_maps import vit_attention_rollout_discard
+            maps = vit_attention_rollout_discard(model.vision_encoder, imgs, discard_ratio)
+            logits_per_image, logits_per_text = model(imgs, labels.to(device), lens.to(device))
+        else:
+            logits_per_image, logits_per_text, maps = model.self_attention_maps(imgs, labels.to(device), lens.to(device), rollout=rollout)
         if eval_type == "image":                          # [4T, gh, gw] -> [T, 4, gh, gw]
             maps = maps.view(T, n_per, *maps.shape[1:])
         else:                                             # one image per trial: its map along the 4 axis
@@ -184,6 +191,10 @@ def check_clip_args(args):
 
 
 def main(args):
+    if not 0 <= args.rollout_discard_ratio < 1:            # (false for nan)
+        raise SystemExit(f"--rollout_discard_ratio {args.rollout_discard_ratio}: a share R of the attentions with 0 <= R < 1")
+    if args.rollout_discard_ratio and not args.attention_rollout:
+        raise SystemExit("--rollout_discard_ratio R thins the blocks' attentions of --attention_rollout; give that flag as well")
     if args.clip_eval:
         check_clip_args(args)
     saycam = args.eval_dataset == "saycam" and not args.clip_eval and bool(data_dir_from(args))
@@ -259,7 +270,7 @@ def main(args):
     def flush():
         nonlocal first
         res = evaluate_trials(model, pending, args.eval_type, device, data, attention_maps=want_maps, rollout=args.attention_rollout,
-                              clip=args.clip_eval)
+                              clip=args.clip_eval, discard_ratio=args.rollout_discard_ratio)
         if want_maps:
             res, maps = res
             cams.append(maps.cpu())
@@ -368,6 +379,10 @@ def _parser():
                         help="ViT checkpoints: the maps of --attention_maps / --plot_attention are the CLS token's attention rollout "
                              "over all blocks (head-mean attention plus the residual path, multiplied through the blocks) instead of "
                              "the last block's CLS row; same shape [n_trials, 4, gh, gw].  An error with a ResNeXt checkpoint")
+    parser.add_argument("--rollout_discard_ratio", type=float, default=0.0, metavar="R",
+                        help="with --attention_rollout: before the blocks are multiplied, set the share R (0 <= R < 1; vit-explain "
+                             "plots 0.9) of the weakest attentions of every block and image to zero, which keeps the maps of a deep "
+                             "ViT from coming out near uniform; 0 (default): the plain rollout")
     return parser
 
 

@@ -755,6 +755,16 @@ enum { CVCL_FUSE_MEAN = 0, CVCL_FUSE_MAX = 1, CVCL_FUSE_MIN = 2 };
 int cvcl_attention_head_fuse(int dtype, const void* qkv, float* fused, int B, int T, int heads, int head_dim, float scale, int fuse,
                              void* stream);
 int cvcl_attention_rollout(const float* fused, float* out, int n_layers, int B, int T, int start_layer, int q_rows, void* stream);
+/* The discard_ratio variant of the rollout (Gildenblat's vit-explain; csrc/vit_discard.hip): between the fuse and the chain, the k
+ * weakest attentions of every fused matrix are zeroed in place.  fused [n_mats][T][T] fp32, n_mats = n_layers B; per matrix,
+ * flattened row-major to M = T T elements: S = the first k indices of a stable ascending sort of the values (ties go to the lowest
+ * flat index); every element with its index in S \ {0} becomes +0.0, every other element keeps its bits.  Flat index 0 (CLS -> CLS)
+ * is never zeroed but counts towards k.  The caller computes k = int(T T discard_ratio).  Exact: a radix select over the uint32 bit
+ * patterns (non-negative floats order as unsigned integers), one workgroup per matrix, integer LDS histograms, no global atomics,
+ * no workspace; two calls give the same bits.  Negative or NaN values: unspecified result, same accesses.  CVCL_EINVAL before
+ * anything is enqueued on a null pointer, n_mats <= 0, T outside 1 .. 4096, k outside 0 .. T T - 1; k == 0 returns CVCL_OK without
+ * a launch.  CVCL_K_ATTENTION.                                                                                                  */
+int cvcl_attention_discard(float* fused, int n_mats, int T, long k, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Beam-search decoding of the LSTM language model (csrc/textgen.hip; its LSTM cells: csrc/lstm.hip).  Replaces the reference's LanguageModel.beam_search_decode

@@ -251,10 +251,23 @@ def vit_attention_rollout(vision_model, x, size=None, head_fusion="mean", start_
     A^_L ... A^_{start_layer + 1} with A^_l = (F_l + I) / rowsum(F_l + I), F_l block l's attention fused over the heads
     (``head_fusion``: "mean", "max", "min") -> [B, gh, gw] fp32.  Where vit_cls_attention shows the last block's mixing step alone,
     this attributes the CLS token to the input patches through every block and the residual paths.  Each map sums to 1 - R[0, 0].
-    ``size=(H, W)``: resized bicubically (cvcl_bicubic_resize).  The ``discard_ratio`` variant is not built."""
+    ``size=(H, W)``: resized bicubically (cvcl_bicubic_resize).  The ``discard_ratio`` variant (the weakest attentions of every
+    block zeroed before the chain) is vit_attention_rollout_discard below."""
+    return vit_attention_rollout_discard(vision_model, x, 0.0, size, head_fusion, start_layer)
+
+
+@torch.no_grad()
+def vit_attention_rollout_discard(vision_model, x, discard_ratio, size=None, head_fusion="mean", start_layer=0):
+    """vit_attention_rollout in the form people plot (Gildenblat's vit-explain, ``discard_ratio`` 0.9): in every block's fused
+    attention F_l[b], flattened to T T elements, the k = int(T T discard_ratio) smallest are set to zero before (F_l + I) is
+    normalised and chained -- ties go to the lowest flat index; element 0 (CLS -> CLS) is kept but counts towards k; each block and
+    each image is selected on its own (the original masks batch element 0 only: a bug not copied).  Without it the rollout of a
+    12-block ViT is close to uniform.  0 <= discard_ratio < 1, ValueError otherwise; 0 is vit_attention_rollout bit for bit.
+    -> [B, gh, gw] fp32; each map still sums to 1 - R[0, 0]."""
     from . import vit_maps
+    vit_maps.check_discard_ratio(discard_ratio)
     vit = _vit_of(vision_model)
-    rows, (gh, gw) = vit_maps.attention_rollout(vit, x, head_fusion, start_layer, q_rows=1)
+    rows, (gh, gw) = vit_maps.attention_rollout(vit, x, head_fusion, start_layer, q_rows=1, discard_ratio=discard_ratio)
     maps = rows[:, 0, 1:].contiguous().view(-1, gh, gw)
     if size is not None:
         maps = bicubic_resize(maps, size)

@@ -1,7 +1,8 @@
 """The DINO ViT's two analysis entry points on libcvcl_hip (reference multimodal/vision_transformer_dino_mugs.py:252-269):
 ``get_last_selfattention`` (the last block's softmax(q k^T scale), written out by csrc/vit_maps.hip) and
 ``get_intermediate_layers`` (the final ``norm`` of the token matrix after each of the last ``n`` blocks); and the attention
-rollout over all blocks (``attention_rollout``; Abnar & Zuidema 2020, not in the reference), which shares the walk.
+rollout over all blocks (``attention_rollout``; Abnar & Zuidema 2020, not in the reference), which shares the walk, with its
+``discard_ratio`` variant (``attention_discard``, csrc/vit_discard.hip).
 
 Both need the token matrix part of the way through the trunk, so they walk the first ``k`` blocks with ``vit_hip._Trunk``, the
 frozen forward's own prologue and plain block, in the model's compute dtype (fp32 or bf16): cvcl_im2col_patches, the patch GEMM,
@@ -113,15 +114,44 @@ def _is_int(v) -> bool:
     return isinstance(v, int) and not isinstance(v, bool)
 
 
+DISCARD_MAX_T = 4096                 # cvcl_attention_discard's limit: T T elements counted in 32 bits
+
+
+def attention_discard(fused: torch.Tensor, k: int) -> torch.Tensor:
+    """fused [n, B, T, T] fp32 (contiguous, non-negative), IN PLACE: in every [T, T] matrix, flattened row-major, the ``k`` smallest
+    elements become +0.0 -- the first k indices of a stable ascending sort, so ties go to the lowest flat index -- except flat index
+    0 (CLS -> CLS), which is never zeroed but counts towards k.  Every other element keeps its bits.  -> ``fused``.  k = 0 launches
+    nothing."""
+    if fused.dim() != 4 or fused.shape[2] != fused.shape[3] or fused.dtype != torch.float32 or not fused.is_contiguous():
+        raise H.CvclError(f"fused {tuple(fused.shape)} {fused.dtype} is not a contiguous fp32 [n, B, T, T]")
+    n, B, T, _ = fused.shape
+    if not _is_int(k) or not 0 <= k <= T * T - 1:
+        raise ValueError(f"k = {k!r} outside 0 .. T*T - 1 = {T * T - 1}")
+    H.check(H.lib().cvcl_attention_discard(H.ptr(fused, torch.float32), n * B, T, k, H.stream_ptr()), "cvcl_attention_discard")
+    return fused
+
+
+def check_discard_ratio(discard_ratio) -> float:
+    """``discard_ratio`` as a float: a finite int or float (no bool) with 0 <= r < 1, ValueError otherwise."""
+    r = discard_ratio
+    if isinstance(r, bool) or not isinstance(r, (int, float)) or not 0 <= r < 1:          # (nan fails both comparisons)
+        raise ValueError(f"discard_ratio = {r!r}: a number with 0 <= discard_ratio < 1")
+    return float(r)
+
+
 def attention_rollout(model, x: torch.Tensor, head_fusion: str = "mean", start_layer: int = 0, q_rows: int = 1,
-                      slab_bytes: int | None = None):
+                      slab_bytes: int | None = None, discard_ratio: float = 0.0):
     """-> (R [B, q_rows, T] fp32, (gh, gw)): the first ``q_rows`` rows of A^_L ... A^_{s+1}, s = ``start_layer``, where
     A^_l = (F_l + I) / rowsum(F_l + I) and F_l is block l's softmax(q k^T scale) fused over the heads by ``head_fusion``.  Row 0
     without column 0 is the CLS token's map over the patch grid.  One walk over the blocks: each block past ``start_layer`` has its
     qkv fused into a slab [L - s, B, T, T] (cvcl_attention_head_fuse), then one cvcl_attention_rollout launch runs the chain.  A batch
     whose slab would exceed ``slab_bytes`` (default ROLLOUT_SLAB_BYTES) is walked in chunks of images; an image's rows do not depend
-    on the chunking.  The last block's attention output and MLP are not computed: nothing reads them."""
+    on the chunking.  The last block's attention output and MLP are not computed: nothing reads them.
+    ``discard_ratio`` r > 0 (Gildenblat's vit-explain plots r = 0.9): before the chain, the k = int(T T r) weakest attentions of
+    every F_l[b] are zeroed (``attention_discard``: one cvcl_attention_discard launch per slab); each block and each image is
+    selected on its own.  With the default 0 nothing is launched and every output keeps its bits."""
     depth = len(model.blocks)
+    ratio = check_discard_ratio(discard_ratio)
     if head_fusion not in HEAD_FUSIONS:
         raise ValueError(f"head_fusion = {head_fusion!r}: one of {sorted(HEAD_FUSIONS)}")
     if depth < 1:
@@ -141,6 +171,7 @@ def attention_rollout(model, x: torch.Tensor, head_fusion: str = "mean", start_l
     n = depth - start_layer
     per_image = n * T * T * 4
     chunk = max(1, min(B, budget // per_image)) if B else 1
+    k = int(T * T * ratio)
     with torch.no_grad():
         if not x.is_cuda:
             raise H.CvclError("the ViT attention maps need device tensors (got a CPU tensor); there is no CPU fallback")
@@ -156,6 +187,8 @@ def attention_rollout(model, x: torch.Tensor, head_fusion: str = "mean", start_l
                                         out=slab[i - start_layer])
                 if i + 1 < depth:
                     t.block(bw, have_qkv=fused)
+            if k > 0:
+                attention_discard(slab, k)
             rows = rollout_chain(slab, 0, q_rows)
             if chunk >= B:
                 return rows, (gh, gw)
