@@ -2,6 +2,7 @@
 lab library (CVCL_ATT_PAIR=0 / 1) and diff: the paired-query-tile kernel must reproduce the one-tile-per-wave kernel bit for bit.
 Also times cvcl_attention at the C4 shape."""
 import hashlib, os, sys, torch
+import timing
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "multimodal-baby_amd"))
 from multimodal import _hip as H
 dev = torch.device("cuda:0")
@@ -39,12 +40,7 @@ if os.environ.get("ATT_TIME", "1") == "1":
     qkv = torch.randn(B * T, 3 * D, device=dev).bfloat16()
     out = torch.empty(B * T, D, dtype=torch.bfloat16, device=dev)
     o8 = torch.zeros(B * T, D, dtype=torch.uint8, device=dev); bs = torch.zeros((D // 128) * B * T * 4, dtype=torch.uint8, device=dev)
-    for name, call in (("bf16", lambda: H.lib().cvcl_attention(H.BF16, H.ptr(qkv), None, H.ptr(out), B, T, heads, 64, 0.125, H.stream_ptr())),
-                       ("mx", lambda: H.lib().cvcl_attention_mx(H.ptr(qkv), H.ptr(o8), H.ptr(bs), B, T, heads, 64, 0.125, H.stream_ptr()))):
-        for _ in range(3): call()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20): call()
-        e1.record(); torch.cuda.synchronize()
-        print(f"# time {name} T=197 B=256: {e0.elapsed_time(e1) / 20 * 1000:.1f} us  (CVCL_ATT_PAIR={os.environ.get('CVCL_ATT_PAIR', 'default')})")
+    sides = {"bf16": (lambda: H.lib().cvcl_attention(H.BF16, H.ptr(qkv), None, H.ptr(out), B, T, heads, 64, 0.125, H.stream_ptr())),
+             "mx": (lambda: H.lib().cvcl_attention_mx(H.ptr(qkv), H.ptr(o8), H.ptr(bs), B, T, heads, 64, 0.125, H.stream_ptr()))}
+    for name, t in timing.measure(sides).items():
+        print(f"# time {name} T=197 B=256: {timing.text(t, 1e3)} us  (CVCL_ATT_PAIR={os.environ.get('CVCL_ATT_PAIR', 'default')})")

@@ -6,25 +6,24 @@ C = 22 categories) and at a vocabulary-scale one (N = 50 000, D = 512, C = 2350)
 
 Yardstick: index_add_ + division for the means, F.normalize and ``@`` for the matrices, the triangle selection and centred double
 moments for r -- what a torch user would write in place of the reference's per-entry loops (which are not timed: they are minutes).
-Per shape and side: warm-up, then ``repeats`` windows of calls sized to ``window-ms`` between two device events; the median window
-per call is reported, the spread (min .. max) beside it, the two sides in alternation.  Also the kernels one by one, and the
+Timed by tools/timing.py: us per call, median [min, max], the sides in alternation.  Also the kernels one by one, and the
 class-mean kernel's achieved GB/s over the bytes it has to move (N D 4 read + N 4 labels + C D 4 written).  Prints one JSON line."""
 import argparse
 import json
 import os
-import statistics
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="4400x512x22,50000x512x2350")
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--window-ms", type=float, default=200.0)
-    a = ap.parse_args()
+    timing.add_arguments(ap)
+    a = ap.parse_args(argv)
     import torch
     import torch.nn.functional as F
     from multimodal import alignment as A
@@ -32,29 +31,9 @@ def main():
         sys.exit("bench_alignment: no GPU")
     dev = torch.device("cuda:0")
 
-    def window(fn, calls):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(calls):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / calls               # us per call
-
-    def measure(fns):
-        """{name: fn} -> {name: {"us", "min_us", "max_us", "calls"}}; the sides alternate window by window"""
-        calls = {}
-        for k, fn in fns.items():
-            for _ in range(3):
-                fn()
-            torch.cuda.synchronize()
-            one = window(fn, 5)
-            calls[k] = max(5, min(20000, int(a.window_ms * 1e3 / max(one, 1.0))))
-        samples = {k: [] for k in fns}
-        for _ in range(a.repeats):
-            for k, fn in fns.items():
-                samples[k].append(window(fn, calls[k]))
-        return {k: {"us": statistics.median(v), "min_us": min(v), "max_us": max(v), "calls": calls[k]} for k, v in samples.items()}
+    def measure_us(fns):
+        """{name: fn} -> {name: {"us", "min_us", "max_us", "calls"}}"""
+        return {k: {**timing.entry(r, "us", 1e3), "calls": r["calls"]} for k, r in timing.measure(fns, **timing.keywords(a)).items()}
 
     out = {"repeats": a.repeats, "window_ms": a.window_ms, "device": torch.cuda.get_device_name(0), "shapes": {}}
     for shape in a.shapes.split(","):
@@ -93,11 +72,11 @@ def main():
         si, st = A.cosine_matrix(means), A.cosine_matrix(text)
         mn, tn = F.normalize(means, dim=1), F.normalize(text, dim=1)
         r_hip, r_torch = float(hip_chain()[0][1]), float(torch_chain()[0])
-        res = measure({"hip_chain": hip_chain, "torch_chain": torch_chain})
-        res.update(measure({"hip_class_means": lambda: A._class_means(x, lab32, Cn), "torch_class_means": torch_means}))
-        res.update(measure({"hip_cosine_self": lambda: A.cosine_matrix(means), "torch_cosine_self": lambda: mn @ mn.T,
-                            "hip_cosine_pair": lambda: A.cosine_matrix(means, text)}))
-        res.update(measure({"hip_pearson": lambda: A._triu_pearson(si, st), "torch_pearson": lambda: torch_pearson(si, st)}))
+        res = measure_us({"hip_chain": hip_chain, "torch_chain": torch_chain})
+        res.update(measure_us({"hip_class_means": lambda: A._class_means(x, lab32, Cn), "torch_class_means": torch_means}))
+        res.update(measure_us({"hip_cosine_self": lambda: A.cosine_matrix(means), "torch_cosine_self": lambda: mn @ mn.T,
+                               "hip_cosine_pair": lambda: A.cosine_matrix(means, text)}))
+        res.update(measure_us({"hip_pearson": lambda: A._triu_pearson(si, st), "torch_pearson": lambda: torch_pearson(si, st)}))
         moved = N * D * 4 + N * 4 + Cn * D * 4
         res["class_means_GBps"] = moved / (res["hip_class_means"]["us"] * 1e-6) / 1e9
         res["torch_class_means_GBps"] = moved / (res["torch_class_means"]["us"] * 1e-6) / 1e9

@@ -9,6 +9,8 @@ import time
 import numpy as np
 import torch
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 from multimodal.augment import DeviceFrameAugment  # noqa: E402
@@ -26,18 +28,10 @@ t0 = time.perf_counter()
 for _ in range(10):
     p = aug.sample_params(a.batch, 224, 224)
 t_draw = (time.perf_counter() - t0) / 10
-for _ in range(3):
-    aug(frames, p)
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-for _ in range(20):
-    aug(frames, p)
-e1.record()
-torch.cuda.synchronize()
-ms = e0.elapsed_time(e1) / 20
+t = timing.measure({"aug": lambda: aug(frames, p)})["aug"]
+ms = t["ms"]
 byt = a.batch * (224 * 224 * 3 + 3 * 224 * 224 * 4)
-print(f"device transform: {ms * 1e3:.0f} us per batch of {a.batch} ({a.batch / ms * 1e3:.0f} frames/s, {byt / ms / 1e6:.0f} GB/s of frame read + tensor "
+print(f"device transform: {timing.text(t, 1e3, '.0f')} us per batch of {a.batch} ({a.batch / ms * 1e3:.0f} frames/s, {byt / ms / 1e6:.0f} GB/s of frame read + tensor "
       f"write); host draws {t_draw * 1e3:.1f} ms per batch")
 try:
     from PIL import Image, ImageFilter

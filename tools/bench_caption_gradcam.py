@@ -7,19 +7,20 @@ B = 256 captions of L = 25 tokens, 224 x 224, fp32 trunk:
       [B, L-1, 7, 7] result to the host (both sides end with their maps as numpy arrays).
 Also: the kernel-class split of (b) (the library's per-launch event brackets: shares, not wall time), its launch count, and the seed
 kernel alone at the sweep's largest step (rows = B (L - 1)) with its streamed bytes per second, on one buffer set (warm
-Infinity Cache) and on four rotating sets that together exceed it (HBM).  Device-event timing after
-warm-up, medians over --iters repetitions, one process.  Prints one JSON line.
+Infinity Cache) and on four rotating sets that together exceed it (HBM).  Timed by tools/timing.py on
+single calls: median [min, max] of --launches bracketed calls per side, (a) and (b) in turn.  Prints one JSON line.
 
-    python tools/bench_caption_gradcam.py [--batch 256] [--length 25] [--iters 5] [--loop_images 4]"""
+    python tools/bench_caption_gradcam.py [--batch 256] [--length 25] [--launches 5] [--loop_images 4]"""
 import argparse
 import contextlib
 import io
 import json
 import os
-import statistics
 import sys
 
 import torch
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
@@ -31,26 +32,13 @@ from multimodal.multimodal_data_module import read_vocab                        
 from multimodal.multimodal_lit import MultiModalLitModel                                     # noqa: E402
 
 
-def median_ms(fn, iters):
-    out = []
-    for _ in range(iters):
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b))
-    return statistics.median(out)
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--length", type=int, default=25)
-    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--launches", type=int, default=5, help="bracketed calls per side")
     ap.add_argument("--loop_images", type=int, default=4, help="images timed in the per-word loop (a)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     ns = argparse.Namespace(
         embedding_type="flat", embedding_dim=512, pretrained_cnn=False, cnn_model="resnext50_32x4d", cnn_dino=False, vit_dino=False,
@@ -91,10 +79,8 @@ def main():
     def batched():
         return gradCAM_captions(lit, x, y, n).cpu().numpy()         # on the host, where the loop's maps end as well
 
-    loop()
-    batched()
-    ms_loop = median_ms(loop, max(1, args.iters // 2))
-    ms_batched = median_ms(batched, args.iters)
+    sides = timing.measure({"loop": loop, "batched": batched}, calls=1, repeats=args.launches, warmup=1)      # single calls, in turn
+    ms_loop, ms_batched = sides["loop"]["ms"], sides["batched"]["ms"]
     torch.cuda.synchronize()
     H.prof_enable(True)
     batched()
@@ -116,12 +102,6 @@ def main():
         H.check(lib.cvcl_lstm_cell_bwd_seeds(H.ptr(gact), H.ptr(csave), H.ptr(c0), H.ptr(n), 0, H.ptr(d_out), H.ptr(dh), H.ptr(dc),
                                              H.ptr(dG), H.ptr(carry), B, K, Hd, rows, H.stream_ptr()), "cvcl_lstm_cell_bwd_seeds")
 
-    def seeds10():
-        for _ in range(10):
-            seeds()
-
-    seeds10()
-    us_seed = median_ms(seeds10, max(5, args.iters)) * 100.0
     # the same launch over SETS rotating buffer sets, together larger than the 256 MiB Infinity Cache: every launch finds its rows in HBM
     SETS = 4
     rot = [(torch.randn(rows, Hd, **f32), torch.randn(rows, Hd, **f32), torch.empty(rows, 4 * Hd, **f32), torch.empty(rows, Hd, **f32))
@@ -133,20 +113,20 @@ def main():
             H.check(lib.cvcl_lstm_cell_bwd_seeds(H.ptr(gact), H.ptr(csave), H.ptr(c0), H.ptr(n), 0, H.ptr(d_out), H.ptr(rh), H.ptr(rc),
                                                  H.ptr(rg), H.ptr(rk), B, K, Hd, rows, H.stream_ptr()), "cvcl_lstm_cell_bwd_seeds")
 
-    seeds_rotating()
-    us_cold = median_ms(seeds_rotating, max(5, args.iters)) * 1e3 / 12
+    kern = timing.measure({"warm": seeds, "rotating": seeds_rotating}, calls={"warm": 10, "rotating": 1}, repeats=max(5, args.launches), warmup=1)
+    us_seed, us_cold = kern["warm"]["ms"] * 1e3, kern["rotating"]["ms"] * 1e3 / 12
     seed_bytes = rows * Hd * 4 * 8 + B * Hd * 4 * 7          # per row: dh, dc in; 4 gate gradients, dc, carry out; the captions' saved rows once
     maps = B * K
     res = {"batch": B, "length": L, "vocab": V, "maps": maps,
-           "a_loop": {"images": args.loop_images, "ms_per_map": round(ms_loop / (args.loop_images * K), 4),
+           "a_loop": {"images": args.loop_images, **timing.entry(sides["loop"], "ms_per_map", 1.0 / (args.loop_images * K), 4),
                       "maps_per_s": round(args.loop_images * K / ms_loop * 1e3, 1)},
-           "b_batched": {"ms": round(ms_batched, 3), "maps_per_s": round(maps / ms_batched * 1e3, 1), "classes": split,
+           "b_batched": {**timing.entry(sides["batched"], digits=3), "maps_per_s": round(maps / ms_batched * 1e3, 1), "classes": split,
                          "launches": sum(v["launches"] for v in split.values())},
            "speedup_per_map": round((ms_loop / (args.loop_images * K)) / (ms_batched / maps), 1),
-           "seed_kernel": {"rows": rows, "hidden": Hd, "us": round(us_seed, 2), "bytes": seed_bytes,
+           "seed_kernel": {"rows": rows, "hidden": Hd, **timing.entry(kern["warm"], "us", 1e3, 2), "bytes": seed_bytes,
                            "gb_per_s": round(seed_bytes / (us_seed * 1e-6) / 1e9, 1),
                            "rotating_sets": SETS, "rotating_footprint_mb": round(SETS * rows * Hd * 4 * 7 / 1e6, 1),
-                           "rotating_us": round(us_cold, 2), "rotating_gb_per_s": round(seed_bytes / (us_cold * 1e-6) / 1e9, 1)}}
+                           **timing.entry(kern["rotating"], "rotating_us", 1e3 / 12, 2), "rotating_gb_per_s": round(seed_bytes / (us_cold * 1e-6) / 1e9, 1)}}
     print(json.dumps(res))
 
 

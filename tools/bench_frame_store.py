@@ -8,14 +8,13 @@ them and packs them into a frame store (tools/pack_frames.py).  Measured, each o
   (a) host     workers decode + transform on the host (fp32 batch), then the copy to the device
   (b) device   --device_frames: workers decode (uint8 batch), copy, cvcl_augment_frames on the device
   (c) store    --frame_store: the loader yields indices, cvcl_augment_frames_indexed reads the HBM-resident store
-and, device-event timed and alternated in one loop, cvcl_augment_frames_indexed on 256 scattered rows of the store against
+and, as single launches alternated by tools/timing.py, cvcl_augment_frames_indexed on 256 scattered rows of the store against
 cvcl_augment_frames on the same 256 frames gathered into a contiguous batch, for the identity transform and the
 --augment_frames draws.  Worker processes are spawned, not forked, so none of them holds the GPU open."""
 import argparse
 import json
 import os
 import random
-import statistics
 import sys
 import tempfile
 import time
@@ -27,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import pack_frames  # noqa: E402
+import timing  # noqa: E402
 from multimodal.augment import DeviceFrameAugment  # noqa: E402
 from multimodal.frame_store import FrameStore  # noqa: E402
 from multimodal.multimodal_data_module import FrameSource, HostFrameTransform, multiModalDataset_collate_fn, read_vocab  # noqa: E402
@@ -78,21 +78,12 @@ def feed_rate(dl, to_batch, warmup, steps, dev):
 
 
 def launch_pair(store, aug, params, index, gathered, reps):
-    """median device time (us) of the indexed and the plain launch, alternated"""
+    """device time (us) of the indexed and the plain launch: single launches, alternated"""
     idx_d = index.to(store.device)
-    for _ in range(5):
-        store._launch(idx_d, aug, params)
-        aug(gathered, params)
-    times = {"indexed": [], "plain": []}
-    for _ in range(reps):
-        for name, fn in (("indexed", lambda: store._launch(idx_d, aug, params)), ("plain", lambda: aug(gathered, params))):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1) * 1e3)
-    return {k: {"median_us": statistics.median(v), "min_us": min(v), "p90_us": sorted(v)[int(0.9 * len(v))]} for k, v in times.items()}
+    t = timing.measure({"indexed": lambda: store._launch(idx_d, aug, params), "plain": lambda: aug(gathered, params)},
+                       calls=1, repeats=reps, warmup=5)
+    return {k: {"median_us": r["ms"] * 1e3, "min_us": r["min_ms"] * 1e3, "max_us": r["max_ms"] * 1e3,
+                "p90_us": sorted(r["samples"])[int(0.9 * reps)] * 1e3} for k, r in t.items()}
 
 
 def main(argv=None):

@@ -1,7 +1,7 @@
 """Perceptual-hash duplicates (multimodal/neighbors.py: ``average_hash``, ``nearest_hamming``, ``nearest_digit_strings``) at the
 leakage check's sizes: 50 000 frames of 3 x 224 x 224 to hash, 2 200 evaluation hashes against 50 000 training hashes to search.
 
-    python tools/bench_hash.py [--nq 2200] [--nb 50000] [--frames 50000] [--size 224] [--iters 5]
+    python tools/bench_hash.py [--nq 2200] [--nb 50000] [--frames 50000] [--size 224] [--repeats 7] [--window-ms 200]
     python tools/bench_hash.py --kernels-only      # the run to put under `rocprofv3 --kernel-trace --stats`
 
 Yardsticks (nothing earlier exists to compare with):
@@ -12,29 +12,32 @@ Yardsticks (nothing earlier exists to compare with):
 - ratio: the plain LCS dynamic programme in numpy on ONE host core (a row of the table per query digit, all base strings of the
   slice at once), timed on ``--ratio-slice`` queries x ``--ratio-base-slice`` base strings and scaled to Nq x Nb; the reference
   calls fuzz.ratio once per pair from nested Python loops.
-Device events after warm-up, one process; prints one JSON line."""
+Device work timed by tools/timing.py (ms per call, median [min, max], a search and its yardstick alternating), the host yardstick by
+the host clock; prints one JSON line."""
 import argparse
 import json
 import os
 import sys
 import time
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=2200)
     ap.add_argument("--nb", type=int, default=50000)
     ap.add_argument("--frames", type=int, default=50000)
     ap.add_argument("--size", type=int, default=224)
-    ap.add_argument("--iters", type=int, default=5)
+    timing.add_arguments(ap)
     ap.add_argument("--eager-chunk", type=int, default=5000)
     ap.add_argument("--ratio-slice", type=int, default=4)
     ap.add_argument("--ratio-base-slice", type=int, default=5000)
     ap.add_argument("--kernels-only", action="store_true", help="no yardsticks (the profiled run)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import numpy as np
     import torch
     from multimodal import neighbors as N
@@ -43,30 +46,18 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     Nq, Nb, F, S = a.nq, a.nb, a.frames, a.size
-    res = {"nq": Nq, "nb": Nb, "frames": F, "size": S, "iters": a.iters}
+    res = {"nq": Nq, "nb": Nb, "frames": F, "size": S, "repeats": a.repeats, "window_ms": a.window_ms}
 
-    def timed(fn, iters=a.iters):
-        fn()                                   # warm-up: loads code objects, allocates
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(iters):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) / iters
+    def measure(sides):
+        """{output key: fn} -> {key, min_key, max_key of every side}, the sides alternating"""
+        return timing.entries(timing.measure(sides, **timing.keywords(a)))
 
     # ---- the hash -----------------------------------------------------------------------------------------------------------------
     frames = torch.empty(F, 3, S, S, dtype=torch.uint8, device=dev)
     for s in range(0, F, 4096):
         frames[s:s + 4096] = torch.randint(0, 256, frames[s:s + 4096].shape, device=dev, generator=g, dtype=torch.uint8)
-    ms = timed(lambda: N.average_hash(frames))
-    # the taps lie in 32 of a channel's rows; their cache lines are what the memory system moves: about those rows in full
-    r = {"ms": ms, "frames_per_s": F / ms * 1e3, "tap_bytes_per_s": F * 3072 / (ms * 1e-3),
-         "tap_row_bytes_per_s": F * 3 * 32 * float(S) / (ms * 1e-3)}
     rows = frames.permute(0, 2, 3, 1).contiguous()
-    r["nhwc_ms"] = timed(lambda: N.average_hash(rows, "NHWC"))
-    del rows
+    sides = {"ms": lambda: N.average_hash(frames), "nhwc_ms": lambda: N.average_hash(rows, "NHWC")}
     if not a.kernels_only:
         d = torch.arange(16, device=dev)
         num = (2 * d + 1) * S - 16
@@ -87,12 +78,16 @@ def main():
         def eager_all():
             return torch.cat([eager_hash(frames[s:s + a.eager_chunk]) for s in range(0, F, a.eager_chunk)])
 
-        e = timed(eager_all, max(1, a.iters // 2))
-        r["eager_ms"] = e
-        r["speedup_vs_eager"] = e / ms
+        sides["eager_ms"] = eager_all
+    r = measure(sides)
+    ms = r["ms"]
+    # the taps lie in 32 of a channel's rows; their cache lines are what the memory system moves: about those rows in full
+    r.update({"frames_per_s": F / ms * 1e3, "tap_bytes_per_s": F * 3072 / (ms * 1e-3), "tap_row_bytes_per_s": F * 3 * 32 * float(S) / (ms * 1e-3)})
+    if not a.kernels_only:
+        r["speedup_vs_eager"] = r["eager_ms"] / ms
         r["equals_eager"] = bool(torch.equal(eager_all(), N.average_hash(frames)))
     res["hash"] = r
-    del frames
+    del frames, rows
     torch.cuda.empty_cache()
 
     # ---- the searches ---------------------------------------------------------------------------------------------------------------
@@ -100,8 +95,7 @@ def main():
     b = torch.randint(0, 256, (Nb, 32), device=dev, generator=g, dtype=torch.uint8).view(torch.int64)
     qg = (torch.arange(Nq, device=dev) % 22).int()
     bg = (torch.arange(Nb, device=dev) % 22).int()
-    ms = timed(lambda: N.nearest_hamming(q, b), 20 * a.iters)
-    r = {"ms": ms, "pairs_per_s": Nq * Nb / (ms * 1e-3), "grouped22_ms": timed(lambda: N.nearest_hamming(q, b, qg, bg), 20 * a.iters)}
+    sides = {"ms": lambda: N.nearest_hamming(q, b), "grouped22_ms": lambda: N.nearest_hamming(q, b, qg, bg)}
     if not a.kernels_only:
         def unpack(h):
             return ((h[:, :, None] >> shifts) & 1).reshape(h.shape[0], 256).float()
@@ -111,9 +105,11 @@ def main():
             dist = qb.sum(dim=1)[:, None] + bb.sum(dim=1)[None, :] - 2.0 * (qb @ bb.T)
             return dist.min(dim=1)
 
-        e = timed(eager_hamming)
-        r["eager_ms"] = e
-        r["speedup_vs_eager"] = e / ms
+        sides["eager_ms"] = eager_hamming
+    r = measure(sides)
+    r["pairs_per_s"] = Nq * Nb / (r["ms"] * 1e-3)
+    if not a.kernels_only:
+        r["speedup_vs_eager"] = r["eager_ms"] / r["ms"]
         ev = eager_hamming()
         hd, hi = N.nearest_hamming(q, b)
         # (random 256-bit hashes: the minimum is attained once; torch's argmin does not promise the first index on a tie)
@@ -124,13 +120,13 @@ def main():
     (qd, ql), (bd, bl) = N.hash_digits(q), N.hash_digits(b)
     res["hash_digits_host_ms"] = (time.perf_counter() - t0) * 1e3
     dq, dql, db, dbl = (torch.from_numpy(x).to(dev) for x in (qd, ql, bd, bl))
-    ms = timed(lambda: N.nearest_digit_strings(dq, dql, db, dbl))
-    r = {"ms": ms, "pairs_per_s": Nq * Nb / (ms * 1e-3), "lcs_steps_per_s": Nq * float(bl.sum()) / (ms * 1e-3),
-         "grouped22_ms": timed(lambda: N.nearest_digit_strings(dq, dql, db, dbl, qg, bg))}
     # the reference's order: frames sorted by category on both sides, so a wave's 64 queries share a category
     qs, bs = torch.sort(qg.long()).indices, torch.sort(bg.long()).indices
     sq, sql, sb, sbl, sqg, sbg = dq[qs].contiguous(), dql[qs].contiguous(), db[bs].contiguous(), dbl[bs].contiguous(), qg[qs], bg[bs]
-    r["grouped22_sorted_ms"] = timed(lambda: N.nearest_digit_strings(sq, sql, sb, sbl, sqg, sbg))
+    r = measure({"ms": lambda: N.nearest_digit_strings(dq, dql, db, dbl), "grouped22_ms": lambda: N.nearest_digit_strings(dq, dql, db, dbl, qg, bg),
+                 "grouped22_sorted_ms": lambda: N.nearest_digit_strings(sq, sql, sb, sbl, sqg, sbg)})
+    ms = r["ms"]
+    r.update({"pairs_per_s": Nq * Nb / (ms * 1e-3), "lcs_steps_per_s": Nq * float(bl.sum()) / (ms * 1e-3)})
     if not a.kernels_only:
         nqs, nbs = min(a.ratio_slice, Nq), min(a.ratio_base_slice, Nb)
         base, base_len = bd[:nbs], bl[:nbs].astype(np.int64)

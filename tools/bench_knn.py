@@ -1,7 +1,7 @@
 """k-nearest-neighbour search and weighted vote (multimodal/neighbors.py knn_cosine / knn_vote) at the leakage check's sizes: Nq = 2200
 evaluation frames, Nb = 10 000 and 50 000 training frames, D = 2048 features, k in {1, 20, 200}.
 
-    python tools/bench_knn.py [--nq 2200] [--nb 10000,50000] [--k 1,20,200] [--iters 3]
+    python tools/bench_knn.py [--nq 2200] [--nb 10000,50000] [--k 1,20,200] [--repeats 7] [--window-ms 200]
     python tools/bench_knn.py --kernels-only      # the run to put under `rocprofv3 --kernel-trace --stats`
 
 - ``knn_cosine`` against ``nearest_cosine`` at the same shape: the price of the lists;
@@ -11,26 +11,28 @@ evaluation frames, Nb = 10 000 and 50 000 training frames, D = 2048 features, k 
   and argmax;
 - the worst case for the lists at the test's small shape (130 x 1500 x 64, k = 64): base rows in ascending similarity, where every
   tile's candidates enter, against the same rows shuffled.
-Device events after warm-up, one process; prints one JSON line."""
+Timed by tools/timing.py: ms per call, median [min, max], the sides of a comparison alternating; prints one JSON line."""
 import argparse
 import json
 import os
 import sys
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=2200)
     ap.add_argument("--nb", default="10000,50000")
     ap.add_argument("--k", default="1,20,200")
     ap.add_argument("--dim", type=int, default=2048)
     ap.add_argument("--classes", type=int, default=1000)
-    ap.add_argument("--iters", type=int, default=3)
+    timing.add_arguments(ap)
     ap.add_argument("--kernels-only", action="store_true", help="no torch yardsticks (the profiled run)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import torch
     import torch.nn.functional as F
     from multimodal import neighbors as N
@@ -40,43 +42,38 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     Nq, D, C, T = a.nq, a.dim, a.classes, 0.07
     ks = [int(v) for v in a.k.split(",") if v]
-    res = {"nq": Nq, "dim": D, "classes": C, "iters": a.iters}
+    res = {"nq": Nq, "dim": D, "classes": C, "repeats": a.repeats, "window_ms": a.window_ms}
 
-    def timed(fn, iters):
-        fn()                                   # warm-up: loads code objects, allocates
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(iters):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) / iters
+    def measure(sides):
+        """{output key: fn} -> {key, min_key, max_key of every side}, the sides alternating"""
+        return timing.entries(timing.measure(sides, **timing.keywords(a)))
 
     q = torch.randn(Nq, D, device=dev, generator=g)
     for Nb in (int(v) for v in a.nb.split(",") if v):
         b = torch.randn(Nb, D, device=dev, generator=g)
         labels = torch.randint(0, C, (Nb,), device=dev, generator=g)
-        r = {"nearest_cosine_ms": timed(lambda: N.nearest_cosine(q, b), 10 * a.iters)}
+        r = {}
         for k in ks:
-            ms = timed(lambda: N.knn_cosine(q, b, k), 10 * a.iters)
-            rk = {"knn_cosine_ms": ms, "over_nearest_cosine": ms / r["nearest_cosine_ms"]}
             cos, idx = N.knn_cosine(q, b, k)
-            rk["knn_vote_ms"] = timed(lambda: N.knn_vote(cos, idx, labels, C, T), 10 * a.iters)
+
+            def eager_topk():
+                qn, bn = F.normalize(q, dim=-1), F.normalize(b, dim=-1)
+                out = [torch.topk(qn[s:s + 256] @ bn.T, k, dim=1) for s in range(0, Nq, 256)]
+                return torch.cat([o.values for o in out]), torch.cat([o.indices for o in out])
+
+            def eager_vote():
+                w = torch.exp(cos / T)
+                scores = (F.one_hot(labels[idx], C) * w[..., None]).sum(dim=1)
+                return scores, scores.argmax(dim=1)
+
+            sides = {"nearest_cosine_ms": lambda: N.nearest_cosine(q, b), "knn_cosine_ms": lambda: N.knn_cosine(q, b, k)}
+            votes = {"knn_vote_ms": lambda: N.knn_vote(cos, idx, labels, C, T)}
             if not a.kernels_only:
-                def eager_topk():
-                    qn, bn = F.normalize(q, dim=-1), F.normalize(b, dim=-1)
-                    out = [torch.topk(qn[s:s + 256] @ bn.T, k, dim=1) for s in range(0, Nq, 256)]
-                    return torch.cat([o.values for o in out]), torch.cat([o.indices for o in out])
-
-                def eager_vote():
-                    w = torch.exp(cos / T)
-                    scores = (F.one_hot(labels[idx], C) * w[..., None]).sum(dim=1)
-                    return scores, scores.argmax(dim=1)
-
-                rk["eager_topk_ms"] = timed(eager_topk, a.iters)
-                rk["speedup_vs_eager_topk"] = rk["eager_topk_ms"] / ms
-                rk["eager_vote_ms"] = timed(eager_vote, a.iters)
+                sides["eager_topk_ms"], votes["eager_vote_ms"] = eager_topk, eager_vote
+            rk = {**measure(sides), **measure(votes)}
+            rk["over_nearest_cosine"] = rk["knn_cosine_ms"] / rk["nearest_cosine_ms"]
+            if not a.kernels_only:
+                rk["speedup_vs_eager_topk"] = rk["eager_topk_ms"] / rk["knn_cosine_ms"]
                 rk["vote_speedup_vs_eager"] = rk["eager_vote_ms"] / rk["knn_vote_ms"]
             r[f"k{k}"] = rk
         res[f"nb{Nb}"] = r
@@ -89,9 +86,8 @@ def main():
     qs = q0[None, :] + 0.1 * torch.randn(nq, d, device=dev, generator=g)
     asc = torch.linspace(0.0, 3.0, nb, device=dev)[:, None] * q0[None, :] + torch.randn(nb, d, device=dev, generator=g)
     shuffled = asc[torch.randperm(nb, device=dev, generator=g)]
-    res["adversary_130x1500x64_k64"] = {"ascending_ms": timed(lambda: N.knn_cosine(qs, asc, k), 20 * a.iters),
-                                        "shuffled_ms": timed(lambda: N.knn_cosine(qs, shuffled, k), 20 * a.iters),
-                                        "nearest_cosine_ms": timed(lambda: N.nearest_cosine(qs, asc), 20 * a.iters)}
+    res["adversary_130x1500x64_k64"] = measure({"ascending_ms": lambda: N.knn_cosine(qs, asc, k), "shuffled_ms": lambda: N.knn_cosine(qs, shuffled, k),
+                                                "nearest_cosine_ms": lambda: N.nearest_cosine(qs, asc)})
     print(json.dumps(res))
 
 

@@ -5,11 +5,11 @@
 - trial scoring: T trials of G images each, scored either as T train-mode passes of G images (the reference's loop,
   eval_linear_decoding.py:89-91, --trial_batch 1) or as one grouped pass (ResNet.trunk(x, bn_groups=G), --trial_batch T).
 
-    python tools/bench_linear_probe.py [--trials 64] [--group 4] [--size 224] [--iters 5] [--train-batches 64,256]
-    python tools/bench_linear_probe.py --kernel-stats DIR      # after `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python <this> --iters 2`
+    python tools/bench_linear_probe.py [--trials 64] [--group 4] [--size 224] [--repeats 7] [--window-ms 200] [--train-batches 64,256]
+    python tools/bench_linear_probe.py --kernel-stats DIR      # after `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python <this> --grouped-only --repeats 1`
 
-Times with device events after warm-up; prints one JSON line.  With --kernel-stats it reads the kernel_stats.csv files under DIR
-and prints, for each grouped BatchNorm kernel, its share of the kernel time and the bytes per second it reached on the bytes
+Timed by tools/timing.py: ms per call, median [min, max]; prints one JSON line.  With --kernel-stats it reads the kernel_stats.csv
+files under DIR and prints, for each grouped BatchNorm kernel, its share of the kernel time and the bytes per second it reached on the bytes
 the algorithm needs (each tensor element read once / written once; the statistics kernel's second, centred pass is counted
 once more as a re-read)."""
 import argparse
@@ -18,6 +18,8 @@ import glob
 import json
 import os
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
@@ -46,7 +48,7 @@ def grouped_bytes(B, S):
     return out
 
 
-def kernel_report(d, B, S, passes):
+def kernel_report(d, B, S):
     rows = []
     for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
         with open(f) as fh:
@@ -55,6 +57,7 @@ def kernel_report(d, B, S, passes):
         sys.exit(f"no kernel_stats.csv under {d}")
     total = sum(float(r["TotalDurationNs"]) for r in rows)
     need = grouped_bytes(B, S)
+    passes = sum(int(r["Calls"]) for r in rows if "bn_group_relu_maxpool_kernel" in r["Name"])          # the stem's kernel: one launch per pass
     rep = {"kernel_time_total_ms": total / 1e6, "kernels": {}}
     for r in rows:
         name = r["Name"]
@@ -65,25 +68,24 @@ def kernel_report(d, B, S, passes):
         ns = float(r["TotalDurationNs"])
         e = {"calls": int(r["Calls"]), "total_ms": ns / 1e6, "share_of_kernel_time": ns / total}
         if key is not None:
-            # the profiled run does `passes` grouped passes in each precision with the same shapes
-            e["GB_per_s"] = need[key] * passes / ns
+            e["GB_per_s"] = need[key] * passes / ns                      # every pass of the profiled run has the same shapes
         rep["kernels"]["bn_group_finalize" if fin else key] = e
     print(json.dumps(rep))
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=64)
     ap.add_argument("--group", type=int, default=4)
     ap.add_argument("--size", type=int, default=224)
-    ap.add_argument("--iters", type=int, default=5)
+    timing.add_arguments(ap)
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--grouped-only", action="store_true", help="time the grouped pass only (the profiled run)")
     ap.add_argument("--train-batches", default="64,256", help="probe-training batch sizes to time ('' = none)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     T, G, S = a.trials, a.group, a.size
     if a.kernel_stats:
-        kernel_report(a.kernel_stats, T * G, S, 2 * (a.iters + 1))
+        kernel_report(a.kernel_stats, T * G, S)
         return
     import torch
     from multimodal.resnext import ResNet
@@ -106,28 +108,17 @@ def main():
     def loop():
         return [m(x[t * G:(t + 1) * G]) for t in range(T)]
 
-    def timed(fn):
-        fn()                                   # warm-up: packs weights, allocates workspaces, loads code objects
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(a.iters):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) / a.iters
-
+    # a precision switch re-packs the trunk's weights on the next pass, so the precisions are measured one after the other; within
+    # one precision the grouped pass and the per-trial loop alternate
     with torch.no_grad():
         for prec, arith in (("32", "exact"), ("32-split", "split")):
             m.trunk_arithmetic = arith
-            ms_g = timed(grouped)
-            res[f"{prec}_grouped_ms"] = ms_g
-            res[f"{prec}_grouped_trials_per_s"] = T / ms_g * 1e3
+            sides = {f"{prec}_grouped_ms": grouped} if a.grouped_only else {f"{prec}_grouped_ms": grouped, f"{prec}_per_trial_ms": loop}
+            res.update(timing.entries(timing.measure(sides, **timing.keywords(a))))
+            res[f"{prec}_grouped_trials_per_s"] = T / res[f"{prec}_grouped_ms"] * 1e3
             if not a.grouped_only:
-                ms_l = timed(loop)
-                res[f"{prec}_per_trial_ms"] = ms_l
-                res[f"{prec}_per_trial_trials_per_s"] = T / ms_l * 1e3
-                res[f"{prec}_speedup"] = ms_l / ms_g
+                res[f"{prec}_per_trial_trials_per_s"] = T / res[f"{prec}_per_trial_ms"] * 1e3
+                res[f"{prec}_speedup"] = res[f"{prec}_per_trial_ms"] / res[f"{prec}_grouped_ms"]
     if not a.grouped_only and a.train_batches:
         from multimodal import linear_probe as L
         opt = torch.optim.Adam(m.parameters(), 5e-4)
@@ -145,9 +136,9 @@ def main():
 
             for prec, arith in (("32", "exact"), ("32-split", "split")):
                 m.trunk_arithmetic = arith
-                ms = timed(step)
-                res[f"train_{prec}_B{B}_ms_per_step"] = ms
-                res[f"train_{prec}_B{B}_images_per_s"] = B / ms * 1e3
+                key = f"train_{prec}_B{B}_ms_per_step"
+                res.update(timing.entries(timing.measure({key: step}, **timing.keywords(a))))
+                res[f"train_{prec}_B{B}_images_per_s"] = B / res[key] * 1e3
     print(json.dumps(res))
 
 

@@ -2,7 +2,7 @@
 same GPU (analysis_cvcl/duplicates.py), at the leakage check's sizes: Nq = 2200 evaluation frames, Nb = 10 000 and 50 000 training
 frames, D = 2048 features, frames of 3 x 224 x 224.
 
-    python tools/bench_neighbors.py [--nq 2200] [--nb 10000,50000] [--pixel-nb 10000,50000] [--iters 3]
+    python tools/bench_neighbors.py [--nq 2200] [--nb 10000,50000] [--pixel-nb 10000,50000] [--repeats 7] [--window-ms 200]
     python tools/bench_neighbors.py --kernels-only      # the run to put under `rocprofv3 --kernel-trace --stats`
 
 - feature search: ``nearest_cosine`` over all base rows, and grouped in 22 categories (one launch sequence);
@@ -12,13 +12,15 @@ frames, D = 2048 features, frames of 3 x 224 x 224.
 - pixel search: ``nearest_pixels`` on uint8 frames; yardstick: the per-query loop over base batches of 256 normalised fp32 frames
   resident on the device, torch.sum(torch.abs(eval_img - train_images), dim=(1, 2, 3)) + min / argmin (:988-1002), timed on
   ``--pixel-slice`` queries (default 2) and scaled to Nq.
-Device events after warm-up, one process; prints one JSON line.  Also reported: the fraction of the 155 TF fp32 MFMA rate the
-feature search reaches (2 Nq Nb D flops over its whole time) and the v_sad_u8 lane-instructions per second of the pixel search
-(Nq Nb C HW / 4 over its whole time)."""
+Timed by tools/timing.py: ms per call, median [min, max], a search and its yardsticks alternating; prints one JSON line.  Also
+reported: the fraction of the 155 TF fp32 MFMA rate the feature search reaches (2 Nq Nb D flops over its whole time) and the
+v_sad_u8 lane-instructions per second of the pixel search (Nq Nb C HW / 4 over its whole time)."""
 import argparse
 import json
 import os
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
@@ -26,17 +28,17 @@ sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 MFMA_F32_PEAK = 155e12
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--nq", type=int, default=2200)
     ap.add_argument("--nb", default="10000,50000")
     ap.add_argument("--pixel-nb", default="10000,50000")
     ap.add_argument("--dim", type=int, default=2048)
     ap.add_argument("--size", type=int, default=224)
-    ap.add_argument("--iters", type=int, default=3)
+    timing.add_arguments(ap)
     ap.add_argument("--pixel-slice", type=int, default=2)
     ap.add_argument("--kernels-only", action="store_true", help="no torch yardsticks (the profiled run)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import torch
     import torch.nn.functional as F
     from multimodal import neighbors as N
@@ -45,54 +47,45 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     Nq, D, S = a.nq, a.dim, a.size
-    res = {"nq": Nq, "dim": D, "size": S, "iters": a.iters}
-
-    def timed(fn, iters=a.iters):
-        fn()                                   # warm-up: loads code objects, allocates
-        torch.cuda.synchronize()
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(iters):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) / iters
+    res = {"nq": Nq, "dim": D, "size": S, "repeats": a.repeats, "window_ms": a.window_ms}
 
     q = torch.randn(Nq, D, device=dev, generator=g)
     qg = (torch.arange(Nq, device=dev) % 22).int()
     for Nb in (int(v) for v in a.nb.split(",") if v):
         b = torch.randn(Nb, D, device=dev, generator=g)
         bg = (torch.arange(Nb, device=dev) % 22).int()
-        ms = timed(lambda: N.nearest_cosine(q, b), 20 * a.iters)             # (a few ms per call: a longer window)
-        r = {"ms": ms, "queries_per_s": Nq / ms * 1e3, "fraction_of_fp32_mfma_peak": 2.0 * Nq * Nb * D / (ms * 1e-3) / MFMA_F32_PEAK}
-        msg = timed(lambda: N.nearest_cosine(q, b, qg, bg), 20 * a.iters)
-        r["grouped22_ms"] = msg
-        r["grouped22_queries_per_s"] = Nq / msg * 1e3
+        n = min(100, Nq)
+
+        def eager_all():
+            sims = F.cosine_similarity(q[:n, None, :], b[None, :, :], dim=-1)
+            return torch.max(sims, dim=-1).values, torch.argmax(sims, dim=-1)
+
+        def eager_category():
+            tb, eb = F.normalize(b[:Nb // 22], dim=-1), F.normalize(q[:n], dim=-1)
+            sims = F.cosine_similarity(tb[:, None, :], eb[None, :, :], dim=-1)
+            return sims.max(dim=0).values, sims.argmax(dim=0)
+
+        r = {}
+        sides = {"ms": lambda: N.nearest_cosine(q, b), "grouped22_ms": lambda: N.nearest_cosine(q, b, qg, bg)}       # side = output key
         if not a.kernels_only:
-            n = min(100, Nq)
-
-            def eager_all():
-                sims = F.cosine_similarity(q[:n, None, :], b[None, :, :], dim=-1)
-                return torch.max(sims, dim=-1).values, torch.argmax(sims, dim=-1)
-
-            def eager_category():
-                tb, eb = F.normalize(b[:Nb // 22], dim=-1), F.normalize(q[:n], dim=-1)
-                sims = F.cosine_similarity(tb[:, None, :], eb[None, :, :], dim=-1)
-                return sims.max(dim=0).values, sims.argmax(dim=0)
-
             try:
-                e = timed(eager_all, 1)
-                r["eager_slice_queries"] = n
-                r["eager_slice_ms"] = e
-                r["eager_scaled_ms"] = e * Nq / n
-                r["speedup_vs_eager"] = e * Nq / n / ms
+                eager_all()
+                sides["eager_slice_ms"] = eager_all
             except torch.OutOfMemoryError:
                 r["eager_scaled_ms"] = "not measured (out of memory)"
             torch.cuda.empty_cache()
-            e = timed(eager_category, 1)
-            r["eager_per_category_ms"] = e
-            r["eager_22_categories_ms"] = e * 22
-            r["grouped22_speedup_vs_eager"] = e * 22 / msg
+            sides["eager_per_category_ms"] = eager_category
+        r.update(timing.entries(timing.measure(sides, **timing.keywords(a))))
+        ms, msg = r["ms"], r["grouped22_ms"]
+        r.update({"queries_per_s": Nq / ms * 1e3, "fraction_of_fp32_mfma_peak": 2.0 * Nq * Nb * D / (ms * 1e-3) / MFMA_F32_PEAK,
+                  "grouped22_queries_per_s": Nq / msg * 1e3})
+        if "eager_slice_ms" in r:
+            r["eager_slice_queries"] = n
+            r["eager_scaled_ms"] = r["eager_slice_ms"] * Nq / n
+            r["speedup_vs_eager"] = r["eager_scaled_ms"] / ms
+        if not a.kernels_only:
+            r["eager_22_categories_ms"] = r["eager_per_category_ms"] * 22
+            r["grouped22_speedup_vs_eager"] = r["eager_22_categories_ms"] / msg
         res[f"cosine_nb{Nb}"] = r
         del b
         torch.cuda.empty_cache()
@@ -100,11 +93,10 @@ def main():
     qf = torch.randint(0, 256, (Nq, 3, S, S), device=dev, generator=g, dtype=torch.uint8)
     for Nb in (int(v) for v in a.pixel_nb.split(",") if v):
         bf = torch.randint(0, 256, (Nb, 3, S, S), device=dev, generator=g, dtype=torch.uint8)
-        ms = timed(lambda: N.nearest_pixels(qf, bf), max(1, a.iters - 1))
-        r = {"ms": ms, "queries_per_s": Nq / ms * 1e3, "sad_lane_instructions_per_s": Nq * Nb * 3.0 * S * S / 4 / (ms * 1e-3),
-             "u8_bytes_compared_per_s": Nq * Nb * 3.0 * S * S / (ms * 1e-3)}
+        n = min(a.pixel_slice, Nq)
+        r, bn = {}, None
+        sides = {"ms": lambda: N.nearest_pixels(qf, bf)}
         if not a.kernels_only:
-            n = min(a.pixel_slice, Nq)
             try:
                 bn = torch.empty(Nb, 3, S, S, device=dev)
                 for s in range(0, Nb, 1024):
@@ -124,16 +116,20 @@ def main():
                         out.append(best_j)
                     return out
 
-                e = timed(eager, 1)
-                r["eager_slice_queries"] = n
-                r["eager_slice_ms"] = e
-                r["eager_scaled_ms"] = e * Nq / n
-                r["speedup_vs_eager"] = e * Nq / n / ms
-                del bn
+                eager()
+                sides["eager_slice_ms"] = eager
             except torch.OutOfMemoryError:
                 r["eager_scaled_ms"] = "not measured (out of memory)"
+        r.update(timing.entries(timing.measure(sides, **timing.keywords(a))))
+        ms = r["ms"]
+        r.update({"queries_per_s": Nq / ms * 1e3, "sad_lane_instructions_per_s": Nq * Nb * 3.0 * S * S / 4 / (ms * 1e-3),
+                  "u8_bytes_compared_per_s": Nq * Nb * 3.0 * S * S / (ms * 1e-3)})
+        if "eager_slice_ms" in r:
+            r["eager_slice_queries"] = n
+            r["eager_scaled_ms"] = r["eager_slice_ms"] * Nq / n
+            r["speedup_vs_eager"] = r["eager_scaled_ms"] / ms
         res[f"pixels_nb{Nb}"] = r
-        del bf
+        del bf, bn
         torch.cuda.empty_cache()
     print(json.dumps(res))
 

@@ -1,16 +1,15 @@
 """The n-gram baseline (csrc/ngram.hip, ngram.NGramModel) at the product shape: batches of B = 256 utterances of L = 25 positions,
 V = 2350, N = 3 and 5, tables counted on a seeded Zipf corpus of 2^20 tokens (the generator of tests/ngram_common.py).
 
-    python tools/bench_ngram.py [--repeats 5] [--window-ms 200] [--loop-batches 8] [--orders 3,5]
+    python tools/bench_ngram.py [--repeats 7] [--window-ms 200] [--loop-batches 8] [--orders 3,5] [--tokens 1048576]
 
 Per order: the three kernels alone (``ops.ngram_keys`` / ``ngram_ce_loss`` / ``ngram_probs``, the probabilities into a buffer
 allocated once), ``update`` per batch (launch + the 4-byte read of the bad-id count), the table rebuild from the whole corpus'
 pending keys (sort + run-length count per order; host clock, device drained at both ends), ``calculate_ce_loss`` against an eager
 torch composition on the same device tensors (the packed keys by shifts, one ``torch.searchsorted`` per table and order, float64
 logs; checked against the kernel's values), and ``calculate_ce_loss`` against the Python-loop restatement of
-tests/ngram_common.py on ``loop-batches`` batches (host clock).  Device timings: warm-up, then ``repeats`` windows of calls sized
-to ``window-ms`` between two device events, the sides of a comparison alternating; the median window per call is reported with the
-smallest and largest beside it.  Prints one JSON line."""
+tests/ngram_common.py on ``loop-batches`` batches (host clock).  Device timings by tools/timing.py: us per call, median [min, max],
+the sides of a comparison alternating.  Prints one JSON line."""
 import argparse
 import json
 import math
@@ -19,20 +18,22 @@ import statistics
 import sys
 import time
 
+import timing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-B, L, V, TOKENS = 256, 25, 2350, 1 << 20
+B, L, V = 256, 25, 2350
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--window-ms", type=float, default=200.0)
+    timing.add_arguments(ap)
     ap.add_argument("--loop-batches", type=int, default=8)
     ap.add_argument("--orders", default="3,5")
-    a = ap.parse_args()
+    ap.add_argument("--tokens", type=int, default=1 << 20, help="tokens of the corpus the tables are counted on")
+    a = ap.parse_args(argv)
     import numpy as np
     import torch
     import torch.nn.functional as F
@@ -44,27 +45,9 @@ def main():
         sys.exit("bench_ngram: no GPU")
     dev = torch.device("cuda:0")
 
-    def window(fn, calls):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(calls):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / calls               # us per call
-
-    def measure(fns):
-        calls = {}
-        for k, fn in fns.items():
-            for _ in range(3):
-                fn()
-            torch.cuda.synchronize()
-            calls[k] = max(5, min(20000, int(a.window_ms * 1e3 / max(window(fn, 5), 1.0))))
-        samples = {k: [] for k in fns}
-        for _ in range(a.repeats):
-            for k, fn in fns.items():
-                samples[k].append(window(fn, calls[k]))
-        return {k: {"us": statistics.median(v), "min_us": min(v), "max_us": max(v), "calls": calls[k]} for k, v in samples.items()}
+    def measure_us(fns):
+        """{name: fn} -> {name: {"us", "min_us", "max_us", "calls"}}"""
+        return {k: {**timing.entry(r, "us", 1e3), "calls": r["calls"]} for k, r in timing.measure(fns, **timing.keywords(a)).items()}
 
     def host_clock(fn, prepare=lambda: None):
         out = []
@@ -77,7 +60,7 @@ def main():
             out.append(time.perf_counter() - t0)
         return {"s": statistics.median(out), "min_s": min(out), "max_s": max(out)}
 
-    n_batches = math.ceil(TOKENS / (B * (L + 1) / 2))          # lengths are uniform in [1, L]
+    n_batches = math.ceil(a.tokens / (B * (L + 1) / 2))          # lengths are uniform in [1, L]
     ty, tl = NC.corpus(0, V, B * n_batches, L)
     ey, el = NC.corpus(1, V, B * a.loop_batches, L)
     train = [(torch.from_numpy(ty[i * B:(i + 1) * B]).to(dev), torch.from_numpy(tl[i * B:(i + 1) * B]).to(dev)) for i in range(n_batches)]
@@ -106,10 +89,10 @@ def main():
             scratch.update(y, y_len)
 
         probs = torch.empty(B, L - 1, V, device=dev)
-        r.update(measure({"keys_kernel": lambda: ops.ngram_keys(y, y_len, N, V),
-                          "ce_loss_kernel": lambda: ops.ngram_ce_loss(tables, N, V, la, l1a, y, y_len),
-                          "probs_kernel": lambda: ops.ngram_probs(tables, N, V, la, l1a, y, y_len, out=probs),
-                          "update": update}))
+        r.update(measure_us({"keys_kernel": lambda: ops.ngram_keys(y, y_len, N, V),
+                             "ce_loss_kernel": lambda: ops.ngram_ce_loss(tables, N, V, la, l1a, y, y_len),
+                             "probs_kernel": lambda: ops.ngram_probs(tables, N, V, la, l1a, y, y_len, out=probs),
+                             "update": update}))
         gram = [(tables[0][tables[2][n]:tables[2][n + 1]], tables[1][tables[2][n]:tables[2][n + 1]]) for n in range(N)]
         ctx = [(tables[3][tables[5][n]:tables[5][n + 1]], tables[4][tables[5][n]:tables[5][n + 1]]) for n in range(N)]
         pos = torch.arange(L, device=dev)[None]
@@ -138,7 +121,7 @@ def main():
 
         want = model.calculate_ce_loss(y, y_len)
         r["torch_vs_hip_max_ulp"] = int(NC.ulp_distance(torch_loss().cpu().numpy(), want.cpu().numpy()).max())
-        r.update(measure({"calculate_ce_loss": lambda: model.calculate_ce_loss(y, y_len), "torch_ce_loss": torch_loss}))
+        r.update(measure_us({"calculate_ce_loss": lambda: model.calculate_ce_loss(y, y_len), "torch_ce_loss": torch_loss}))
         r["torch_over_hip"] = r["torch_ce_loss"]["us"] / r["calculate_ce_loss"]["us"]
         # the Python loops on the host against the class on the same batches
         rest = NC.Model(N, V, [(k.cpu().numpy(), c.cpu().numpy()) for k, c in gram])

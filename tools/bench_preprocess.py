@@ -1,5 +1,5 @@
 """The evaluation-time transform on the device (cvcl_preprocess_frames) at 256 frames of 480 x 640 and at a mixed-size batch, in both
-modes, vs Pillow on one host core.      python tools/bench_preprocess.py [--batch 256] [--cpu-frames 32]"""
+modes, vs Pillow on one host core.      python tools/bench_preprocess.py [--batch 256] [--cpu-frames 32] [--repeats 7] [--window-ms 200]"""
 import argparse
 import os
 import sys
@@ -7,6 +7,8 @@ import time
 
 import numpy as np
 import torch
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
@@ -17,7 +19,7 @@ MIXED = [(480, 640), (640, 480), (224, 224), (240, 320), (720, 1280), (1080, 192
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--cpu-frames", type=int, default=32)
-ap.add_argument("--iters", type=int, default=50)
+timing.add_arguments(ap)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 g = torch.Generator().manual_seed(0)
@@ -51,22 +53,14 @@ for name, sizes in (("480 x 640", [(480, 640)] * a.batch), ("mixed sizes", [MIXE
     for mode in MODES:
         pre = DevicePreprocess(mode=mode)
         plan = pre.plan(frames)
-        for _ in range(3):
-            pre.run(*plan)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            pre.run(*plan)
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / a.iters
+        t = timing.measure({"run": lambda: pre.run(*plan)}, **timing.keywords(a))["run"]
+        ms = t["ms"]
         t0 = time.perf_counter()
         for _ in range(5):
             pre(frames)
         torch.cuda.synchronize()
         call_ms = (time.perf_counter() - t0) / 5 * 1e3
-        line = (f"{name:12s} {mode:26s} {ms * 1e3:8.0f} us per batch of {a.batch} ({(src_bytes + out_bytes) / ms / 1e6:6.0f} GB/s of source + "
+        line = (f"{name:12s} {mode:26s} {timing.text(t, 1e3, '.0f'):>20s} us per batch of {a.batch} ({(src_bytes + out_bytes) / ms / 1e6:6.0f} GB/s of source + "
                 f"output bytes); whole call with packing {a.batch} device frames and the table {call_ms:.2f} ms")
         if Image is not None:
             line += f"; Pillow + torch on one host core {pillow_ms_per_frame([f.numpy() for f in host[:a.cpu_frames]], mode):.2f} ms per frame"

@@ -1,9 +1,10 @@
 """The 32-split precision (fp32 storage, split-bf16 products in the ResNeXt trunk's convolutions) against the exact-fp32 and
-bf16 modes: C2 at B = 256, 224^2, on bench.py's weights and batch, all three modes timed in one process.  Prints ONE JSON line:
+bf16 modes: C2 at B = 256, 224^2, on bench.py's weights and batch, all three modes timed in one process
+(tools/timing.py: ms per step, median [min, max]).  Prints ONE JSON line:
 ms/step and pairs/s per mode, logits_rel / cosine / loss_abs of 32-split vs 32 at bench's noise batch and at the conditioned point
 (bench.structured_parity's setting), and the per-class kernel times of one 32-split step.
 
-    python tools/bench_split.py [--steps 10 --warmup 3 --batch 256]
+    python tools/bench_split.py [--batch 256 --repeats 7 --window-ms 200]
 """
 import argparse
 import json
@@ -17,6 +18,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 
 import bench                                                          # noqa: E402
+import timing                                                         # noqa: E402
 from multimodal import _hip as H                                      # noqa: E402
 
 
@@ -36,12 +38,11 @@ def conditioned(lit, ve, batch_size, dev, gamma3=0.25):
                 b.weight.copy_(g)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    args = ap.parse_args()
+    timing.add_arguments(ap)
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     lit, ve, opt = bench.build_model("c2", dev, "32")
     batch = bench.synthetic_batch_on_device(args.batch, seed=0, device=dev) + (None,)
@@ -59,17 +60,9 @@ def main():
     ve.model.enable_trunk_stream(dev, inputs="ready", n_streams=2)    # bench.py's schedule
     for p in ("32-split", "32", "bf16"):
         lit.set_precision(p)
-        for _ in range(args.warmup):
-            step()
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(args.steps):
-            step()
-        b.record()
-        torch.cuda.synchronize()
-        ms = a.elapsed_time(b) / args.steps
-        res[p] = {"ms_per_step": round(ms, 3), "pairs_per_s": round(args.batch / ms * 1e3, 1)}
+        # (a precision switch re-packs the weights on the next step, so the modes are measured one after the other)
+        t = timing.measure({p: step}, **timing.keywords(args))[p]
+        res[p] = {**timing.entry(t, "ms_per_step", digits=3), "pairs_per_s": round(args.batch / t["ms"] * 1e3, 1)}
     ve.model.enable_trunk_stream(dev, inputs=None)
 
     lit.set_precision("32-split")
@@ -80,7 +73,7 @@ def main():
     torch.cuda.synchronize()
     kern = {k: round(v[0], 3) for k, v in H.prof_collect().items() if v[1]}
     H.prof_enable(False)
-    print(json.dumps({"config": "c2", "batch": args.batch, "steps": args.steps, "warmup": args.warmup, "modes": res,
+    print(json.dumps({"config": "c2", "batch": args.batch, "repeats": args.repeats, "window_ms": args.window_ms, "modes": res,
                       "split_over_fp32_step": round(res["32-split"]["ms_per_step"] / res["32"]["ms_per_step"], 3),
                       "split_vs_fp32": parity, "split_kernel_ms_by_class": kern}))
 

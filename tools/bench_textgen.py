@@ -2,10 +2,10 @@
 flat image features of B images: the HIP decode (LanguageModel.beam_search_decode -> ops.beam_search_lstm) against an eager torch
 composition of the reference algorithm on the same GPU (a yardstick only, defined here).
 
-    python tools/bench_textgen.py [--batch 256] [--beam 3] [--decode-length 25] [--alpha 0.0] [--iters 20] [--no-eager]
+    python tools/bench_textgen.py [--batch 256] [--beam 3] [--decode-length 25] [--alpha 0.0] [--repeats 7] [--window-ms 200] [--no-eager]
 
-Times with device events after warm-up; prints one JSON line.  Kernel times come from a separate `rocprofv3 --kernel-trace --stats`
-run of this script."""
+Timed by tools/timing.py: ms per decode, median [min, max], the two decodes alternating; prints one JSON line.  Kernel times come
+from a separate `rocprofv3 --kernel-trace --stats` run of this script."""
 import argparse
 import contextlib
 import io
@@ -14,6 +14,8 @@ import os
 import sys
 
 import torch
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
@@ -66,28 +68,15 @@ def eager_decode(lm, feats, K, T, alpha, sos=2, eos=3):
     return torch.where(any_fin[:, None, None], fin_seq, alive_seq), torch.where(any_fin[:, None], fin_sc, alive_lp)
 
 
-def timed(fn, iters):
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    fn()
-    torch.cuda.synchronize()
-    s.record()
-    for _ in range(iters):
-        out = fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters, out
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--beam", type=int, default=3)
     ap.add_argument("--decode-length", type=int, default=25)
     ap.add_argument("--alpha", type=float, default=0.0)
-    ap.add_argument("--iters", type=int, default=20)
+    timing.add_arguments(ap)
     ap.add_argument("--no-eager", action="store_true")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     from multimodal.multimodal import LanguageModel, TextEncoder
     from multimodal import _hip as H
     dev = torch.device("cuda:0")
@@ -106,17 +95,22 @@ def main():
     feats = torch.nn.functional.normalize(torch.randn(a.batch, 512, device=dev), dim=1)
     B, K, T = a.batch, a.beam, a.decode_length
     with torch.no_grad():
-        hip_ms, (seq, lp) = timed(lambda: lm.beam_search_decode(B, K, T, a.alpha, image_features=feats), a.iters)
+        sides = {"hip_ms_per_decode": lambda: lm.beam_search_decode(B, K, T, a.alpha, image_features=feats)}
+        if not a.no_eager:
+            sides["eager_ms_per_decode"] = lambda: eager_decode(lm, feats, K, T, a.alpha)
+        t = timing.entries(timing.measure(sides, **timing.keywords(a)), digits=3)
+        hip_ms = t["hip_ms_per_decode"]
+        seq, lp = lm.beam_search_decode(B, K, T, a.alpha, image_features=feats)
         H.prof_enable(True)
         lm.beam_search_decode(B, K, T, a.alpha, image_features=feats)
         torch.cuda.synchronize()
         launches = sum(n for _ms, n in H.prof_collect().values())
         H.prof_enable(False)
         rec = {"metric": "textgen_decode", "batch": B, "beam": K, "decode_length": T, "alpha": a.alpha, "steps": int(seq.shape[2]) - 1,
-               "hip_ms_per_decode": round(hip_ms, 3), "captions_per_s": round(B / hip_ms * 1e3, 1), "hip_launches_per_decode": launches}
+               **t, "captions_per_s": round(B / hip_ms * 1e3, 1), "hip_launches_per_decode": launches}
         if not a.no_eager:
-            eager_ms, (es, elp) = timed(lambda: eager_decode(lm, feats, K, T, a.alpha), max(2, a.iters // 4))
-            rec.update({"eager_ms_per_decode": round(eager_ms, 3), "speedup": round(eager_ms / hip_ms, 2),
+            es, elp = eager_decode(lm, feats, K, T, a.alpha)
+            rec.update({"speedup": round(t["eager_ms_per_decode"] / hip_ms, 2),
                         "top_beam_agreement": float((es[:, 0] == seq[:, 0]).all(1).float().mean()) if es.shape == seq.shape else None})
     print(json.dumps(rec))
 

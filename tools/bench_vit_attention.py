@@ -3,17 +3,19 @@
   (the reference's lines, vision_transformer_dino_mugs.py:232-269, on torch's ROCm ops with the same weights; under
   torch.autocast(bfloat16) for the bf16 rows), and cvcl_attention_probs alone (q_rows = T and 1): ms and GB/s of the bytes it must
   write.  The parent of this entry cannot run these calls at all, so the eager composition is the only baseline.
-Warm-up, then ``--repeats`` device-event timings of ``--iters`` calls each; reported as median [min, max].  Prints one JSON line.
+Timed by tools/timing.py: ms per call, median [min, max], the HIP call and its eager composition alternating.  Prints one JSON line.
 
-    python tools/bench_vit_attention.py [--batch 256] [--iters 3] [--repeats 5] [--patches 16,14] [--dtypes bf16,f32] [--kernel-only]"""
+    python tools/bench_vit_attention.py [--batch 256] [--repeats 7] [--window-ms 200] [--model 12x768x12x224] [--patches 16,14] [--dtypes bf16,f32] [--kernel-only]"""
 import argparse
 import json
 import os
-import statistics
 import sys
+from functools import partial
 
 import torch
 import torch.nn.functional as F
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
@@ -23,18 +25,9 @@ from multimodal import vit_maps                                       # noqa: E4
 from multimodal.attention_maps import vit_cls_attention               # noqa: E402
 
 
-def timed(fn, iters, repeats):
-    out = []
-    for _ in range(repeats):
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return {"ms": round(statistics.median(out), 3), "min": round(min(out), 3), "max": round(max(out), 3)}
+def timed(fns, args):
+    """fns: {name: callable}, the sides alternating -> {name: {ms (median), min_ms, max_ms}}."""
+    return {k: timing.entry(r, digits=3) for k, r in timing.measure(fns, **timing.keywords(args)).items()}
 
 
 def eager(model, x, want, n=4):
@@ -58,25 +51,29 @@ def eager(model, x, want, n=4):
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--model", type=str, default="12x768x12x224", help="depth x width x heads x image size (default: ViT-B at 224)")
+    timing.add_arguments(ap)
     ap.add_argument("--patches", type=str, default="16,14")
     ap.add_argument("--dtypes", type=str, default="bf16,f32")
     ap.add_argument("--kernel-only", action="store_true", help="time cvcl_attention_probs alone (the run to put under rocprofv3)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     B = args.batch
-    res = {"batch": B, "iters": args.iters, "repeats": args.repeats, "cases": []}
+    depth, width, heads, S = (int(v) for v in args.model.split("x"))
+    hd, scale = width // heads, (width // heads) ** -0.5
+    n_last = min(4, depth)
+    res = {"batch": B, "model": args.model, "repeats": args.repeats, "window_ms": args.window_ms, "cases": []}
     for patch in (int(p) for p in args.patches.split(",")):
         torch.manual_seed(0)
-        model = vits.vit_base(patch_size=patch, num_classes=0).to(dev).eval()
+        model = vits.VisionTransformer(img_size=[S], patch_size=patch, embed_dim=width, depth=depth, num_heads=heads, mlp_ratio=4, qkv_bias=True,
+                                       norm_layer=partial(torch.nn.LayerNorm, eps=1e-6), num_classes=0).to(dev).eval()
         for p in model.parameters():
             p.requires_grad_(False)
-        x = torch.randn(B, 3, 224, 224, device=dev)
-        T, heads = (224 // patch) ** 2 + 1, model.num_heads
+        x = torch.randn(B, 3, S, S, device=dev)
+        T = (S // patch) ** 2 + 1
         for name in args.dtypes.split(","):
             dt = torch.bfloat16 if name == "bf16" else torch.float32
             model.compute_dtype = dt
@@ -84,26 +81,21 @@ def main():
             cast = torch.autocast("cuda", dtype=torch.bfloat16, enabled=dt == torch.bfloat16)
             calls = {"get_last_selfattention": (lambda: model.get_last_selfattention(x), "attn"),
                      "vit_cls_attention": (lambda: vit_cls_attention(model, x), "cls"),
-                     "get_intermediate_layers_4": (lambda: model.get_intermediate_layers(x, 4), "layers")}
+                     f"get_intermediate_layers_{n_last}": (lambda: model.get_intermediate_layers(x, n_last), "layers")}
             for key, (fn, want) in ({} if args.kernel_only else calls).items():
                 def ref(want=want):
                     with torch.no_grad(), cast:
-                        return eager(model, x, want)
-                fn(), ref()                                            # warm-up: packing, allocator, library handles
-                torch.cuda.empty_cache()
-                case[key] = {"hip": timed(fn, args.iters, args.repeats), "eager_torch": timed(ref, args.iters, args.repeats)}
+                        return eager(model, x, want, n_last)
+                case[key] = timed({"hip": fn, "eager_torch": ref}, args)
                 case[key]["speedup"] = round(case[key]["eager_torch"]["ms"] / case[key]["hip"]["ms"], 2)
             # the kernel alone on one qkv matrix of the model's shape
             qkv = torch.randn(B * T, 3 * model.embed_dim, device=dev).to(dt)
-            for q_rows in (T, 1):
-                def k(q_rows=q_rows):
-                    vit_maps.attention_probs(qkv, B, T, heads, 64, 0.125, q_rows)
-                k()
-                t = timed(k, max(args.iters, 10), args.repeats)
-                nbytes = B * heads * q_rows * T * 4
-                t["write_bytes"] = nbytes
-                t["write_gbs"] = round(nbytes / (t["ms"] * 1e-3) / 1e9, 1)
-                case[f"kernel_q_rows_{'T' if q_rows == T else 1}"] = t
+            kernels = timed({"kernel_q_rows_T": lambda: vit_maps.attention_probs(qkv, B, T, heads, hd, scale, T),
+                             "kernel_q_rows_1": lambda: vit_maps.attention_probs(qkv, B, T, heads, hd, scale, 1)}, args)
+            for (key, t), q_rows in zip(kernels.items(), (T, 1)):
+                t["write_bytes"] = B * heads * q_rows * T * 4
+                t["write_gbs"] = round(t["write_bytes"] / (t["ms"] * 1e-3) / 1e9, 1)
+                case[key] = t
             del qkv
             torch.cuda.empty_cache()
             res["cases"].append(case)

@@ -9,19 +9,20 @@
   topk(k, largest=False), index 0 put back, zeros scattered).  Both work in place, so every call is preceded by a copy that
   restores the slab and the copy alone is timed as a third side; the kernel's GB/s counts one read of the slab per digit pass (4),
   the final read and the k zeros written per matrix, over the time without the copy.
-The sides of a comparison alternate window by window: warm-up, then ``--repeats`` device-event windows of ``--iters`` calls for each
-side in turn; reported as median [min, max].  Prints one JSON line.
+Timed by tools/timing.py: ms per call, median [min, max], the sides of a comparison alternating.  Prints one JSON line.
 
-    python tools/bench_vit_rollout.py [--batch 256] [--iters 3] [--repeats 5] [--patches 16,14] [--dtypes bf16,f32] [--discard_ratio 0.9]
+    python tools/bench_vit_rollout.py [--batch 256] [--repeats 7] [--window-ms 200] [--model 12x768x12x224] [--patches 16,14] [--dtypes bf16,f32] [--discard_ratio 0.9]
                                        [--kernel-only]"""
 import argparse
 import json
 import os
-import statistics
 import sys
+from functools import partial
 
 import torch
 import torch.nn.functional as F
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
@@ -31,24 +32,9 @@ from multimodal import vit_maps                                       # noqa: E4
 from multimodal.attention_maps import vit_attention_rollout, vit_attention_rollout_discard, vit_cls_attention   # noqa: E402
 
 
-def _window(fn, iters):
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
-def timed(fns, iters, repeats):
-    """fns: {name: callable}.  One window per side in turn, ``repeats`` rounds -> {name: {ms (median), min, max}}."""
-    out = {k: [] for k in fns}
-    for _ in range(repeats):
-        for k, fn in fns.items():
-            out[k].append(_window(fn, iters))
-    return {k: {"ms": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)} for k, v in out.items()}
+def timed(fns, args):
+    """fns: {name: callable}, the sides alternating -> {name: {ms (median), min_ms, max_ms}}."""
+    return {k: timing.entry(r, digits=3) for k, r in timing.measure(fns, **timing.keywords(args)).items()}
 
 
 def eager_rollout(model, x):
@@ -85,27 +71,30 @@ def eager_discard(slab, k):
     return slab
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--model", type=str, default="12x768x12x224", help="depth x width x heads x image size (default: ViT-B at 224)")
+    timing.add_arguments(ap)
     ap.add_argument("--patches", type=str, default="16,14")
     ap.add_argument("--dtypes", type=str, default="bf16,f32")
     ap.add_argument("--discard_ratio", type=float, default=0.9, help="the ratio of the discard rows; 0: leave them out")
     ap.add_argument("--kernel-only", action="store_true", help="time the kernels alone (the run to put under rocprofv3)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     ratio = vit_maps.check_discard_ratio(args.discard_ratio)
     dev = torch.device("cuda:0")
     B = args.batch
-    res = {"batch": B, "iters": args.iters, "repeats": args.repeats, "discard_ratio": ratio, "cases": []}
+    depth, width, heads, S = (int(v) for v in args.model.split("x"))
+    hd, scale = width // heads, (width // heads) ** -0.5
+    res = {"batch": B, "model": args.model, "repeats": args.repeats, "window_ms": args.window_ms, "discard_ratio": ratio, "cases": []}
     for patch in (int(p) for p in args.patches.split(",")):
         torch.manual_seed(0)
-        model = vits.vit_base(patch_size=patch, num_classes=0).to(dev).eval()
+        model = vits.VisionTransformer(img_size=[S], patch_size=patch, embed_dim=width, depth=depth, num_heads=heads, mlp_ratio=4, qkv_bias=True,
+                                       norm_layer=partial(torch.nn.LayerNorm, eps=1e-6), num_classes=0).to(dev).eval()
         for p in model.parameters():
             p.requires_grad_(False)
-        x = torch.randn(B, 3, 224, 224, device=dev)
-        T, heads, depth = (224 // patch) ** 2 + 1, model.num_heads, len(model.blocks)
+        x = torch.randn(B, 3, S, S, device=dev)
+        T = (S // patch) ** 2 + 1
         for name in args.dtypes.split(","):
             dt = torch.bfloat16 if name == "bf16" else torch.float32
             model.compute_dtype = dt
@@ -119,10 +108,7 @@ def main():
                          "vit_cls_attention": lambda: vit_cls_attention(model, x)}
                 if ratio:
                     sides["vit_attention_rollout_discard"] = lambda: vit_attention_rollout_discard(model, x, ratio)
-                for fn in sides.values():                              # warm-up: packing, allocator, library handles
-                    fn()
-                torch.cuda.empty_cache()
-                case.update(timed(sides, args.iters, args.repeats))
+                case.update(timed(sides, args))
                 case["speedup_vs_eager"] = round(case["eager_torch"]["ms"] / case["vit_attention_rollout"]["ms"], 2)
                 case["rollout_over_cls_floor_ms"] = round(case["vit_attention_rollout"]["ms"] - case["vit_cls_attention"]["ms"], 3)
                 if ratio:
@@ -131,11 +117,9 @@ def main():
             # the kernels alone: one block's qkv, then a depth-layer slab of row-stochastic matrices
             qkv = torch.randn(B * T, 3 * model.embed_dim, device=dev).to(dt)
             fused = torch.empty(B, T, T, dtype=torch.float32, device=dev)
-            sides = {"head_fuse": lambda: vit_maps.attention_head_fuse(qkv, B, T, heads, 64, 0.125, "mean", out=fused),
-                     "attention_probs_q_rows_T": lambda: vit_maps.attention_probs(qkv, B, T, heads, 64, 0.125, T)}
-            for fn in sides.values():
-                fn()
-            t = timed(sides, max(args.iters, 10), args.repeats)
+            sides = {"head_fuse": lambda: vit_maps.attention_head_fuse(qkv, B, T, heads, hd, scale, "mean", out=fused),
+                     "attention_probs_q_rows_T": lambda: vit_maps.attention_probs(qkv, B, T, heads, hd, scale, T)}
+            t = timed(sides, args)
             for key, nbytes in (("head_fuse", qkv.numel() * qkv.element_size() * 2 // 3 + B * T * T * 4),
                                 ("attention_probs_q_rows_T", qkv.numel() * qkv.element_size() * 2 // 3 + B * heads * T * T * 4)):
                 t[key]["bytes"] = nbytes
@@ -146,9 +130,7 @@ def main():
             slab = torch.randn(depth, B, T, T, device=dev).softmax(-1)
             sides = {"rollout_q_rows_1": lambda: vit_maps.rollout_chain(slab, 0, 1),
                      "rollout_q_rows_T": lambda: vit_maps.rollout_chain(slab, 0, T)}
-            for fn in sides.values():
-                fn()
-            t = timed(sides, max(args.iters, 10), args.repeats)
+            t = timed(sides, args)
             for key in sides:
                 t[key]["slab_bytes"] = slab.numel() * 4
                 t[key]["slab_gbs"] = round(slab.numel() * 4 / (t[key]["ms"] * 1e-3) / 1e9, 1)
@@ -159,9 +141,7 @@ def main():
                 sides = {"copy": lambda: work.copy_(slab),
                          "copy_discard": lambda: vit_maps.attention_discard(work.copy_(slab), k),
                          "copy_eager_discard": lambda: eager_discard(work.copy_(slab), k)}
-                for fn in sides.values():
-                    fn()
-                t = timed(sides, args.iters, args.repeats)
+                t = timed(sides, args)
                 nbytes = slab.numel() * 4 * 5 + depth * B * k * 4
                 for key in ("copy_discard", "copy_eager_discard"):
                     t[key]["ms_without_copy"] = round(t[key]["ms"] - t["copy"]["ms"], 3)

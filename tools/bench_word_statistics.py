@@ -5,18 +5,18 @@ reference-style per-token Python loop, at the product shape: B = 256 utterances 
     python tools/bench_word_statistics.py [--repeats 7] [--window-ms 200] [--loop-batches 8]
 
 Yardsticks: ``index_add_`` of the rows / the float64 losses / ones into the tables for the accumulate (not order-preserving: it
-uses atomics), ``softmax(-1)`` + ``topk`` + ``gather`` for the top-k.  Per side: warm-up, then ``repeats`` windows of calls sized to
-``window-ms`` between two device events; the median window per call is reported, the spread beside it, the two sides in
-alternation.  GB/s over the bytes each kernel has to move (accumulate: n_valid rows of H floats and their losses read, the touched
+uses atomics), ``softmax(-1)`` + ``topk`` + ``gather`` for the top-k.  Timed by tools/timing.py: us per call, median [min, max],
+the two sides in alternation.  GB/s over the bytes each kernel has to move (accumulate: n_valid rows of H floats and their losses read, the touched
 table rows read and written; top-k: R V floats read, R (2 k + 1) values written).  The per-token loop -- one ``.item()`` and one
 SumData ``+=`` per token, as analysis_tools/processing.py:326-331 of the reference -- is timed on ``loop-batches`` batches with the
 host clock, next to the CSR build + accumulate launch of this repository on the same batches.  Prints one JSON line."""
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
@@ -24,12 +24,11 @@ sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 B, L, HD, V, K, TOP_K = 256, 25, 512, 2350, 3000, 5
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--window-ms", type=float, default=200.0)
+    timing.add_arguments(ap)
     ap.add_argument("--loop-batches", type=int, default=8)
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     import numpy as np
     import torch
     from analysis_tools import processing as P
@@ -38,27 +37,9 @@ def main():
         sys.exit("bench_word_statistics: no GPU")
     dev = torch.device("cuda:0")
 
-    def window(fn, calls):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(calls):
-            fn()
-        t1.record()
-        t1.synchronize()
-        return t0.elapsed_time(t1) * 1e3 / calls               # us per call
-
-    def measure(fns):
-        calls = {}
-        for k, fn in fns.items():
-            for _ in range(3):
-                fn()
-            torch.cuda.synchronize()
-            calls[k] = max(5, min(20000, int(a.window_ms * 1e3 / max(window(fn, 5), 1.0))))
-        samples = {k: [] for k in fns}
-        for _ in range(a.repeats):
-            for k, fn in fns.items():
-                samples[k].append(window(fn, calls[k]))
-        return {k: {"us": statistics.median(v), "min_us": min(v), "max_us": max(v), "calls": calls[k]} for k, v in samples.items()}
+    def measure_us(fns):
+        """{name: fn} -> {name: {"us", "min_us", "max_us", "calls"}}"""
+        return {k: {**timing.entry(r, "us", 1e3), "calls": r["calls"]} for k, r in timing.measure(fns, **timing.keywords(a)).items()}
 
     rng = np.random.default_rng(0)
     zipf = 1.0 / np.arange(1, K)
@@ -95,8 +76,8 @@ def main():
 
     res = {"shape": {"B": B, "L": L, "H": HD, "V": V, "K": K, "segments": S, "n_valid": n_valid,
                      "largest_segment": int((seg_ptr[1:] - seg_ptr[:-1]).max())}}
-    res.update(measure({"hip_accumulate": lambda: ops.token_items_accumulate(outputs, loss, seg_ptr, rows, slot, vector, loss_sum, cnt),
-                        "torch_accumulate": torch_accumulate}))
+    res.update(measure_us({"hip_accumulate": lambda: ops.token_items_accumulate(outputs, loss, seg_ptr, rows, slot, vector, loss_sum, cnt),
+                           "torch_accumulate": torch_accumulate}))
     moved = n_valid * (HD * 4 + 4 + 4) + S * (2 * HD * 4 + 2 * 8 + 2 * 8 + 4) + (S + 1) * 4
     res["accumulate_GBps"] = moved / (res["hip_accumulate"]["us"] * 1e-6) / 1e9
     res["torch_accumulate_GBps"] = moved / (res["torch_accumulate"]["us"] * 1e-6) / 1e9
@@ -109,7 +90,7 @@ def main():
         t = p.topk(TOP_K, -1)
         return t, p.gather(1, labels[:, None])
 
-    res.update(measure({"hip_topk": lambda: ops.token_topk(logits, labels, TOP_K), "torch_topk": torch_topk}))
+    res.update(measure_us({"hip_topk": lambda: ops.token_topk(logits, labels, TOP_K), "torch_topk": torch_topk}))
     moved = N * V * 4 + N * 8 + N * (TOP_K * 12 + 4)
     res["topk_GBps"] = moved / (res["hip_topk"]["us"] * 1e-6) / 1e9
     res["torch_topk_GBps"] = moved / (res["torch_topk"]["us"] * 1e-6) / 1e9

@@ -1,6 +1,7 @@
 """cvcl_bn_bwd (reduce + finalize + apply) on the trunk's shapes at B = 256, stand-alone: time and bytes per second.
 bytes: mode 1 reads x, dy twice and writes dx (5 tensor passes); mode 2 reads x, out, dy twice and writes dx, g (8 passes)."""
 import os, sys, torch
+import timing
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 from multimodal import _hip as H
@@ -17,12 +18,8 @@ for rows, C, mode in ((802816, 128, 1), (802816, 256, 2), (200704, 256, 1), (200
         H.check(lib.cvcl_bn_bwd(H.BF16, mode, H.ptr(x), H.ptr(out), H.ptr(dy), H.ptr(scale), H.ptr(shift), H.ptr(mean), H.ptr(rstd), H.ptr(gamma),
                                 H.ptr(scratch[prow * 2 + 3]), H.ptr(scratch[prow * 2 + 4]), H.ptr(dx), H.ptr(g), rows, C, H.ptr(scratch[:prow * 2]), prow,
                                 H.ptr(scratch[prow * 2:prow * 2 + 3]), H.stream_ptr()), "bn_bwd")
-    for _ in range(3): run()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10): run()
-    e1.record(); torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 100
+    t = timing.measure({"run": run})["run"]
+    us = t["ms"] * 1e3
     passes = 5 if mode == 1 else 8
     mb = rows * C * 2 / 1e6
-    print(f"[{rows:7d},{C:5d}] mode {mode}: {us:7.1f} us  {passes} x {mb:6.1f} MB -> {passes * mb / us / 1e3:5.2f} TB/s")
+    print(f"[{rows:7d},{C:5d}] mode {mode}: {timing.text(t, 1e3):>24s} us  {passes} x {mb:6.1f} MB -> {passes * mb / us / 1e3:5.2f} TB/s")

@@ -1,5 +1,6 @@
 """Timing of the grouped-conv kernel on the trunk's shapes; CVCL_HIP_LIB selects the library."""
 import os, sys, torch
+import timing
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "multimodal-baby_amd"))
 from multimodal import _hip as H
 dev = torch.device("cuda:0")
@@ -17,12 +18,6 @@ def run(B, S, C, stride):
     st = torch.empty(rows, 2, C, device=dev)
     def call():
         H.check(H.lib().cvcl_gconv3x3(H.BF16, H.ptr(x), H.ptr(sc), H.ptr(sh), H.ptr(wp), H.ptr(y), H.ptr(st), rows, None, B, S, S, C, 32, stride, H.stream_ptr()), "gconv")
-    for _ in range(3): call()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10): call()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / 10 * 1000
-print("lib%s  layer1(56,128,s1): %.0f us   layer2.0(56,256,s2): %.0f us   layer2(28,256,s1): %.0f us   layer3(14,512): %.0f us" % (
+    return timing.text(timing.measure({"call": call})["call"], 1e3, ".0f")
+print("lib%s  layer1(56,128,s1): %s us   layer2.0(56,256,s2): %s us   layer2(28,256,s1): %s us   layer3(14,512): %s us" % (
     os.path.basename(os.environ.get("CVCL_HIP_LIB", "")), run(256, 56, 128, 1), run(256, 56, 256, 2), run(256, 28, 256, 1), run(256, 14, 512, 1)))

@@ -1,5 +1,6 @@
 """cvcl_gconv3x3_wgrad on the trunk's shapes at B = 256 (bf16): time per call."""
 import os, sys, torch
+import timing
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 from multimodal import _hip as H
@@ -12,10 +13,6 @@ for C, S, stride in ((128, 56, 1), (256, 56, 2), (256, 28, 1), (512, 28, 2), (51
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
     def run():
         H.check(lib.cvcl_gconv3x3_wgrad(H.ptr(x), H.ptr(dy), H.ptr(dw), B, S, S, C, 32, stride, H.ptr(ws), nb, H.stream_ptr()), "wgrad")
-    for _ in range(3): run()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10): run()
-    e1.record(); torch.cuda.synchronize()
+    t = timing.measure({"run": run})["run"]
     mb = (x.numel() + dy.numel()) * 2 / 1e6
-    print(f"C {C:5d} {S:3d}x{S:<3d} stride {stride}: {e0.elapsed_time(e1) * 100:7.1f} us  (x + dy = {mb:6.1f} MB, one pass at 5.5 TB/s = {mb / 5.5:5.1f} us)")
+    print(f"C {C:5d} {S:3d}x{S:<3d} stride {stride}: {timing.text(t, 1e3):>24s} us  (x + dy = {mb:6.1f} MB, one pass at 5.5 TB/s = {mb / 5.5:5.1f} us)")

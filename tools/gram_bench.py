@@ -2,17 +2,10 @@
 it replaces, on the trunk's shapes at B = 256 (layer-1 / layer-2 conv3, layer1.0 downsample)."""
 import ctypes as C, os, sys
 import torch
+import timing
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "multimodal-baby_amd"))
 from multimodal import _hip as H
 dev = torch.device("cuda:0")
-def timeit(f, n=20):
-    for _ in range(3): f()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n): f()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) / n * 1e3
 big = torch.empty(1 << 28, dtype=torch.float32, device=dev)          # 1 GiB: evicts the caches between variants
 for name, M, K, N in (("layer1 conv3", 802816, 128, 256), ("layer2 conv3", 200704, 256, 512), ("layer1.0 downsample", 802816, 64, 256)):
     a = (torch.randn(M, K, device=dev) * 1.5 + 0.3).bfloat16()
@@ -48,6 +41,9 @@ for name, M, K, N in (("layer1 conv3", 802816, 128, 256), ("layer2 conv3", 20070
             big.zero_()
             f()
         return g
-    z = timeit(cold(lambda: None))
-    print(f"{name:22s} M={M} K={K} N={N}: Gram route {timeit(gram):7.1f} us (gram + reduce alone {timeit(gram_only):7.1f}) | statistics pass + finalize "
-          f"{timeit(stats_pass):7.1f} us | behind a 1 GiB memset: Gram {timeit(cold(gram)) - z:7.1f}, pass {timeit(cold(stats_pass)) - z:7.1f}")
+    t = timing.measure({"gram": gram, "gram_only": gram_only, "pass": stats_pass, "memset": cold(lambda: None), "cold_gram": cold(gram),
+                        "cold_pass": cold(stats_pass)})                                           # the variants alternate
+    z = t["memset"]["ms"]
+    print(f"{name:22s} M={M} K={K} N={N}: Gram route {timing.text(t['gram'], 1e3)} us (gram + reduce alone {timing.text(t['gram_only'], 1e3)}) | "
+          f"statistics pass + finalize {timing.text(t['pass'], 1e3)} us | behind a 1 GiB memset: Gram {(t['cold_gram']['ms'] - z) * 1e3:7.1f}, "
+          f"pass {(t['cold_pass']['ms'] - z) * 1e3:7.1f}")

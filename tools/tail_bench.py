@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "multimodal-baby_amd"))
 import torch  # noqa: E402
 
 import bench  # noqa: E402
+import timing  # noqa: E402
 from multimodal import _hip as H  # noqa: E402
 
 cfg = sys.argv[1] if len(sys.argv) > 1 else "c2"
@@ -34,14 +35,7 @@ def step():
 with bench.frozen_trunk_cached(ve, cfg, batch[0]):
     for _ in range(5):
         step()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        step()
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / steps
+    ms = timing.window(step, steps)
     H.prof_enable(True)
     for _ in range(steps):
         step()
