@@ -404,6 +404,11 @@ constexpr int STEMP_TP = 2;
 constexpr int STEMP_CR = 2 * STEMP_TP + 1;             // convolution rows per item
 constexpr int STEMP_ROWS = 2 * STEMP_CR + 5;           // input rows per channel
 constexpr int STEMP_BW = 128;                          // band row width in pixels (column 0 = the left padding column)
+// bytes of the band [STEMP_CR][STEMP_BW][64] bf16 plus ONE pixel of slack.  A convolution tile stores its pixel ox at band column
+// ox + 1, and at 114 <= Wo <= 126 (W = 228 .. 252) the row has 8 tiles: lane 15 of the last one (a padding pixel, it stores zeros)
+// lands on column STEMP_BW = column 0 of the next band row (a padding column: zero anyway) and, in the last band row, on the 128
+// bytes behind the band.  Without the slack those were -centre[0..31], which every later tile starts its accumulators from.
+constexpr int STEMP_BAND_BYTES = (STEMP_CR * STEMP_BW + 1) * 128;
 __global__ __launch_bounds__(512, 1) void stem_pool_mfma_kernel(const float* __restrict__ x, const bf16_t* __restrict__ wp,
                                                                 bf16_t* __restrict__ y, const float* __restrict__ scale,
                                                                 const float* __restrict__ shift, const float* __restrict__ centre,
@@ -411,7 +416,7 @@ __global__ __launch_bounds__(512, 1) void stem_pool_mfma_kernel(const float* __r
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned int* patch = (unsigned int*)smem;                 // [3 * STEMP_ROWS][STEM_PITCH] dwords (2 bf16 each)
     char* band = smem + 3 * STEMP_ROWS * STEM_PITCH * 4;       // [STEMP_CR][STEMP_BW][64] bf16
-    float* cen = reinterpret_cast<float*>(band + STEMP_CR * STEMP_BW * 128);      // [64] -centre | [64] scale | [64] shift
+    float* cen = reinterpret_cast<float*>(band + STEMP_BAND_BYTES);               // [64] -centre | [64] scale | [64] shift
     const int Ho = Hin / 2, Wo = Win / 2;
     const int Hp = (Ho - 1) / 2 + 1, Wp = (Wo - 1) / 2 + 1;
     const int bands = cvcl_div_up(Hp, STEMP_TP);
@@ -1479,7 +1484,7 @@ extern "C" int cvcl_stem_pool(int dtype, const float* x_nchw, const void* w_pack
     CVCL_CHECK_ARG(x_nchw && w_packed && scale && shift && y_nhwc && B > 0, "cvcl_stem_pool: bad args");
     CVCL_CHECK_ARG(cvcl_stem_pool_supported(dtype, H, W), "cvcl_stem_pool: bf16 and a width <= %d only (got dtype %d, %d x %d)",
                    2 * (STEMP_BW - 2), dtype, H, W);
-    const size_t lds = (size_t)3 * STEMP_ROWS * STEM_PITCH * 4 + (size_t)STEMP_CR * STEMP_BW * 128 + 3 * 64 * 4;
+    const size_t lds = (size_t)3 * STEMP_ROWS * STEM_PITCH * 4 + (size_t)STEMP_BAND_BYTES + 3 * 64 * 4;
     static CvclLdsAttr attr;
     if (const int rc = cvcl_raise_lds_limit(attr, (const void*)stem_pool_mfma_kernel, (int)lds, "cvcl_stem_pool")) return rc;
     attr.mark();
@@ -1661,7 +1666,7 @@ extern "C" int cvcl_bn_add_relu(int dtype, const void* raw, const float* scale, 
                                 const float* idn_scale, const float* idn_shift, void* out, long rows, int C, void* stream) {
     CVCL_CHECK_DTYPE_TRUNK(dtype, "cvcl_bn_add_relu");
     dtype = cvcl_storage_dtype(dtype);
-    CVCL_CHECK_ARG(raw && scale && shift && idn && out && rows > 0 && C % 8 == 0, "cvcl_bn_add_relu: bad args");
+    CVCL_CHECK_ARG(raw && scale && shift && idn && out && rows > 0, "cvcl_bn_add_relu: bad args");
     CvclProfScope prof(stream, CVCL_K_BN_ADD_RELU);
     CVCL_CHECK_ARG((idn_scale == nullptr) == (idn_shift == nullptr), "cvcl_bn_add_relu: idn_scale/idn_shift pair");
     const int epc = dtype == CVCL_F32 ? 4 : 8;
