@@ -18,8 +18,19 @@ data module.
 
 ``--eval_dataset saycam --data_dir DIR [--frame_store PATH] --eval_metadata_filename F`` scores the trials of ``DIR/F`` (a dataset
 directory in the reference's layout, multimodal/multimodal_saycam_data_module.py; ``$CVCL_DATA_DIR`` stands in for ``--data_dir``).
-``--eval_dataset object_categories``, and ``saycam`` without a dataset directory or under ``--clip_eval``, are not available here;
-``synthetic`` uses the synthetic trials of the data module (same item layout)."""
+``saycam`` without a dataset directory or under ``--clip_eval`` is not available here; ``synthetic`` uses the synthetic trials of the
+data module (same item layout).
+
+``--eval_dataset object_categories --data_dir DIR [--object_categories_dir DIR2] [--seed S]`` is the reference's out-of-distribution
+evaluation (eval.py:149-160): 4-way trials over the category folders ``DIR/object_categories/<category>/*.jpg``
+(multimodal/object_categories_data_module.py; ``DIR/eval_object_categories.json`` is used if present and generated from ``--seed``
+otherwise), with a checkpoint or under ``--clip_eval``; without the directory the run exits.  It has one set of trials: ``--stage`` is
+recorded and selects nothing.  Its trials share their frames (5 trials per image, 3 foil images each from the same folders) and
+their ~64 one-word labels, so they are not encoded per trial: every distinct frame is encoded once, ``4 * --trial_batch`` frames per
+pass, every category word once, and all trials are scored from an index table in one launch (multimodal/trials.py,
+``cvcl_trial_scores``) with one copy to the host.  Spatial embeddings with ``sim == "max"`` and runs that write attention maps have
+no table form and go through the per-trial path above over the same trials, as does any run under ``--no_trial_table``
+(``--no_trial_table --trial_batch 1`` is the reference's loop)."""
 import argparse
 import glob
 import json
@@ -34,6 +45,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "mul
 from multimodal.multimodal_data_module import (EOS_TOKEN_ID, SOS_TOKEN_ID, SyntheticDataModule, data_dir_from,   # noqa: E402
                                                load_data)
 from multimodal.multimodal_saycam_data_module import MultiModalSAYCamDataModule   # noqa: E402
+from multimodal.object_categories_data_module import OBJECT_CATEGORIES_DIRNAME, ObjectCategoriesDataModule   # noqa: E402
 from multimodal.multimodal_lit import MultiModalLitModel                          # noqa: E402
 from train import _setup_parser                                                   # noqa: E402
 
@@ -190,6 +202,14 @@ def check_clip_args(args):
         raise SystemExit(f"--clip_eval runs in --precision 32 or bf16, not {args.precision}")
 
 
+def object_categories_dir(args):
+    """--object_categories_dir, else object_categories/ under the dataset root, else None"""
+    if args.object_categories_dir:
+        return args.object_categories_dir
+    root = data_dir_from(args)
+    return os.path.join(root, OBJECT_CATEGORIES_DIRNAME) if root else None
+
+
 def main(args):
     if not 0 <= args.rollout_discard_ratio < 1:            # (false for nan)
         raise SystemExit(f"--rollout_discard_ratio {args.rollout_discard_ratio}: a share R of the attentions with 0 <= R < 1")
@@ -198,11 +218,15 @@ def main(args):
     if args.clip_eval:
         check_clip_args(args)
     saycam = args.eval_dataset == "saycam" and not args.clip_eval and bool(data_dir_from(args))
-    if args.eval_dataset != "synthetic" and not saycam:
+    objcat = args.eval_dataset == "object_categories" and os.path.isdir(object_categories_dir(args) or "")
+    if args.eval_dataset != "synthetic" and not saycam and not objcat:
         raise SystemExit(f"--eval_dataset {args.eval_dataset} reads the reference's private evaluation frames from hard-coded "
                          "cluster paths and is not available here; use --eval_dataset synthetic"
                          + (", or give --eval_dataset saycam a dataset directory in the reference's layout with --data_dir DIR (or "
-                            "$CVCL_DATA_DIR; not under --clip_eval)" if args.eval_dataset == "saycam" else ""))
+                            "$CVCL_DATA_DIR; not under --clip_eval)" if args.eval_dataset == "saycam" else "")
+                         + (", or give --eval_dataset object_categories the category folders: DIR/object_categories/<category>/*.jpg "
+                            "with --data_dir DIR (or $CVCL_DATA_DIR), or --object_categories_dir DIR"
+                            if args.eval_dataset == "object_categories" else ""))
     device = torch.device("cuda:0")
     data_args = _setup_parser().parse_args("")
     if args.clip_eval:                                     # eval.py:29-47
@@ -230,7 +254,11 @@ def main(args):
     data_args.eval_type = args.eval_type
     data_args.eval_metadata_filename = args.eval_metadata_filename
     data_args.n_eval_trials = args.n_trials
-    if saycam:
+    if objcat:
+        # where the data is and what seeds a generated metadata file are this run's, not the checkpoint's training run's
+        data_args.data_dir, data_args.object_categories_dir, data_args.seed = data_dir_from(args), args.object_categories_dir, args.seed
+        data = ObjectCategoriesDataModule(data_args)
+    elif saycam:
         # where the data is and how its frames travel are this run's, not the checkpoint's training run's
         data_args.data_dir, data_args.frame_store = data_dir_from(args), args.frame_store
         data_args.device_frames = bool(getattr(data_args, "device_frames", False)) and not args.frame_store
@@ -239,16 +267,25 @@ def main(args):
         data = SyntheticDataModule(data_args)
     data.prepare_data()
     data.setup()
-    loaders = {"dev": data.val_dataloader, "test": data.test_dataloader}[args.stage]()
-    dataloader = loaders[1]                                # the second dataloader holds the evaluation trials
-    if saycam:                                             # eval.py:134-148 (the classes are the metadata's targets: no directory listing)
+    if objcat:                                             # eval.py:149-160: one set of trials, whatever --stage
+        dataloader = data.test_dataloader()
+    else:
+        loaders = {"dev": data.val_dataloader, "test": data.test_dataloader}[args.stage]()
+        dataloader = loaders[1]                            # the second dataloader holds the evaluation trials
+    if objcat:
+        vocab = data.vocab
+        eval_data = data.data
+    elif saycam:                                           # eval.py:134-148 (the classes are the metadata's targets: no directory listing)
         vocab = data.read_vocab()
         eval_data = load_data(os.path.join(data.data_dir, data_args.eval_metadata_filename))
     else:
         vocab = None
         eval_data = data.eval_sets["val" if args.stage == "dev" else "test"].metadata()
     classes = sorted({t["target_category"] for t in eval_data})
-    kitty = bool(saycam and args.use_kitty_label)          # eval.py:162-165, 181-194: "cat" trials are scored with the word "kitty"
+    if objcat:                                             # eval.py:159: the module's category list (and whatever else the metadata scores)
+        classes = list(data.object_categories) + [c for c in classes if c not in data.object_categories]
+    # eval.py:162-165, 181-194: "cat" trials are scored with the word "kitty"
+    kitty = bool((saycam or (objcat and not args.clip_eval)) and args.use_kitty_label)
     if kitty and "cat" in classes:
         classes.remove("cat")
         classes.append("kitty")
@@ -267,6 +304,23 @@ def main(args):
     if args.plot_attention:
         os.makedirs(args.attention_maps or "results", exist_ok=True)
 
+    def record(i, class_label, logits_list, pred):
+        """trial i's record and its count; -> the class it was counted under"""
+        if kitty and class_label == "cat":
+            class_label = "kitty"
+        correct = pred == 0                                # the target is always at index 0
+        correct_pred[class_label] += int(correct)
+        total_pred[class_label] += 1
+        trial = eval_data[i]
+        results.append({
+            "checkpoint": checkpoint_name, "model": cfg["model"], "seed": cfg["seed"],
+            "shuffle_utterances": cfg["shuffle_utterances"], "augment_frames": cfg["augment_frames"],
+            "multiple_frames": cfg["multiple_frames"], "cnn": cfg["cnn"], "eval_type": args.eval_type,
+            "eval_dataset": args.eval_dataset, "stage": args.stage, "trial_idx": i,
+            "categories": [trial["target_category"]] + trial["foil_categories"],
+            "logits": logits_list, "pred": pred, "correct": bool(correct)})
+        return class_label
+
     def flush():
         nonlocal first
         res = evaluate_trials(model, pending, args.eval_type, device, data, attention_maps=want_maps, rollout=args.attention_rollout,
@@ -276,20 +330,7 @@ def main(args):
             cams.append(maps.cpu())
         for k, (logits_list, pred) in enumerate(res):
             i = first + k
-            class_label = pending[k][3][0][0]
-            if kitty and class_label == "cat":
-                class_label = "kitty"
-            correct = pred == 0                            # the target is always at index 0
-            correct_pred[class_label] += int(correct)
-            total_pred[class_label] += 1
-            trial = eval_data[i]
-            results.append({
-                "checkpoint": checkpoint_name, "model": cfg["model"], "seed": cfg["seed"],
-                "shuffle_utterances": cfg["shuffle_utterances"], "augment_frames": cfg["augment_frames"],
-                "multiple_frames": cfg["multiple_frames"], "cnn": cfg["cnn"], "eval_type": args.eval_type,
-                "eval_dataset": args.eval_dataset, "stage": args.stage, "trial_idx": i,
-                "categories": [trial["target_category"]] + trial["foil_categories"],
-                "logits": logits_list, "pred": pred, "correct": bool(correct)})
+            class_label = record(i, pending[k][3][0][0], logits_list, pred)
             if args.plot_attention:                        # the target (index 0): its frame and its map w.r.t. the label
                 frames = pending[k][0].squeeze(0).to(device)
                 if frames.dtype in (torch.uint8, torch.int64):
@@ -298,6 +339,19 @@ def main(args):
                 plot_attention(os.path.join(args.attention_maps or "results", name), frames[0], maps[k, 0])
         first += len(pending)
         pending.clear()
+
+    # object categories: frames and words encoded once, all trials scored from an index table in one launch (multimodal/trials.py)
+    # -- unless the model has no table form (sim == "max"), maps are asked for (they come from the per-trial encoder pass), or the
+    # run says --no_trial_table
+    use_table = False
+    if objcat and not args.no_trial_table and not want_maps:
+        from multimodal import trials as trial_table
+        use_table = trial_table.table_route(model) is None
+    if use_table:
+        res = trial_table.evaluate_trial_table(model, data, args.eval_type, kitty, frame_batch=4 * max(args.trial_batch, 1))
+        for i, (logits_list, pred) in enumerate(res):
+            record(i, eval_data[i]["target_category"], logits_list, pred)
+        dataloader = ()
 
     for batch in dataloader:
         if kitty and batch[3][0][0] == "cat":
@@ -317,6 +371,8 @@ def main(args):
         flush()
 
     for classname, correct_count in correct_pred.items():
+        if objcat and not total_pred[classname]:           # a category folder that an existing metadata file leaves out
+            continue
         print(f"Accuracy for class {classname:8s} is: {float(correct_count) / total_pred[classname]:.1%}")
     print(f"Total accuracy: {sum(correct_pred.values()) / sum(total_pred.values()):%}")
 
@@ -339,7 +395,8 @@ def _parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--checkpoint", type=str, help="path to checkpoint to use for evaluation")
     parser.add_argument("--clip_eval", action="store_true", help="Use CLIP model for evaluation")
-    parser.add_argument("--stage", type=str, default="test", choices=["dev", "test"], help="which evaluation stage to use")
+    parser.add_argument("--stage", type=str, default="test", choices=["dev", "test"],
+                        help="which evaluation stage to use (object_categories has one set of trials: recorded, selects nothing)")
     parser.add_argument("--eval_include_sos_eos", action="store_true", help="include SOS/EOS tokens for eval labels")
     parser.add_argument("--eval_type", type=str, default="image", choices=["image", "text"],
                         help="Run evaluation using multiple images or multiple labels")
@@ -351,7 +408,18 @@ def _parser():
     parser.add_argument("--save_predictions", action="store_true", help="save model predictions to JSON")
     # additions of this implementation
     parser.add_argument("--data_dir", type=str, default=None, metavar="DIR",
-                        help="--eval_dataset saycam: the dataset root in the reference's layout (default: $CVCL_DATA_DIR)")
+                        help="--eval_dataset saycam / object_categories: the dataset root in the reference's layout (default: "
+                             "$CVCL_DATA_DIR)")
+    parser.add_argument("--object_categories_dir", type=str, default=None, metavar="DIR",
+                        help="--eval_dataset object_categories: the folder of <category>/*.jpg folders (default: "
+                             "object_categories/ under --data_dir; without --data_dir the metadata file sits beside DIR)")
+    parser.add_argument("--seed", type=int, default=0,
+                        help="--eval_dataset object_categories: seeds the draws of a GENERATED eval_object_categories.json (an "
+                             "existing file is used as it is)")
+    parser.add_argument("--no_trial_table", action="store_true",
+                        help="--eval_dataset object_categories: encode every trial's 4 frames and its label(s) per trial, "
+                             "--trial_batch trials a pass, instead of every distinct frame and word once and one scoring launch "
+                             "(with --trial_batch 1: the reference's loop)")
     parser.add_argument("--frame_store", type=str, default=None, metavar="PATH",
                         help="--eval_dataset saycam: a store written by tools/pack_frames.py (it must hold the frames of the trials); "
                              "the trials travel as frame indices")
@@ -359,7 +427,9 @@ def _parser():
                         help="--clip_eval: OpenAI CLIP weights (TorchScript archive, e.g. ViT-L-14.pt, or a state_dict file); not shipped")
     parser.add_argument("--clip_bpe", type=str, default=None, metavar="PATH",
                         help="--clip_eval: CLIP's BPE merges file bpe_simple_vocab_16e6.txt(.gz); not shipped")
-    parser.add_argument("--trial_batch", type=int, default=64, help="trials encoded per device pass (1 = the reference's loop)")
+    parser.add_argument("--trial_batch", type=int, default=64,
+                        help="trials encoded per device pass (1 = the reference's loop); object_categories from its trial table: "
+                             "4 * T distinct frames per encoder pass")
     parser.add_argument("--hip_graph", action="store_true", help="capture the eval-mode image encoder into a HIP graph per batch "
                                                                   "shape and replay it (removes the host's launch lead; same results)")
     parser.add_argument("--precision", type=str, default="32", choices=["32", "bf16", "32-split"],

@@ -1050,6 +1050,30 @@ int cvcl_ngram_probs(const int64_t* gram_key, const int64_t* gram_cnt, const int
                      const int64_t* ctx_tot, const int64_t* ctx_off, int64_t n_ctx, int N, int vocab_size, double log_alpha,
                      double log_1m_alpha, const int64_t* y, const int64_t* y_len, int B, int L, float* probs, int* bad, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Trial scores (csrc/trials.hip, ABI v7 additive): the scoring of the reference's forced-choice evaluation loop, eval.py:196-232 --
+ * per trial `logits = model(img, label, label_len)`, `torch.softmax(logits, dim=-1)`, `torch.argmax(logits)` -- for ALL trials of an
+ * evaluation at once, from features that were computed once per distinct frame and once per distinct word (multimodal/trials.py).
+ *
+ * cvcl_trial_scores: query [Nq, D] and cand [Nc, D] f32 rows, read in place through their leading dimensions ldq, ldc >= D (elements;
+ *   no alignment beyond float).  q_idx [T] and c_idx [T, n] int32 (device) name the rows of trial t: its query row and its n
+ *   candidate rows, 1 <= n <= CVCL_TRIAL_MAX_CHOICES.  log_scale: a device scalar (the model's logit_neg_log_temperature, CLIP's
+ *   logit_scale) or NULL (= scale 1).
+ *     logits[t][j] = expf(*log_scale) * <query[q_idx[t]], cand[c_idx[t][j]]>      [T, n] f32; the pointer may be NULL (not written)
+ *     probs[t]     = softmax(logits[t]) in fp32, the maximum subtracted             [T, n] f32
+ *     pred[t]      = the LOWEST j that attains the maximum logit                    [T] int32
+ *   One kernel whatever T, a wave64 per trial, the query row's slice in registers, one reduction per candidate in an order that
+ *   depends on D alone: a trial's bits do not depend on T, on its place in the table or on the grid.  No atomics, no workspace.
+ *   Everything is validated before anything is enqueued (CVCL_EINVAL, cvcl_last_error names the argument): null query / cand /
+ *   q_idx / c_idx / probs / pred, n outside 1 .. CVCL_TRIAL_MAX_CHOICES, D < 1, ldq or ldc < D, Nq or Nc < 1, T < 0.  T = 0
+ *   enqueues nothing and succeeds.  The indices are device data and cannot be validated on the host: a trial with an index outside
+ *   [0, Nq) / [0, Nc) reads no row at all and gets NaN logits, NaN probs and pred = -1; its neighbours are not affected.
+ *   CVCL_K_HEAD. */
+#define CVCL_TRIAL_MAX_CHOICES 16
+int cvcl_trial_scores(const float* query, long ldq, int Nq, const float* cand, long ldc, int Nc, int D, const int32_t* q_idx,
+                      const int32_t* c_idx, int T, int n, const float* log_scale, float* logits, float* probs, int32_t* pred,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,8 +3,8 @@
 Mirrors the constants, ``read_vocab`` / ``load_data``, ``multiModalDataset_collate_fn``, the two evaluation datasets, setup, the
 data loaders and the CLI flags of the reference (multimodal/multimodal_data_module.py:26-69, 98-214, 283-427).  The SAYCam
 module on top of it is multimodal_saycam_data_module.py: it reads a dataset directory in the reference's layout, given by
-``--data_dir`` / ``$CVCL_DATA_DIR`` (the reference's data is private, its format is not).  The COCO and object-categories
-modules are not built; ``SyntheticDataModule`` produces batches of the same shape without any files.
+``--data_dir`` / ``$CVCL_DATA_DIR`` (the reference's data is private, its format is not).  The object-categories module is
+object_categories_data_module.py; the COCO module is not built; ``SyntheticDataModule`` produces batches of the same shape without any files.
 
 A frame reaches the model by one of three paths (``FrameSource``): decoded and transformed in the loader workers (default),
 decoded in the workers and transformed on the device (``--device_frames``), or never decoded at run time at all -- the
