@@ -1074,6 +1074,47 @@ int cvcl_trial_scores(const float* query, long ldq, int Nq, const float* cand, l
                       const int32_t* c_idx, int T, int n, const float* log_scale, float* logits, float* probs, int32_t* pred,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Caption scores (csrc/textgen_scores.hip, ABI v7 additive): the n-gram arithmetic of the pycocoevalcap scorers that the reference's
+ * multimodal/textgen_eval.py calls with default arguments -- BLEU-1..4 (option "closest"), ROUGE-L (beta 1.2) and CIDEr (n = 4,
+ * sigma = 6) -- on sentences of integer ids; DESIGN.md "Caption scores" states the definitions.  All three entries validate
+ * everything before they enqueue anything (CVCL_EINVAL, cvcl_last_error names the argument), enqueue ONE kernel on the caller's
+ * stream, one workgroup per example, and use no atomics: two calls on the same inputs give the same bits.  Floating-point work is
+ * in double.  CVCL_K_OTHER.
+ *
+ * Corpus: hyp [N, Lh] int64 ids in [0, vocab_size) with hyp_len [N] int64: the hypothesis of each of the N >= 1 examples.
+ *   ref [R, Lr] int64 with ref_len [R]: every reference, example i owning the rows ref_off[i] .. ref_off[i + 1].  Lengths are
+ *   clamped to [0, row width] as the n-gram entries clamp theirs; a length of 0 is an empty sentence.  ref_off is a HOST array of
+ *   N + 1 int64 (it starts at 0, ends at R, and gives every example 1 .. CVCL_CAPTION_MAX_REFS rows); ref_off_dev is the caller's
+ *   copy of the same values on the device, which the kernels read through clamps (a copy that differs gives wrong scores, never an
+ *   access outside ref).  Limits: 1 <= Lh, Lr <= CVCL_CAPTION_MAX_LEN tokens per sentence, CVCL_CAPTION_ORDERS * bits <= 63 with
+ *   bits = max(1, bit_length(vocab_size - 1)) (vocab_size <= 32768), N * Lh and R * Lr < 2^31.  Ids are read through the bit
+ *   mask, as the n-gram entries read theirs.
+ * cvcl_caption_bleu_rouge: stats [N, 10] int64 = testlen, the closest reflen (the reference length minimising (|l - testlen|, l)),
+ *   guess[1..4] = max(0, testlen - n + 1), correct[1..4] = sum over the hypothesis' distinct n-grams of min(its count, the largest
+ *   count in one reference); rouge [N] f64 = (1 + b^2) p r / (r + b^2 p), p = max_r LCS / len(hyp), r = max_r LCS / len(ref_r), each
+ *   maximum on its own, 0 when either is 0 (an empty sentence contributes 0).  bad [1] int on the device receives the number of ids
+ *   outside [0, vocab_size) inside the lengths of hyp and ref (the caller decides what a non-zero count means).
+ * cvcl_caption_ref_keys: keys [CVCL_CAPTION_ORDERS, R, Lr] int64: keys[n - 1, r, q] = the packed n-gram ref[r, q .. q + n) (big-endian,
+ *   `bits` per token, as "N-gram baseline" packs) where it fits the reference's length AND no earlier position of the same example's
+ *   references holds it; CVCL_CAPTION_SENTINEL elsewhere.  Sorting slice n - 1 and run-length counting it gives order n's document
+ *   frequencies: the number of examples whose references hold the n-gram.
+ * cvcl_caption_cider: df_key / df_cnt [n_df] int64 on the device hold those tables, order n in [df_off[n - 1], df_off[n]) (keys
+ *   ascending and distinct; df_off a HOST array of CVCL_CAPTION_ORDERS + 1 int64 from 0 to n_df).  cider [N] f64 = 10 * mean_n(sum_r
+ *   sim_n(hyp, ref_r)) / n_refs with the vectors tf(g) * (log(N) - log(max(1, df(g)))) (df by binary search, 0 when absent), sim_n =
+ *   sum_{g in hyp} min(h[g], r[g]) r[g] / (|h|_n |r|_n) (the division only when both norms are non-zero) times
+ *   exp(-(len_h - len_r)^2 / (2 sigma^2)), a sentence's "length" being its number of bigram occurrences.  N = 1 gives 0. */
+enum { CVCL_CAPTION_MAX_LEN = 128, CVCL_CAPTION_MAX_REFS = 32, CVCL_CAPTION_ORDERS = 4 };
+#define CVCL_CAPTION_SENTINEL (-1)
+int cvcl_caption_bleu_rouge(const int64_t* hyp, const int64_t* hyp_len, int N, int Lh, const int64_t* ref, const int64_t* ref_len, int R,
+                            int Lr, const int64_t* ref_off, const int64_t* ref_off_dev, int vocab_size, int64_t* stats, double* rouge,
+                            int* bad, void* stream);
+int cvcl_caption_ref_keys(const int64_t* ref, const int64_t* ref_len, int N, int R, int Lr, const int64_t* ref_off,
+                          const int64_t* ref_off_dev, int vocab_size, int64_t* keys, void* stream);
+int cvcl_caption_cider(const int64_t* hyp, const int64_t* hyp_len, int N, int Lh, const int64_t* ref, const int64_t* ref_len, int R, int Lr,
+                       const int64_t* ref_off, const int64_t* ref_off_dev, int vocab_size, const int64_t* df_key, const int64_t* df_cnt,
+                       const int64_t* df_off, int64_t n_df, double* cider, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -343,6 +343,23 @@ __device__ inline ACC ordered_sum(int n, F load) {
     return acc;
 }
 
+// ---- packed n-gram keys (csrc/ngram.hip, csrc/textgen_scores.hip): token ids big-endian at cvcl_key_bits(vocab_size) bits each in a
+// non-negative int64, looked up in sorted tables of distinct keys
+__host__ __device__ inline int cvcl_key_bits(int vocab_size) {   // max(1, bit_length(vocab_size - 1))
+    int bits = 1;
+    while (bits < 31 && ((int64_t)1 << bits) < (int64_t)vocab_size) ++bits;
+    return bits;
+}
+// first index in [lo, hi) whose key is >= key (hi if none); -> that index if it holds key, else -1
+__device__ inline int64_t cvcl_find_key(const int64_t* __restrict__ keys, int64_t lo, int64_t hi, int64_t key) {
+    const int64_t end = hi;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return (lo < end && keys[lo] == key) ? lo : -1;
+}
+
 // ---- GELU (erf form) with Abramowitz-Stegun 7.1.26 for erf (|error| < 1.5e-7, far below bf16 resolution) on v_rcp_f32 / v_exp_f32;
 // shared by the GEMM epilogues and the standalone passes so that fused and unfused paths round identically
 __device__ inline float gelu_erf_fast(float v) {

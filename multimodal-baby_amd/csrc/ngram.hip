@@ -25,22 +25,6 @@ struct NgramTables {
     double log_alpha, log_1m_alpha;
 };
 
-__host__ __device__ inline int ngram_bits(int vocab_size) {   // max(1, bit_length(vocab_size - 1))
-    int bits = 1;
-    while (bits < 31 && ((int64_t)1 << bits) < (int64_t)vocab_size) ++bits;
-    return bits;
-}
-
-// first index in [lo, hi) whose key is >= key (hi if none); -> that index if it holds key, else -1
-__device__ inline int64_t ngram_find(const int64_t* __restrict__ keys, int64_t lo, int64_t hi, int64_t key) {
-    const int64_t end = hi;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return (lo < end && keys[lo] == key) ? lo : -1;
-}
-
 // ngram.py:58-69, the back-off chain of position i of the utterance `history` for the candidate word w: from the longest order
 // the position allows down to the unigram, log(alpha) per order left behind; the sum in double, in the reference's order of
 // additions.  Tokens are read through the bit mask, so no id can reach the sign bit.
@@ -53,9 +37,9 @@ __device__ inline double ngram_logprob(const NgramTables& t, const int64_t* __re
     double lp = 0.0;
     for (int n = top; n >= 0; --n) {
         const int64_t ctx = n ? (ctx_full & (((int64_t)1 << (n * t.bits)) - 1)) : 0;     // the last n tokens
-        const int64_t c = ngram_find(t.ctx_key, t.ctx_off[n], t.ctx_off[n + 1], ctx);
+        const int64_t c = cvcl_find_key(t.ctx_key, t.ctx_off[n], t.ctx_off[n + 1], ctx);
         if (c >= 0) {
-            const int64_t g = ngram_find(t.gram_key, t.gram_off[n], t.gram_off[n + 1], (ctx << t.bits) | w);
+            const int64_t g = cvcl_find_key(t.gram_key, t.gram_off[n], t.gram_off[n + 1], (ctx << t.bits) | w);
             if (n == 0) {
                 const int64_t seen = g >= 0 ? t.gram_cnt[g] : 0;
                 return lp + (log((double)(seen + 1)) - log((double)(t.ctx_tot[c] + t.vocab_size)));
@@ -146,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void ngram_probs_kernel(NgramTables t, co
 int check_model(const char* entry, int N, int vocab_size, int B, int L, int* bits) {
     CVCL_CHECK_ARG(N >= 1 && N <= CVCL_NGRAM_MAX_N, "%s: N %d outside 1..%d", entry, N, CVCL_NGRAM_MAX_N);
     CVCL_CHECK_ARG(vocab_size >= 1, "%s: vocab_size %d < 1", entry, vocab_size);
-    *bits = ngram_bits(vocab_size);
+    *bits = cvcl_key_bits(vocab_size);
     CVCL_CHECK_ARG(N * *bits <= 63, "%s: N %d x %d bits per token (vocab_size %d) > 63 key bits", entry, N, *bits, vocab_size);
     CVCL_CHECK_ARG(B >= 0, "%s: B %d < 0", entry, B);
     CVCL_CHECK_ARG(L >= 1, "%s: L %d < 1", entry, L);

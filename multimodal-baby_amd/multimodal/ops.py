@@ -6,6 +6,7 @@ path is a libcvcl_hip kernel.  Functions raise if handed CPU tensors (no fallbac
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -550,3 +551,58 @@ def ngram_probs(tables, N, vocab_size, log_alpha, log_1m_alpha, y, y_len, out=No
     if tuple(probs.shape) != (B, L - 1, vocab_size):
         raise ValueError("ngram_probs: out must be [B, L - 1, vocab_size]")
     return _ngram_score("cvcl_ngram_probs", tables, N, vocab_size, log_alpha, log_1m_alpha, y, y_len, probs)
+
+
+def bleu_from_totals(totals):
+    """The eight closing lines of pycocoevalcap's BleuScorer.compute_score (option "closest") on the corpus sums of
+    cvcl_caption_bleu_rouge's ten statistics, in float64 on the host -> [BLEU_1, .., BLEU_4]."""
+    testlen, reflen, guess, correct = totals[0], totals[1], totals[2:6], totals[6:10]
+    tiny, small = 1e-15, 1e-9
+    ratio = (testlen + tiny) / (reflen + small)
+    out, b = [], 1.0
+    for k in range(4):
+        b *= (correct[k] + tiny) / (guess[k] + small)
+        score = b ** (1.0 / (k + 1))
+        out.append(score * math.exp(1 - 1 / ratio) if ratio < 1 else score)
+    return out
+
+
+def caption_scores(hyp, hyp_len, ref, ref_len, ref_off, vocab_size):
+    """BLEU-1..4, ROUGE-L and CIDEr of N hypotheses against their references (include/cvcl_hip.h "Caption scores") ->
+    (scores, arrays).  ``hyp`` [N, Lh], ``hyp_len`` [N], ``ref`` [R, Lr], ``ref_len`` [R] and ``ref_off`` [N + 1] are contiguous
+    int64 device tensors of ids in [0, vocab_size): example i owns the references ref_off[i] .. ref_off[i + 1].
+    ``scores``: {"BLEU_1", .., "BLEU_4", "ROUGE_L", "CIDEr": float}, the corpus numbers.  ``arrays``: "stats" [N, 10] int64,
+    "rouge" and "cider" [N] f64 per example, and "df": per order n = 1..4 the sorted packed n-grams of the references and the number
+    of examples that hold each.  Sorting and run-length counting the keys, the two means and BLEU's closing lines are plumbing."""
+    N, Lh = hyp.shape
+    R, Lr = ref.shape
+    if hyp_len.numel() != N or ref_len.numel() != R or ref_off.numel() != N + 1:
+        raise ValueError("caption_scores: one length per sentence and N + 1 reference offsets")
+    i64, f64, dev = torch.int64, torch.float64, hyp.device
+    corpus = (H.ptr(ref, i64), H.ptr(ref_len, i64), R, Lr)          # (refuses CPU tensors before anything is allocated beside them)
+    hyps = (H.ptr(hyp, i64), H.ptr(hyp_len, i64), N, Lh)
+    offsets = ((C.c_int64 * (N + 1))(*ref_off.tolist()), H.ptr(ref_off, i64), int(vocab_size))
+    lib, stream = H.lib(), H.stream_ptr()
+    stats = torch.empty(N, 10, dtype=i64, device=dev)
+    rouge, cider = torch.empty(N, dtype=f64, device=dev), torch.empty(N, dtype=f64, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    H.check(lib.cvcl_caption_bleu_rouge(*hyps, *corpus, *offsets, H.ptr(stats), H.ptr(rouge), H.ptr(bad), stream), "cvcl_caption_bleu_rouge")
+    keys = torch.empty(H.CAPTION_ORDERS, R, Lr, dtype=i64, device=dev)
+    H.check(lib.cvcl_caption_ref_keys(*corpus[:2], N, R, Lr, *offsets, H.ptr(keys), stream), "cvcl_caption_ref_keys")
+    if int(bad):
+        raise ValueError(f"caption_scores: {int(bad)} token ids outside [0, {vocab_size})")
+    df = []
+    for n in range(H.CAPTION_ORDERS):
+        k, cnt = torch.unique_consecutive(torch.sort(keys[n].reshape(-1)).values, return_counts=True)
+        first = int(k[0] == H.CAPTION_SENTINEL)                     # the sentinel is negative: it sorts in front of every key
+        df.append((k[first:], cnt[first:]))
+    df_off = [0]
+    for k, _ in df:
+        df_off.append(df_off[-1] + k.numel())
+    df_key, df_cnt = torch.cat([k for k, _ in df]), torch.cat([c for _, c in df])
+    H.check(lib.cvcl_caption_cider(*hyps, *corpus, *offsets, H.ptr(df_key, i64), H.ptr(df_cnt, i64),
+                                   (C.c_int64 * (H.CAPTION_ORDERS + 1))(*df_off), df_off[-1], H.ptr(cider), stream), "cvcl_caption_cider")
+    scores = dict(zip(("BLEU_1", "BLEU_2", "BLEU_3", "BLEU_4"), bleu_from_totals(stats.sum(0).tolist())))
+    scores["ROUGE_L"] = float(rouge.sum()) / N
+    scores["CIDEr"] = float(cider.sum()) / N
+    return scores, {"stats": stats, "rouge": rouge, "cider": cider, "df": df}
