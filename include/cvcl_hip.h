@@ -500,13 +500,24 @@ int cvcl_lstm_cell_bwd(const float* gates_act, const float* c_save, const int64_
  * Backward side of the ResNeXt trunk for --finetune_cnn (multimodal/multimodal.py:175-179: the CNN's parameters keep
  * requires_grad, so autograd runs through torchvision's Bottlenecks).  Used by the autograd-composed fine-tuning
  * path; [rows, C] = NHWC activations flattened over pixels.                                              */
+/* The elementwise entries below work on 16-byte channel chunks: 8 bf16 or 4 fp32 elements.  Wherever an entry takes a channel
+ * count C or a flat element count n (cvcl_bn_apply, cvcl_bn_bwd, cvcl_add, cvcl_relu_mask, cvcl_maxpool3x3s2_idx,
+ * cvcl_zero_stuff2), it must be a multiple of that chunk; anything else is refused with CVCL_EINVAL and nothing is launched.
+ * (cvcl_avgpool_bwd, cvcl_transpose and cvcl_conv_wgrad_direct work per element and take any positive size.)                  */
+/* y = x * scale + shift (ReLU if relu).  A thread keeps one channel chunk, so the chunks per row cc = C / chunk must be a power
+ * of two, a divisor of 256 or a multiple of 256 (cc = 3 is refused, cc = 768 is served by a grid rounded to a multiple of 3). */
 int cvcl_bn_apply(int dtype, const void* x, const float* scale, const float* shift, void* y, long rows, int C, int relu,
                   void* stream);
 /* train-mode BatchNorm backward, g = dy * mask:
  *   mode 0: no mask | mode 1: [x*scale+shift > 0] (ReLU right after the BN; recomputed, y is not read) |
  *   mode 2: [out > 0], out = relu(bn(x) + identity) the Bottleneck output; g_out (optional) receives g = d identity.
  *   dbeta = sum g;  dgamma = sum g * xhat;  dx = gamma * rstd * (g - dbeta/n - xhat * dgamma/n)
- * partial: scratch [partial_rows >= cvcl_bn_bwd_partial_rows(dtype, rows, C)][2][C] f32;  coef: scratch [3][C] f32 */
+ * partial: scratch [partial_rows >= cvcl_bn_bwd_partial_rows(dtype, rows, C)][2][C] f32, of which exactly that many rows are
+ *   written;  coef: scratch [3][C] f32, left holding k1 = gamma*rstd, k2 = -k1*rstd*dgamma/n, k3 = -k1*dbeta/n - k2*mean
+ *   (dx = k1*g + k2*x + k3).
+ * C / chunk must be a power of two (C = 8, 16, 32, .. in bf16; 4, 8, 16, .. in fp32).  scale, shift, mean, rstd and coef are
+ * read as 16-byte vectors and must be 16-byte aligned.  mode 1 needs scale and shift, mode 2 needs out; a mode outside 0..2, a
+ * missing operand, a misaligned vector or partial_rows below the count above is refused with CVCL_EINVAL, nothing launched.  */
 int cvcl_bn_bwd_partial_rows(int dtype, long rows, int C);
 int cvcl_bn_bwd(int dtype, int mode, const void* x, const void* out, const void* dy, const float* scale, const float* shift,
                 const float* mean, const float* rstd, const float* gamma, float* dgamma, float* dbeta, void* dx, void* g_out,
@@ -522,10 +533,9 @@ int cvcl_gconv_weight_dgrad(const float* w, float* out, int C, int cin_per_group
 int cvcl_transpose(int dtype, const void* in, void* out, long rows, int cols, void* stream);     /* out[c][r] = in[r][c] */
 int cvcl_add(int dtype, const void* a, const void* b, void* y, long n, int relu, void* stream);  /* y = a + b (ReLU if relu) */
 int cvcl_relu_mask(int dtype, const void* y, const void* dy, void* dx, long n, void* stream);    /* dx = dy where y > 0 */
-/* max pool 3x3/2 pad 1, NHWC: dy == NULL -> forward (out = pooled); else backward (out = dx, first arg-max wins) */
-int cvcl_maxpool3x3s2(int dtype, const void* x, const void* dy, void* out, int B, int H, int W, int C, void* stream);
-/* same pooling with the arg-max recorded (idx [B,Ho,Wo,C] u8, window position 0..8, first maximum): dy == NULL ->
- * forward (reads x, writes out = pooled and idx); else backward from idx (x unused, out = dx)               */
+/* max pool 3x3/2 pad 1, NHWC, with the arg-max recorded (idx [B,Ho,Wo,C] u8: window position ky*3 + kx in 0..8, the first
+ * maximum in row-major window order, as torch): dy == NULL -> forward (reads x, writes out = pooled and idx); else backward
+ * from idx (x unused, out = dx [B,H,W,C]: the sum of dy over the windows whose arg-max the pixel is)          */
 int cvcl_maxpool3x3s2_idx(int dtype, const void* x, const void* dy, void* out, uint8_t* idx, int B, int H, int W, int C,
                           void* stream);
 int cvcl_avgpool_bwd(int dtype, const float* d_pooled, void* dx, int B, int HW, int C, void* stream);

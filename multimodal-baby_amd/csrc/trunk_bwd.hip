@@ -254,81 +254,7 @@ __global__ __launch_bounds__(256) void relu_mask_kernel(const T* y, const T* dy,
     }
 }
 
-// ---- max pool 3x3 / 2 pad 1 (NHWC) forward on an already-activated tensor, and backward (first arg-max wins) -----------
-template <typename T>
-__global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int H, int W, int C) {
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const long total = (long)B * Ho * Wo * C;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        const long p = i / C;
-        const int ox = (int)(p % Wo), oy = (int)((p / Wo) % Ho), b = (int)(p / ((long)Wo * Ho));
-        float m = -INFINITY;
-        for (int ky = 0; ky < 3; ++ky) {
-            const int yin = 2 * oy - 1 + ky;
-            if (yin < 0 || yin >= H) continue;
-            for (int kx = 0; kx < 3; ++kx) {
-                const int xin = 2 * ox - 1 + kx;
-                if (xin < 0 || xin >= W) continue;
-                m = fmaxf(m, ElemTraits<T>::to_f(x[(((long)b * H + yin) * W + xin) * C + c]));
-            }
-        }
-        y[i] = ElemTraits<T>::from_f(m);
-    }
-}
-
-// gather form of the backward (deterministic, no atomics): dx[in] = sum over the <= 4 windows containing `in` of
-// dy[window] where `in` is that window's first arg-max (row-major scan order, like torch).  One 16-byte channel chunk
-// per thread; the 3x3 neighbourhoods of the candidate windows overlap in a 5x5 patch that is loaded once.
-template <typename T>
-__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx,
-                                                          int B, int H, int W, int C) {
-    constexpr int EPC = ElemTraits<T>::kPerChunk;
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, CC = C / EPC;
-    const long total = (long)B * H * W * CC;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % CC) * EPC;
-        const long p = i / CC;
-        const int xi = (int)(p % W), yi = (int)((p / W) % H), b = (int)(p / ((long)W * H));
-        Chunk<T> v, o;
-        v.load(x + p * C + c);
-        float acc[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) acc[e] = 0.f;
-        for (int oy = (yi + 1) / 2 - 1; oy <= (yi + 1) / 2; ++oy) {         // windows with 2*oy - 1 <= yi <= 2*oy + 1
-            if (oy < 0 || oy >= Ho || 2 * oy - 1 > yi || 2 * oy + 1 < yi) continue;
-            for (int ox = (xi + 1) / 2 - 1; ox <= (xi + 1) / 2; ++ox) {
-                if (ox < 0 || ox >= Wo || 2 * ox - 1 > xi || 2 * ox + 1 < xi) continue;
-                bool first[EPC];
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) first[e] = true;
-                for (int ky = 0; ky < 3; ++ky) {
-                    const int yy = 2 * oy - 1 + ky;
-                    if (yy < 0 || yy >= H) continue;
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const int xx = 2 * ox - 1 + kx;
-                        if (xx < 0 || xx >= W || (yy == yi && xx == xi)) continue;
-                        Chunk<T> u;
-                        u.load(x + (((long)b * H + yy) * W + xx) * C + c);
-                        const bool before = (yy < yi) || (yy == yi && xx < xi);
-#pragma unroll
-                        for (int e = 0; e < EPC; ++e)
-                            if (u.get(e) > v.get(e) || (before && u.get(e) == v.get(e))) first[e] = false;
-                    }
-                }
-                Chunk<T> g;
-                g.load(dy + (((long)b * Ho + oy) * Wo + ox) * C + c);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e)
-                    if (first[e]) acc[e] += g.get(e);
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) o.set(e, acc[e]);
-        o.store(dx + p * C + c);
-    }
-}
-
+// ---- max pool 3x3 / 2 pad 1 (NHWC) on an already-activated tensor ----------------------------------------------------------
 // max pool with recorded arg-max (first maximum in row-major window order, like torch): the backward then needs, per input
 // pixel, the <= 4 covering windows' index bytes and gradients instead of re-scanning 4 x 9 inputs
 template <typename T>
@@ -647,23 +573,6 @@ extern "C" int cvcl_relu_mask(int dtype, const void* y, const void* dy, void* dx
         hipLaunchKernelGGL(relu_mask_kernel<float>, dim3(cvcl_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const float*)y, (const float*)dy, (float*)dx, n);
     else
         hipLaunchKernelGGL(relu_mask_kernel<bf16_t>, dim3(cvcl_grid(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y, (const bf16_t*)dy, (bf16_t*)dx, n);
-    CVCL_LAUNCH_CHECK();
-    return CVCL_OK;
-}
-
-extern "C" int cvcl_maxpool3x3s2(int dtype, const void* x, const void* dy, void* out, int B, int H, int W, int C, void* stream) {
-    CVCL_CHECK_DTYPE(dtype, "cvcl_maxpool3x3s2");
-    CVCL_CHECK_ARG(x && out && B > 0 && H > 0 && W > 0 && C > 0 && C % epc_of(dtype) == 0, "cvcl_maxpool3x3s2: bad args");
-    CvclProfScope prof(stream, CVCL_K_MAXPOOL);
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipStream_t s = (hipStream_t)stream;
-    if (!dy) {       // forward: out = pooled [B,Ho,Wo,C]
-        if (dtype == CVCL_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(cvcl_grid((long)B * Ho * Wo * C, 256, 8192)), dim3(256), 0, s, (const float*)x, (float*)out, B, H, W, C);
-        else hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(cvcl_grid((long)B * Ho * Wo * C, 256, 8192)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, B, H, W, C);
-    } else {         // backward: out = dx [B,H,W,C]
-        if (dtype == CVCL_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(cvcl_grid((long)B * H * W * C / 4, 256, 8192)), dim3(256), 0, s, (const float*)x, (const float*)dy, (float*)out, B, H, W, C);
-        else hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(cvcl_grid((long)B * H * W * C / 8, 256, 8192)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, B, H, W, C);
-    }
     CVCL_LAUNCH_CHECK();
     return CVCL_OK;
 }

@@ -15,7 +15,7 @@ trunk's compute dtype (fp32 parity mode / bf16); parameter gradients are returne
   stem 7x7        fwd  cvcl_stem_conv7x7                  dW  cvcl_stem_im2col + cvcl_gemm_tn (bf16) / cvcl_conv_wgrad_direct (fp32)
   BatchNorm(+ReLU) fwd statistics from the conv epilogues -> bn_finalize (running stats) -> bn_apply;  bwd  cvcl_bn_bwd
   Bottleneck tail  fwd cvcl_bn_add_relu (BN3 + identity + ReLU in one pass);  bwd  cvcl_bn_bwd mode 2 (mask from the output)
-  max / avg pool, residual add + ReLU: cvcl_maxpool3x3s2, cvcl_avgpool(_bwd), cvcl_bn_add_relu / cvcl_relu_mask
+  max / avg pool, residual add + ReLU: cvcl_maxpool3x3s2_idx, cvcl_avgpool(_bwd), cvcl_bn_add_relu / cvcl_relu_mask
 
 There is no PyTorch-op fallback: CPU tensors raise in ``_hip.ptr``.
 """
