@@ -27,7 +27,7 @@ namespace {
 
 constexpr size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-constexpr int kMaxD = 2048, kMaxC = 4096, kMaxN = 1 << 24, kMaxRows = 4096;
+constexpr int kMaxD = 2048, kMaxClasses = 4096, kMaxN = 1 << 24, kMaxRows = 4096;
 
 // ================================================================================================================================
 // class means
@@ -48,7 +48,7 @@ ChunkPlan chunk_plan(int N) {
 // hist[chunk][c] = rows of class c in the chunk (integer LDS counters: exact, order-free)
 __global__ __launch_bounds__(256) void cm_hist_kernel(const int32_t* __restrict__ label, int N, int C, int chunk_rows,
                                                       int32_t* __restrict__ hist) {
-    __shared__ int cnt[kMaxC];
+    __shared__ int cnt[kMaxClasses];
     for (int c = threadIdx.x; c < C; c += 256) cnt[c] = 0;
     __syncthreads();
     const int r0 = blockIdx.x * chunk_rows, r1 = min(N, r0 + chunk_rows);
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void cm_offsets_kernel(const int32_t* __restri
 __global__ __launch_bounds__(64) void cm_scatter_kernel(const int32_t* __restrict__ label, int N, int C, int chunk_rows,
                                                         const int32_t* __restrict__ hist, const int32_t* __restrict__ class_off,
                                                         int32_t* __restrict__ perm) {
-    __shared__ int base[kMaxC];
+    __shared__ int base[kMaxClasses];
     const int lane = threadIdx.x;
     for (int c = lane; c < C; c += 64) base[c] = class_off[c] + hist[(long)blockIdx.x * C + c];
     __syncthreads();
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256) void paired_l2_kernel(const float* __restrict_
 }  // namespace
 
 extern "C" size_t cvcl_class_mean_workspace_bytes(int N, int D, int C) {
-    if (N < 1 || N >= kMaxN || D < 1 || D > kMaxD || C < 1 || C > kMaxC) return 0;
+    if (N < 1 || N >= kMaxN || D < 1 || D > kMaxD || C < 1 || C > kMaxClasses) return 0;
     const ChunkPlan cp = chunk_plan(N);
     return align16((size_t)cp.n * C * 4) + align16((size_t)C * 4) + align16((size_t)N * 4);
 }
@@ -394,7 +394,7 @@ extern "C" int cvcl_class_mean_f32(const float* x, const int32_t* label, int N, 
     CVCL_CHECK_ARG(N >= 1, "cvcl_class_mean_f32: N %d < 1", N);
     CVCL_CHECK_ARG(N < kMaxN, "cvcl_class_mean_f32: N %d >= 2^24", N);
     CVCL_CHECK_ARG(D >= 1 && D <= kMaxD, "cvcl_class_mean_f32: D %d outside 1..%d", D, kMaxD);
-    CVCL_CHECK_ARG(C >= 1 && C <= kMaxC, "cvcl_class_mean_f32: C %d outside 1..%d", C, kMaxC);
+    CVCL_CHECK_ARG(C >= 1 && C <= kMaxClasses, "cvcl_class_mean_f32: C %d outside 1..%d", C, kMaxClasses);
     CVCL_CHECK_ARG(workspace, "cvcl_class_mean_f32: null pointer (workspace)");
     const size_t need = cvcl_class_mean_workspace_bytes(N, D, C);
     CVCL_CHECK_ARG(workspace_bytes >= need, "cvcl_class_mean_f32: workspace_bytes %zu < %zu", workspace_bytes, need);
@@ -467,7 +467,7 @@ extern "C" int cvcl_triu_pearson_f32(const float* A, const float* B, int C, doub
 extern "C" int cvcl_paired_l2_f32(const float* x, const float* y, int C, int D, float eps, float* d, void* stream) {
     CVCL_CHECK_ARG(x && y, "cvcl_paired_l2_f32: null pointer (x / y)");
     CVCL_CHECK_ARG(d, "cvcl_paired_l2_f32: null pointer (d)");
-    CVCL_CHECK_ARG(C >= 1 && C <= kMaxC, "cvcl_paired_l2_f32: C %d outside 1..%d", C, kMaxC);
+    CVCL_CHECK_ARG(C >= 1 && C <= kMaxClasses, "cvcl_paired_l2_f32: C %d outside 1..%d", C, kMaxClasses);
     CVCL_CHECK_ARG(D >= 1 && D <= kMaxD, "cvcl_paired_l2_f32: D %d outside 1..%d", D, kMaxD);
     hipStream_t st = (hipStream_t)stream;
     CvclProfScope prof(stream, CVCL_K_OTHER);

@@ -267,7 +267,7 @@ __device__ __forceinline__ void cvcl_bn_stats_out(float* stats, int acc_mode, lo
 // the running-statistics update r <- (1 - m) r + m x: one spelling, shared by the in-place, the deferred and the on-load forms
 __device__ inline float bn_ema(float r, float x, float m) { return fmaf(m, x, (1.f - m) * r); }
 
-// finalize-on-load source: the accumulators of the layer whose output a kernel is about to normalise (csrc/resnext.hip)
+// finalize-on-load source: the accumulators of the layer whose output a kernel is about to normalise (csrc/bn.hip)
 struct BnSrc {
     const long long* acc;           // [8][2][C] accumulators of the STORED tensor (NULL: no finalize-on-load, read scale / shift)
     int C;
@@ -325,6 +325,43 @@ __device__ __forceinline__ void bn_slice_affine(const BnSrc& b, int c0, bool pub
 // cvcl_conv1x1_gram with the operand's BatchNorm affine formed inside the kernel from `src` (internal, C++ linkage: bn_gram.hip)
 int cvcl_conv1x1_gram_src(const void* A, int lda, long M, int K, const float* a_scale, const float* a_shift, const BnSrc* src, int a_relu,
                           void* workspace, size_t workspace_bytes, const double** gram_out, void* stream);
+
+// ---- between the trunk walk (csrc/resnext.hip) and the kernel files it launches into (csrc/bn.hip, stem.hip, gconv.hip); the public
+// entries are in cvcl_hip.h ----
+constexpr int kTrunkLayers = 53;                          // conv+bn layers: the stem, then conv1, conv2, conv3[, downsample] per block
+constexpr int kMaxC = 2048;                               // the widest layer: row length of the centres and of each affine half
+constexpr int kAffStride = 2 * kMaxC;                     // floats per layer of the affines [scale | shift] and the moments [mean | var]
+constexpr int kMaxStatsRows = 1024;                       // partial statistics rows of a trunk workspace
+constexpr size_t kTrunkAccLayer = (size_t)kBnAccRows * 2 * kMaxC;     // int64 slots of one layer's BatchNorm accumulators [8][2][2048]
+// the layer tables of the two one-launch kernels over the whole trunk (they travel by value in the kernel argument block)
+struct EvalAffineAll {
+    const float* gamma[kTrunkLayers]; const float* beta[kTrunkLayers]; const float* rm[kTrunkLayers]; const float* rv[kTrunkLayers];
+    int C[kTrunkLayers];
+};
+struct ApplyMomentsAll {
+    float* rm[kTrunkLayers]; float* rv[kTrunkLayers]; int64_t* nbt[kTrunkLayers];
+    int C[kTrunkLayers];
+};
+// csrc/bn.hip.  cvcl_bn_finalize with the moments output of the deferred-statistics pass (moments != NULL: [mean | var] at moments_ld)
+int cvcl_bn_finalize_launch(const float* stats, int rows, long count, const float* gamma, const float* beta, float* running_mean,
+                            float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* scale, float* shift, int C,
+                            float* moments, int moments_ld, const float* centre, void* stream);
+int cvcl_bn_eval_affine_all(const EvalAffineAll& t, float eps, float* affine, const float* centres, float* centres_out, void* stream);
+int cvcl_bn_apply_moments_all(const ApplyMomentsAll& t, const float* moments, float momentum, void* stream);
+// grouped train-mode BatchNorm: T groups of rows_g rows; a group affine `a` is [scale [T][C] | shift [T][C]]; part: partials scratch
+size_t cvcl_bn_group_part_floats(int T);
+int cvcl_bn_group_affine(const float* y, int T, long rows_g, int C, const float* gamma, const float* beta, float eps, float* part, float* a,
+                         void* stream);
+int cvcl_bn_group_relu(float* x, const float* a, int T, long rows, int C, long rows_g, void* stream);               // in place
+int cvcl_bn_group_add_relu(const float* raw, const float* a, const float* idn, const float* idn_a, float* out, int T, long rows, int C,
+                           long rows_g, void* stream);                                                                // idn_a NULL: plain identity
+int cvcl_bn_group_relu_maxpool(const float* x, const float* a, float* y, int B, int H, int W, int C, int group, void* stream);
+// csrc/stem.hip, csrc/gconv.hip: the bf16 weight layouts (shapes checked by cvcl_pack_conv_weight), and cvcl_gconv3x3 with the input's
+// BatchNorm affine formed inside the kernel from `src` (bf16 only; NULL: a_scale / a_shift)
+int cvcl_pack_stem_bf16(const float* w_oihw, void* out, void* stream);
+int cvcl_pack_gconv_bf16(const float* w_oihw, void* out, int cout, int cin_per_group, void* stream);
+int cvcl_gconv3x3_src(int dtype, const void* x, const float* a_scale, const float* a_shift, const BnSrc* src, const void* w_packed, void* y,
+                      float* stats, int stats_rows, const float* centre, int B, int H, int W, int C, int groups, int stride, void* stream);
 
 // sum_{i < n} load(i), UN loads in flight per wait, additions in index order (same result as the plain loop, deterministic).
 // A `for (...) acc += p[i]` loop waits for every load before issuing the next (one L2 / HBM round trip per element): these

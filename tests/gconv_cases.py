@@ -1,4 +1,4 @@
-"""The case tables of cvcl_gconv3x3 (csrc/resnext.hip: gconv_mfma_kernel<WIDE, NPF, NMT> for bf16, gconv_tiled_f32_kernel<CG> and
+"""The case tables of cvcl_gconv3x3 (csrc/gconv.hip: gconv_mfma_kernel<WIDE, NPF, NMT> for bf16, gconv_tiled_f32_kernel<CG> and
 gconv_direct_f32_kernel for fp32), an exact float64 reference of the entry, integer-valued operands on which every fp32 sum is
 exact in any order, and Python restatements of the two launch plans.
 
@@ -23,7 +23,7 @@ def out_hw(H, W, stride):
 
 # ---- the launch plans, restated ---------------------------------------------------------------------------------------------------
 def bf16_plan(B, H, W, C, stride):
-    """restates gconv_plan and the instantiation choice of gconv3x3_impl (csrc/resnext.hip)"""
+    """restates gconv_plan and the instantiation choice of cvcl_gconv3x3_src (csrc/gconv.hip)"""
     Ho, Wo = out_hw(H, W, stride)
     Wp = W + 2
 
@@ -52,7 +52,7 @@ def bf16_plan(B, H, W, C, stride):
 
 
 def f32_plan(B, H, W, C, stride, aligned=True):
-    """restates the fp32 branch of gconv3x3_impl (csrc/resnext.hip): the tiled kernel's band rule and grid, or the direct kernel"""
+    """restates the fp32 branch of cvcl_gconv3x3_src (csrc/gconv.hip): the tiled kernel's band rule and grid, or the direct kernel"""
     Ho, Wo = out_hw(H, W, stride)
     cg = C // GROUPS
 

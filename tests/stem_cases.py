@@ -1,4 +1,4 @@
-"""The case tables of the ResNeXt forward kernels around the grouped convolution (csrc/resnext.hip: the four stem kernels,
+"""The case tables of the ResNeXt forward kernels around the grouped convolution (csrc/stem.hip: the four stem kernels; csrc/bn.hip:
 bn_finalize, bn_eval_affine, col_stats, bn_relu_maxpool, bn_add_relu, bn_relu_apply, avgpool), exact float64 references of each
 entry, operands on which every fp32 product, sum, fmaf and maximum is exact in any order, and Python restatements of the launchers.
 

@@ -1,4 +1,4 @@
-"""Finalize-on-load (round 6; csrc/resnext.hip "finalize-on-load", include/cvcl_hip.h "BatchNorm accumulators"): in the bf16
+"""Finalize-on-load (round 6; csrc/bn.hip "finalize-on-load", include/cvcl_hip.h "BatchNorm accumulators"): in the bf16
 train-mode trunk the convolutions whose consumer normalises a fixed set of channels ACCUMULATE their per-channel batch statistics
 (int64 fixed point, one row per XCD) and that consumer -- the grouped 3x3's prologue (BN1 of every Bottleneck), the Gram launch ahead of
 conv3 (BN2 of layers 1-2) -- forms its channels' (scale, shift) itself instead of waiting for a ``cvcl_bn_finalize`` launch

@@ -4,7 +4,7 @@
 import csv, sys
 trace = sys.argv[1]
 out = sys.argv[2] if len(sys.argv) > 2 else None
-fused = 2  # stages with the fused tail in train mode (csrc/resnext.hip)
+fused = 2  # stages with the fused tail in train mode (bottleneck_fwd, csrc/resnext.hip)
 rows = list(csv.DictReader(open(trace)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 def is_conv_gemm(n):
