@@ -180,6 +180,20 @@ def plot_attention(path, image, cam):
     plt.close(fig)
 
 
+def write_attention_overlays(paths, frames, cams):
+    """--attention_overlays: the PNGs --plot_attention names, without matplotlib -- ``frames`` [T, 3, H, W] normalised device frames
+    with ``cams`` [T, h, w], rendered in one batch on the device (attention_maps.overlay_attention_maps: bicubic resize, scipy's
+    gaussian blur, min-max normalisation, viridis, the attn ** 0.7 blend of getAttMap) and written at the frames' own size with PIL."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise SystemExit(f"--attention_overlays needs Pillow ({e})")
+    from multimodal.attention_maps import overlay_attention_maps
+    tiles = overlay_attention_maps(frames.float(), cams).cpu().numpy()             # uint8 [T, H, W, 3]
+    for path, tile in zip(paths, tiles):
+        Image.fromarray(tile).save(path)
+
+
 CLIP_CONFIG = {"model": "clip", "seed": None, "shuffle_utterances": None, "cnn": "clip", "augment_frames": None,
                "multiple_frames": None}                    # the run attributes of a --clip_eval record (eval.py:39-47)
 
@@ -195,6 +209,7 @@ def check_clip_args(args):
         raise SystemExit("--clip_eval needs --clip_checkpoint PATH (OpenAI CLIP weights: a TorchScript archive such as ViT-L-14.pt, or a "
                          "state_dict file) and --clip_bpe PATH (CLIP's bpe_simple_vocab_16e6.txt or .txt.gz); neither is shipped or fetched")
     for flag, on in (("--attention_maps", args.attention_maps), ("--plot_attention", args.plot_attention),
+                     ("--attention_overlays", getattr(args, "attention_overlays", False)),
                      ("--attention_rollout", args.attention_rollout), ("--hip_graph", args.hip_graph)):
         if on:
             raise SystemExit(f"{flag} is not built for --clip_eval (CLIP attention maps and graph replay of the CLIP towers are out of scope)")
@@ -295,13 +310,13 @@ def main(args):
     if args.attention_rollout and not getattr(model.vision_encoder, "vit_dino", False):        # (never under --clip_eval)
         raise SystemExit("--attention_rollout is defined for a ViT checkpoint (--vit_dino) only: a ResNeXt encoder has no "
                          "self-attention to roll out; its --attention_maps are Grad-CAM maps")
-    if args.attention_rollout and not (args.attention_maps or args.plot_attention):
+    if args.attention_rollout and not (args.attention_maps or args.plot_attention or args.attention_overlays):
         raise SystemExit("--attention_rollout selects the kind of map --attention_maps DIR / --plot_attention write; give one of them")
 
     results, pending, first = [], [], 0
-    want_maps = bool(args.attention_maps or args.plot_attention)
+    want_maps = bool(args.attention_maps or args.plot_attention or args.attention_overlays)
     cams = []
-    if args.plot_attention:
+    if args.plot_attention or args.attention_overlays:
         os.makedirs(args.attention_maps or "results", exist_ok=True)
 
     def record(i, class_label, logits_list, pred):
@@ -328,15 +343,22 @@ def main(args):
         if want_maps:
             res, maps = res
             cams.append(maps.cpu())
+        overlay_paths, overlay_frames = [], []
         for k, (logits_list, pred) in enumerate(res):
             i = first + k
             class_label = record(i, pending[k][3][0][0], logits_list, pred)
-            if args.plot_attention:                        # the target (index 0): its frame and its map w.r.t. the label
+            if args.plot_attention or args.attention_overlays:     # the target (index 0): its frame and its map w.r.t. the label
                 frames = pending[k][0].squeeze(0).to(device)
                 if frames.dtype in (torch.uint8, torch.int64):
                     frames = data.on_after_batch_transfer((frames,), 1, training=False)[0]
                 name = f"{cfg['model']}_{class_label}_{i % 100}_attn_map.png"
-                plot_attention(os.path.join(args.attention_maps or "results", name), frames[0], maps[k, 0])
+                if args.plot_attention:
+                    plot_attention(os.path.join(args.attention_maps or "results", name), frames[0], maps[k, 0])
+                else:                                      # rendered below, the whole pending batch in one device pass
+                    overlay_paths.append(os.path.join(args.attention_maps or "results", name))
+                    overlay_frames.append(frames[0])
+        if overlay_paths:
+            write_attention_overlays(overlay_paths, torch.stack(overlay_frames), maps[:len(overlay_paths), 0].contiguous())
         first += len(pending)
         pending.clear()
 
@@ -445,6 +467,10 @@ def _parser():
     parser.add_argument("--plot_attention", action="store_true",
                         help="save one overlay PNG per trial, {model}_{class}_{i %% 100}_attn_map.png, under the --attention_maps "
                              "directory (results/ without it); needs matplotlib")
+    parser.add_argument("--attention_overlays", action="store_true",
+                        help="the PNGs of --plot_attention without matplotlib: every pending batch of trials is rendered in one pass on "
+                             "the device (resize, blur, normalisation, viridis, blend) and written with Pillow at the frames' own size; "
+                             "with --plot_attention as well, that flag's matplotlib figures are written")
     parser.add_argument("--attention_rollout", action="store_true",
                         help="ViT checkpoints: the maps of --attention_maps / --plot_attention are the CLS token's attention rollout "
                              "over all blocks (head-mean attention plus the residual path, multiplied through the blocks) instead of "

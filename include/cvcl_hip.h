@@ -1125,6 +1125,35 @@ int cvcl_caption_cider(const int64_t* hyp, const int64_t* hyp_len, int N, int Lh
                        const int64_t* ref_off, const int64_t* ref_off_dev, int vocab_size, const int64_t* df_key, const int64_t* df_cnt,
                        const int64_t* df_off, int64_t n_df, double* cider, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Attention overlays (csrc/overlay.hip, ABI v7 additive): what getAttMap / preprocess_attn_map (multimodal/attention_maps.py) do per
+ * map on the host, for M maps in one call; DESIGN.md "Attention overlays" states the definitions.  Everything is validated before
+ * anything is enqueued (CVCL_EINVAL, cvcl_last_error names the argument); the kernels run on the caller's stream only, in the caller's
+ * workspace, without atomics: two calls give the same bits.  CVCL_K_OTHER.
+ *   maps [M, h, w] f32; images [N, 3, H, W] f32 NCHW, normalised; mean, std: HOST arrays of 3 floats, the frame is img * std + mean
+ *   (one multiply, one add); image_of_map [M] int32 on the device: the image under map m (NULL: image m, needs M <= N); lut [n_lut, 3]
+ *   f32, 2 <= n_lut <= 1024.  Limits: 1 <= H, W <= 1024, 1 <= h <= H, 1 <= w <= W.  Per map, in order:
+ *   1. (h, w) != (H, W): cvcl_bicubic_resize to H x W.
+ *   2. CVCL_OVERLAY_BLUR: scipy.ndimage.gaussian_filter(map, sigma = 0.02 max(H, W)): separable, rows axis first, radius
+ *      int(4 sigma + 0.5), weights exp(-t^2 / 2 sigma^2) normalised to sum 1 in double, mode "reflect" (period 2n, any radius), fp32 sums.
+ *   3. x = (m - lo) / (hi - lo) with the map's own min / max (a constant map: x = m - lo = 0).  CVCL_OVERLAY_HAS_RANGE: lo = vmin,
+ *      hi = vmax and x is clamped to [0, 1] (the host functions do not clamp, and their x ** 0.7 is NaN below vmin).
+ *   4. colour = lut[min(int(x n_lut), n_lut - 1)];  5. t = x^gamma, out = (1 - t) frame + t colour  (0 <= gamma <= 64);
+ *   6. out_u8 = floor(clamp(out, 0, 1) 255 + 0.5).
+ *   CVCL_OVERLAY_IMAGE_ONLY: t = 0, out = frame; maps, lut, gamma, the range and out_map are not used (maps and lut may be NULL).
+ *   Outputs, each optional, at least one: out_f32 / out_u8 hold pixel (y, x) channel c of map m at element dst_offset[m] + y row_pitch
+ *   + 3 x + c (dst_offset [M] int64 on the device; NULL: m H row_pitch; row_pitch >= 3 W), so one launch writes the tiles of a larger
+ *   canvas; out_elems is the element count of those buffers, and a map whose tile would not lie inside it (or whose image_of_map entry
+ *   is outside [0, N)) is skipped.  out_map [M, H, W] f32: x.  NaN in a map: unspecified values, same accesses.
+ *   maps, images, the outputs and the workspace are 16-byte aligned; workspace >= cvcl_attn_overlay_workspace_bytes (0 = refused sizes
+ *   or flags, never 0 otherwise).                                                                                                  */
+enum { CVCL_OVERLAY_BLUR = 1, CVCL_OVERLAY_HAS_RANGE = 2, CVCL_OVERLAY_IMAGE_ONLY = 4 };
+size_t cvcl_attn_overlay_workspace_bytes(int M, int h, int w, int H, int W, int flags);
+int cvcl_attn_overlay(const float* maps, int M, int h, int w, const float* images, int N, int H, int W, const float* mean,
+                      const float* std, const int32_t* image_of_map, const float* lut, int n_lut, int flags, float gamma, float vmin,
+                      float vmax, const int64_t* dst_offset, int64_t row_pitch, int64_t out_elems, float* out_f32, uint8_t* out_u8,
+                      float* out_map, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@ backward reaches the hooked layer-4 map through the trunk's avgpool bridge, ``re
 map as one exact-fp32 MFMA contraction over the layer-4 map (cvcl_hip.h, "Grad-CAM").  ``gradCAM_captions`` /
 ``gradCAM_for_captioning_lm`` (reference analysis_tools/multimodal_visualization.py:9-49) give one map per word of a caption for the
 captioning LM: the per-word gradients of all captions come from one multi-seed BPTT sweep (csrc/lstm.hip) and feed the same
-contraction.  The plotting helpers are host-side
+contraction.  ``overlay_attention_maps`` / ``attention_grid`` render any of these maps over their frames on the device
+(csrc/overlay.hip): the batched form of ``getAttMap``.  The reference's own plotting helpers (``getAttMap``, ``preprocess_attn_map``,
+``plot_image``) stay host-side
 numpy / matplotlib; matplotlib and scipy are imported only when a helper needs them."""
 from __future__ import annotations
 
@@ -430,6 +432,186 @@ def gradCAM_for_captioning_lm(model, x, y, y_len, steps=None):
     cams = gradCAM_captions(model, x.unsqueeze(0).to(dev), y.unsqueeze(0).to(dev), y_len.reshape(1).to(dev))[0]
     host = cams.cpu().numpy()
     return [None if step == 0 else host[step - 1] for step in steps]
+
+
+# ---- overlays on the device (csrc/overlay.hip) ---------------------------------------------------------------------------
+
+_LUT_CACHE = {}                                             # (colormap name, device) -> [n, 3] fp32 device tensor
+
+
+def resolve_lut(cmap) -> np.ndarray:
+    """The [n, 3] float32 colour table of ``cmap``: a matplotlib colormap name (``cm(np.arange(cm.N))[:, :3]``; matplotlib is imported
+    here, only for a name that colormaps.BUILTIN does not hold -- "viridis", the default, is built in with matplotlib's own values) or
+    an explicit [n, 3] array / tensor of RGB values, 2 <= n <= 1024."""
+    from .colormaps import BUILTIN
+    if isinstance(cmap, str) and cmap in BUILTIN:
+        lut = np.asarray(BUILTIN[cmap], dtype=np.float64)
+    elif isinstance(cmap, str):
+        try:
+            import matplotlib
+        except ImportError as e:
+            raise H.CvclError(f"cmap {cmap!r} is a matplotlib name and matplotlib is missing ({e}); pass an [n, 3] array instead") from e
+        cm = matplotlib.colormaps[cmap]
+        lut = cm(np.arange(cm.N))[:, :3]
+    else:
+        lut = cmap.detach().cpu().numpy() if torch.is_tensor(cmap) else np.asarray(cmap)
+    lut = np.ascontiguousarray(lut, dtype=np.float32)
+    if lut.ndim != 2 or lut.shape[1] != 3 or not 2 <= lut.shape[0] <= 1024:
+        raise ValueError(f"a colour table is [n, 3] with 2 <= n <= 1024, got {lut.shape}")
+    return lut
+
+
+def device_lut(cmap, device) -> torch.Tensor:
+    """resolve_lut on ``device``; a colormap NAME is resolved and uploaded once per (name, device)."""
+    device = torch.device(device)
+    if not isinstance(cmap, str):
+        return torch.from_numpy(resolve_lut(cmap)).to(device)
+    index = torch.cuda.current_device() if device.type == "cuda" and device.index is None else device.index
+    key = (cmap, device.type, index)
+    if key not in _LUT_CACHE:
+        _LUT_CACHE[key] = torch.from_numpy(resolve_lut(cmap)).to(device)
+    return _LUT_CACHE[key]
+
+
+def grid_geometry(n_tiles: int, H: int, W: int, nrow: int = 4, padding: int = 2):
+    """torchvision.utils.make_grid's layout of ``n_tiles`` >= 2 tiles of H x W: -> (Hc, Wc, [(y, x) of every tile's top-left pixel]).
+    min(nrow, n_tiles) tiles per row, ``padding`` pixels between tiles and around the canvas, a ragged last row left empty."""
+    if n_tiles < 1 or nrow < 1 or padding < 0 or H < 1 or W < 1:
+        raise ValueError(f"grid of {n_tiles} tiles of {H} x {W}, nrow {nrow}, padding {padding}")
+    xmaps = min(nrow, n_tiles)
+    ymaps = -(-n_tiles // xmaps)
+    th, tw = H + padding, W + padding
+    return th * ymaps + padding, tw * xmaps + padding, [((k // xmaps) * th + padding, (k % xmaps) * tw + padding) for k in range(n_tiles)]
+
+
+def _overlay_launch(images, maps, image_of_map, lut, flags, gamma, vmin, vmax, mean, std, dst_offset, pitch, out_f32, out_u8, out_map):
+    """One cvcl_attn_overlay call; ``maps`` [M, h, w] (None with OVERLAY_IMAGE_ONLY: one tile per entry of the destination table)."""
+    import ctypes
+    N, _, Hh, Ww = images.shape
+    if maps is None:
+        M, h, w = (dst_offset.numel() if dst_offset is not None else N), Hh, Ww
+    else:
+        M, h, w = maps.shape
+    lib = H.lib()
+    need = lib.cvcl_attn_overlay_workspace_bytes(M, h, w, Hh, Ww, flags)
+    if need == 0:
+        raise H.CvclError(f"attention overlays: {M} maps of {h} x {w} on frames of {Hh} x {Ww} are outside the limits "
+                          "(1 <= H, W <= 1024, 1 <= h <= H, 1 <= w <= W)")
+    ws = torch.empty(need, dtype=torch.uint8, device=images.device)
+    colour = out_f32 if out_f32 is not None else out_u8
+    mean_c, std_c = ((ctypes.c_float * 3)(*(float(v) for v in t)) for t in (mean, std))     # host arrays, read during the call
+    H.check(lib.cvcl_attn_overlay(H.ptr(maps, torch.float32), M, h, w, H.ptr(images, torch.float32), N, Hh, Ww, ctypes.cast(mean_c, ctypes.c_void_p),
+                                  ctypes.cast(std_c, ctypes.c_void_p),
+                                  H.ptr(image_of_map, torch.int32), H.ptr(lut, torch.float32), 0 if lut is None else lut.shape[0], flags,
+                                  float(gamma), float(vmin), float(vmax), H.ptr(dst_offset, torch.int64), int(pitch),
+                                  0 if colour is None else colour.numel(), H.ptr(out_f32, torch.float32), H.ptr(out_u8, torch.uint8),
+                                  H.ptr(out_map, torch.float32), H.ptr(ws), need, H.stream_ptr()), "cvcl_attn_overlay")
+
+
+def _maps_and_index(images, maps, image_index):
+    """-> (maps as [M, h, w], image_of_map int32 [M] or None (map m over image m), the leading shape of the result)."""
+    N = images.shape[0]
+    if maps.dim() == 3:
+        lead, k = tuple(maps.shape[:1]), None
+    elif maps.dim() == 4:
+        if maps.shape[0] != N:
+            raise ValueError(f"[N, k, h, w] maps pair image n with its k maps: {maps.shape[0]} map rows for {N} images")
+        lead, k = tuple(maps.shape[:2]), maps.shape[1]
+    else:
+        raise ValueError(f"maps are [M, h, w], [N, k, h, w] or [N, 1, h, w], got {tuple(maps.shape)}")
+    flat = maps.reshape(-1, *maps.shape[-2:]).to(torch.float32).contiguous()
+    M = flat.shape[0]
+    if image_index is not None:
+        if k is not None:
+            raise ValueError("image_index goes with [M, h, w] maps; [N, k, h, w] maps are paired by their layout")
+        idx = torch.as_tensor(image_index, device=images.device).reshape(-1)
+        if idx.numel() != M or idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"image_index: one integer per map ({M}), got {tuple(idx.shape)} {idx.dtype}")
+        if bool(((idx < 0) | (idx >= N)).any()):
+            raise ValueError(f"image_index has entries outside [0, {N})")
+        return flat, idx.to(torch.int32).contiguous(), lead
+    if k is not None and k > 1:
+        return flat, torch.arange(N, dtype=torch.int32, device=images.device).repeat_interleave(k).contiguous(), lead
+    if M != N:
+        raise ValueError(f"{M} maps for {N} images: give image_index (one image per map) or [N, k, h, w] maps")
+    return flat, None, lead
+
+
+def _overlay_flags(blur, vmin, vmax):
+    if (vmin is None) != (vmax is None):
+        raise ValueError("vmin and vmax go together")
+    return (H.OVERLAY_BLUR if blur else 0) | (0 if vmin is None else H.OVERLAY_HAS_RANGE)
+
+
+@torch.no_grad()
+def overlay_attention_maps(images, maps, image_index=None, blur=True, cmap="viridis", vmin=None, vmax=None, gamma=0.7,
+                           mean=IMAGENET_MEAN, std=IMAGENET_STD, out="uint8", return_map=False):
+    """getAttMap for a batch, on the device (cvcl_attn_overlay): every map is resized bicubically to the frames' H x W (as
+    gradCAM(resize=True) does), blurred (scipy.ndimage.gaussian_filter, sigma = 0.02 max(H, W), mode reflect), normalised to [0, 1] by
+    its own min / max, coloured through ``cmap`` and blended into its de-normalised frame with weight x ** gamma.
+
+      images  [N, 3, H, W] fp32, normalised with ``mean`` / ``std`` (undone as img * std + mean)
+      maps    [M, h, w] (map m over image m, or over image ``image_index[m]``), [N, k, h, w] (image n with its k maps: the
+              ("block", k, .) layouts of gradCAM_pairs and the per-word maps of gradCAM_captions) or [N, 1, h, w]; h <= H, w <= W
+      cmap    a matplotlib name (resolved lazily, uploaded once per name and device) or an [n, 3] table: no matplotlib needed
+      vmin, vmax  normalise by this range instead and CLAMP x to [0, 1] (getAttMap does not clamp; its x ** 0.7 is NaN below vmin)
+      out     "uint8" (floor(clamp(v, 0, 1) * 255 + 0.5)), "float" or "both" (float, uint8): [..., H, W, 3] with the maps' leading shape
+      return_map  also return x, the normalised map after the blur, [..., H, W] fp32
+
+    Device tensors only; there is no CPU fallback."""
+    if out not in ("uint8", "float", "both"):
+        raise ValueError(f"out = {out!r}: 'uint8', 'float' or 'both'")
+    if not (torch.is_tensor(images) and torch.is_tensor(maps) and images.is_cuda and maps.is_cuda):
+        raise H.CvclError("overlay_attention_maps needs device tensors (got a CPU tensor); there is no CPU fallback")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"images are [N, 3, H, W], got {tuple(images.shape)}")
+    images = images.to(torch.float32).contiguous()
+    flat, index, lead = _maps_and_index(images, maps, image_index)
+    flags = _overlay_flags(blur, vmin, vmax)
+    M, (Hh, Ww), dev = flat.shape[0], images.shape[2:], images.device
+    out_f32 = torch.empty(M, Hh, Ww, 3, dtype=torch.float32, device=dev) if out in ("float", "both") else None
+    out_u8 = torch.empty(M, Hh, Ww, 3, dtype=torch.uint8, device=dev) if out in ("uint8", "both") else None
+    out_map = torch.empty(M, Hh, Ww, dtype=torch.float32, device=dev) if return_map else None
+    _overlay_launch(images, flat, index, device_lut(cmap, dev), flags, gamma, 0.0 if vmin is None else vmin, 0.0 if vmax is None else vmax,
+                    mean, std, None, 3 * Ww, out_f32, out_u8, out_map)
+    res = [t.view(*lead, *t.shape[1:]) for t in (out_f32, out_u8, out_map) if t is not None]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+@torch.no_grad()
+def attention_grid(images, maps, nrow=4, padding=2, **overlay_kwargs):
+    """The reference's attention-map figure (analysis_cvcl/generate_attention_maps.py) as one uint8 [Hc, Wc, 3] device tensor: the K
+    frames first, then their K overlays, ``nrow`` per row, laid out as torchvision.utils.make_grid lays out 2 K tiles (``padding``
+    pixels of 0 between and around them).  ``images`` [K, 3, H, W], ``maps`` [K, h, w] or [K, 1, h, w]; ``overlay_kwargs``: blur,
+    cmap, vmin, vmax, gamma, mean, std of overlay_attention_maps.  Both halves are written straight into the canvas by the overlay
+    kernel through its destination table (the frames with weight 0 on the colour): there is no paste pass."""
+    unknown = set(overlay_kwargs) - {"blur", "cmap", "vmin", "vmax", "gamma", "mean", "std"}
+    if unknown:
+        raise TypeError(f"attention_grid: unexpected arguments {sorted(unknown)}")
+    if not (torch.is_tensor(images) and torch.is_tensor(maps) and images.is_cuda and maps.is_cuda):
+        raise H.CvclError("attention_grid needs device tensors (got a CPU tensor); there is no CPU fallback")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"images are [K, 3, H, W], got {tuple(images.shape)}")
+    images = images.to(torch.float32).contiguous()
+    K, _, Hh, Ww = images.shape
+    if maps.dim() == 4 and maps.shape[1] == 1:
+        maps = maps[:, 0]
+    if maps.dim() != 3 or maps.shape[0] != K:
+        raise ValueError(f"maps are [K, h, w] or [K, 1, h, w] with K = {K}, got {tuple(maps.shape)}")
+    flat = maps.to(torch.float32).contiguous()
+    mean, std = overlay_kwargs.get("mean", IMAGENET_MEAN), overlay_kwargs.get("std", IMAGENET_STD)
+    vmin, vmax = overlay_kwargs.get("vmin"), overlay_kwargs.get("vmax")
+    flags = _overlay_flags(overlay_kwargs.get("blur", True), vmin, vmax)
+    Hc, Wc, origins = grid_geometry(2 * K, Hh, Ww, nrow, padding)
+    dev = images.device
+    canvas = torch.zeros(Hc, Wc, 3, dtype=torch.uint8, device=dev)
+    offsets = torch.tensor([(y * Wc + x) * 3 for y, x in origins], dtype=torch.int64).to(dev)
+    _overlay_launch(images, None, None, None, H.OVERLAY_IMAGE_ONLY, 0.0, 0.0, 0.0, mean, std, offsets[:K].contiguous(), 3 * Wc, None, canvas,
+                    None)
+    _overlay_launch(images, flat, None, device_lut(overlay_kwargs.get("cmap", "viridis"), dev), flags, overlay_kwargs.get("gamma", 0.7),
+                    0.0 if vmin is None else vmin, 0.0 if vmax is None else vmax, mean, std, offsets[K:].contiguous(), 3 * Wc, None, canvas,
+                    None)
+    return canvas
 
 
 # ---- host-side visualisation (numpy / matplotlib) ------------------------------------------------------------------------
