@@ -906,6 +906,30 @@ int cvcl_knn_vote(const float* top_cos, const int64_t* top_idx, int Nq, int k, c
                   float temperature, float* scores, int64_t* pred, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Retrieval ranks (csrc/neighbors.hip, ABI v7 additive): how far down the list of all base rows, sorted by cosine, a query's own row
+ * stands -- Recall@K, median rank.  The reference has no retrieval evaluation; this is the third consumer of the cosine tile walk.
+ *
+ * cvcl_rank_cosine: query i's positives are the base rows j with base_key[j] == q_key[i], every other row is a negative (both key
+ *   arrays are required; a single target per query is base_key[j] = j, q_key[i] = target[i]).  thr_cos [Nq] f32 / thr_idx [Nq] int64 =
+ *   the query's best positive and its global row: what cvcl_nn_cosine returns with q_group = q_key, base_group = base_key over the
+ *   WHOLE base set (the caller runs that search first; -1 / -inf without a positive).  rank [Nq] int64 = the number of negatives j of
+ *   this call with cos(i, j) > thr_cos[i], or cos(i, j) == thr_cos[i] and idx_offset + j < thr_idx[i]: the 0-based position of the best
+ *   positive in a stable descending sort with the other positives removed.  thr_idx[i] < 0: rank[i] = -1, also under accumulate.
+ *   accumulate = 1 adds this chunk's count to what rank holds; the counts are integers, so chunks in ANY order give the one-shot ranks.
+ *   cos(i, j) is cvcl_nn_cosine's expression on the same tile walk (norms in double, exact fp32 products, chains of 128 k,
+ *   float(double(dot) inv_q inv_b)): a pair's cosine has the bits the threshold has, which is what makes the comparison meaningful.
+ *   q, base, ldq, ldb, eps, idx_offset and the ranges of Nq / Nb / D as cvcl_nn_cosine.  No list and no matrix: each lane counts for
+ *   its queries in a register; the counts are reduced over lanes and waves, written per (split, query) into the workspace and summed
+ *   by a second kernel (no atomics).  Everything is validated before anything is enqueued (null pointers, sizes, strides below D, a
+ *   workspace that is too small or not 16-byte aligned, accumulate outside {0, 1}: CVCL_EINVAL, cvcl_last_error names the argument);
+ *   work is enqueued on the caller's stream only; NaN inputs are not supported.  Workspace: cvcl_rank_cosine_workspace_bytes
+ *   (0 = refused sizes).  CVCL_K_HEAD. */
+size_t cvcl_rank_cosine_workspace_bytes(int Nq, int Nb, int D);
+int cvcl_rank_cosine(const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, float eps, const int32_t* q_key,
+                     const int32_t* base_key, const float* thr_cos, const int64_t* thr_idx, int64_t idx_offset, int accumulate,
+                     int64_t* rank, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Perceptual-hash duplicates (csrc/phash.hip, ABI v7 additive): the first half of the reference's analysis_cvcl/duplicates.py, "exact
  * and approximate duplicates" -- the 16 x 16 average hash of a frame, and per evaluation hash the closest training hash, by Hamming
  * distance and by the reference's own measure, fuzz.ratio of the two hashes written as decimal strings.  All three entries validate

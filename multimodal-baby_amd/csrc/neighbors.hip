@@ -16,6 +16,9 @@
 // cvcl_knn_cosine  the same device function (cosine_tile_walk) with another tile epilogue: a sorted list of k per (split, query) in the
 //                  workspace instead of one running best, so a pair's cosine has cvcl_nn_cosine's bits by construction;
 //                  cvcl_knn_vote sums exp(cos / T) per class over such lists (section "k nearest neighbours" below).
+// cvcl_rank_cosine the walk's third epilogue: per query the number of negatives (base rows of another key) that beat a given
+//                  threshold (the query's best positive, which cvcl_nn_cosine found with the keys as groups), an integer counter per
+//                  lane and query, so the position of the best positive among all base rows costs no list and no matrix.
 // cvcl_nn_l1_u8    each WAVE owns TQ x TB (8 x 8) frame pairs: its lanes stride over the pixel dwords of one channel, every lane
 //                  holds TQ + TB loaded 16-byte pieces and TQ TB accumulators, so each loaded dword feeds TB (or TQ) v_sad_u8.
 //                  At the end of a channel a transposing wave reduction (63 exchanges for 64 sums) leaves the total of pair l in
@@ -105,6 +108,13 @@ struct KnnDev : CosDev {                         // pval / pidx: the lists, [spl
     int k;
 };
 
+struct RankDev : CosDev {                        // qg / bg: the keys; pidx: the counts, [splits][Nq]; pval is not used
+    const float* thr_cos; const int64_t* thr_idx;
+    long idx_offset;
+};
+
+enum { WALK_ARGMAX = 0, WALK_TOPK = 1, WALK_RANK = 2 };      // what becomes of a finished tile
+
 template <typename I>
 __device__ __forceinline__ bool knn_better(float v, I i, float bv, I bi) {      // (bitwise: three compares, no branches)
     return (bool)((int)(v > bv) | ((int)(v == bv) & (int)(i < bi)));
@@ -177,13 +187,16 @@ __device__ __forceinline__ void knn_wave_merge(float* lv, I* li, int k, bool liv
     if (lane == 0) *cnt = min(k, count + nlive);
 }
 
-// The tile walk of both cosine searches: this workgroup's query tile against the base tiles blockIdx.y, + gridDim.y, ...  TOPK
-// chooses what becomes of a finished tile: the running best per lane (cvcl_nn_cosine; reduced over lane halves and waves and written
-// per split at the end), or the sorted lists of `topk` entries (cvcl_knn_cosine; s_thr_v / s_thr_i / s_cnt [CT] in LDS are the lists'
-// thresholds and fill counts, null for the arg-max).  Everything up to tot[][] is one piece of code for both, which is why a pair's
-// cosine has the same bits in either search, whatever k, split or chunk.
-template <bool VEC, bool TOPK>
-__device__ __forceinline__ void cosine_tile_walk(const CosDev& p, int topk, float* s_thr_v, int* s_thr_i, int* s_cnt) {
+// The tile walk of the cosine searches: this workgroup's query tile against the base tiles blockIdx.y, + gridDim.y, ...  MODE
+// chooses what becomes of a finished tile: the running best per lane (WALK_ARGMAX, cvcl_nn_cosine; reduced over lane halves and waves
+// and written per split at the end), the sorted lists of `topk` entries (WALK_TOPK, cvcl_knn_cosine; s_thr_v / s_thr_i / s_cnt [CT] in
+// LDS are the lists' thresholds and fill counts, null otherwise), or the count per lane of the negatives that beat the query's
+// threshold (WALK_RANK, cvcl_rank_cosine; reduced and written as the running best is).  Everything up to tot[][] is one piece of code
+// for all three, which is why a pair's cosine has the same bits in each, whatever k, split or chunk -- and why comparing a cosine of
+// the rank count with a threshold the arg-max search produced is meaningful.
+template <bool VEC, int MODE, typename Dev>
+__device__ __forceinline__ void cosine_tile_walk(const Dev& p, int topk, float* s_thr_v, int* s_thr_i, int* s_cnt) {
+    constexpr bool TOPK = MODE == WALK_TOPK;
     __shared__ __attribute__((aligned(16))) char smem[2 * CT * CROWB];
     char* sQ = smem;
     char* sB = smem + CT * CROWB;
@@ -250,6 +263,23 @@ __device__ __forceinline__ void cosine_tile_walk(const CosDev& p, int topk, floa
         invq[mt] = m < p.Nq ? p.invq[m] : 0.0;
         qg[mt] = (p.qg && m < p.Nq) ? p.qg[m] : 0;
     }
+    // (rank count only) the threshold of each query: its cosine, and its row inside this call's base rows, clamped to 0 .. Nb (a
+    // row of an earlier chunk is below every row of this one, a row of a later chunk above); the count of a query without a
+    // threshold is not read
+    float thr_v[2] = {0.f, 0.f};
+    int thr_n[2] = {0, 0};
+    int beat[2] = {0, 0};
+    if constexpr (MODE == WALK_RANK) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const int m = m0 + wm * 64 + mt * 32 + l31;
+            if (m < p.Nq) {
+                const long t = (long)p.thr_idx[m] - p.idx_offset;
+                thr_v[mt] = p.thr_cos[m];
+                thr_n[mt] = t < 0 ? 0 : (t > (long)p.Nb ? p.Nb : (int)t);
+            }
+        }
+    }
 
     if (steps > 0) issue(0);
     long s = 0;
@@ -298,7 +328,24 @@ __device__ __forceinline__ void cosine_tile_walk(const CosDev& p, int topk, floa
                         for (int e = 0; e < 16; ++e) { tot[i][j][e] += acc[i][j][e]; acc[i][j][e] = 0.f; }
             }
         }
-        if constexpr (!TOPK) {
+        if constexpr (MODE == WALK_RANK) {
+            // epilogue (rows as below): a negative -- a row of another key -- counts where it would stand before the threshold in
+            // a stable descending sort
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int n = nbase + wn * 64 + nt * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
+                    const bool n_ok = n < p.Nb;
+                    const double ib = n_ok ? p.invb[n] : 0.0;
+                    const int g = n_ok ? p.bg[n] : 0;
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt) {
+                        const float c = (float)((double)tot[nt][mt][e] * invq[mt] * ib);
+                        beat[mt] += (int)(n_ok && g != qg[mt] && cvcl_better(c, n, thr_v[mt], thr_n[mt]));
+                    }
+                }
+        } else if constexpr (MODE == WALK_ARGMAX) {
             // epilogue: element e of tile (nt, mt) is base row nbase + wn 64 + nt 32 + 8 (e >> 2) + 4 h + (e & 3) against query mt
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
@@ -362,7 +409,19 @@ __device__ __forceinline__ void cosine_tile_walk(const CosDev& p, int topk, floa
             }
         }
     }
-    if constexpr (!TOPK) {
+    if constexpr (MODE == WALK_RANK) {
+        // lane halves, then the two waves of a query half (through LDS), then one count per query and split
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) beat[mt] += __shfl_xor(beat[mt], 32, 64);
+        __syncthreads();
+        int* rc = reinterpret_cast<int*>(smem);                  // [2][128]
+        if (h == 0) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) rc[wn * CT + wm * 64 + mt * 32 + l31] = beat[mt];
+        }
+        __syncthreads();
+        if (tid < CT && m0 + tid < p.Nq) p.pidx[(long)blockIdx.y * p.Nq + m0 + tid] = rc[tid] + rc[CT + tid];
+    } else if constexpr (MODE == WALK_ARGMAX) {
         // lane halves, then the two waves of a query half (through LDS), then one partial per query and split
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -395,7 +454,24 @@ __device__ __forceinline__ void cosine_tile_walk(const CosDev& p, int topk, floa
 
 template <bool VEC>
 __global__ __launch_bounds__(256, 2) void nn_cosine_kernel(CosDev p) {
-    cosine_tile_walk<VEC, false>(p, 1, nullptr, nullptr, nullptr);
+    cosine_tile_walk<VEC, WALK_ARGMAX>(p, 1, nullptr, nullptr, nullptr);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256, 2) void rank_cosine_kernel(RankDev p) {
+    cosine_tile_walk<VEC, WALK_RANK>(p, 1, nullptr, nullptr, nullptr);
+}
+
+// the splits' counts of a query, added in split order to what rank holds (accumulate) or to 0; -1 without a threshold
+__global__ __launch_bounds__(256) void rank_cosine_merge_kernel(const int32_t* __restrict__ pcnt, int splits, int Nq,
+                                                                const int64_t* __restrict__ thr_idx, int accumulate,
+                                                                int64_t* __restrict__ rank) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= Nq) return;
+    if (thr_idx[m] < 0) { rank[m] = -1; return; }
+    int64_t r = accumulate ? rank[m] : 0;
+    for (int s = 0; s < splits; ++s) r += pcnt[(long)s * Nq + m];
+    rank[m] = r;
 }
 
 template <bool VEC>
@@ -403,7 +479,7 @@ __global__ __launch_bounds__(256, 2) void knn_cosine_kernel(KnnDev p) {
     __shared__ float s_thr_v[CT];                    // per query of the tile: its list's k-th entry (the threshold) and fill count
     __shared__ int s_thr_i[CT];
     __shared__ int s_cnt[CT];
-    cosine_tile_walk<VEC, true>(p, p.k, s_thr_v, s_thr_i, s_cnt);
+    cosine_tile_walk<VEC, WALK_TOPK>(p, p.k, s_thr_v, s_thr_i, s_cnt);
 }
 
 // one wave per query: the result list is built in LDS from the previous outputs (accumulate) and the splits' lists, split by split.
@@ -717,7 +793,7 @@ int pixel_splits(int Nq, int Nb) {
 }
 
 // ================================================================================================================================
-// host side of the two cosine searches
+// host side of the cosine searches and the rank count
 // ================================================================================================================================
 // the workspace: 1 / |row| of both sides (double), then the splits' partial results, `per_query` (value, row) pairs per
 // (split, query): 1 for the arg-max, k for the lists.  Byte offsets of 16-byte aligned pieces.
@@ -727,6 +803,21 @@ CosineWs cosine_workspace(int Nq, int Nb, int per_query) {
     const size_t nq = align16((size_t)Nq * 8), nb = align16((size_t)Nb * 8);
     const size_t part = align16((size_t)cosine_splits(Nq, Nb) * Nq * per_query * 4);
     return {0, nq, nq + nb, nq + nb + part, nq + nb + 2 * part};
+}
+
+// what the three entries share once their arguments are accepted: the walk's arguments, and the two norm passes enqueued
+void cosine_begin(CosDev& p, const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, float eps, const int32_t* q_group,
+                  const int32_t* base_group, void* workspace, const CosineWs& w, hipStream_t st) {
+    char* ws = (char*)workspace;
+    double* invq = (double*)(ws + w.invq);
+    double* invb = (double*)(ws + w.invb);
+    p.q = q; p.b = base; p.ldq = ldq; p.ldb = ldb; p.Nq = Nq; p.Nb = Nb; p.D = D;
+    p.invq = invq; p.invb = invb; p.qg = q_group; p.bg = base_group;
+    p.pval = (float*)(ws + w.pval); p.pidx = (int32_t*)(ws + w.pidx);
+    p.nbt = cvcl_div_up(Nb, CT);
+    p.vec = (((uintptr_t)q | (uintptr_t)base) & 15) == 0 && ldq % 4 == 0 && ldb % 4 == 0 && D % 4 == 0;
+    nn_inv_norm_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(q, ldq, Nq, D, eps, invq);
+    nn_inv_norm_kernel<<<cvcl_div_up(Nb, 4), 256, 0, st>>>(base, ldb, Nb, D, eps, invb);
 }
 
 // cvcl_nn_cosine (topk false; k is not read) and cvcl_knn_cosine (topk true) under the entry's own name and output names
@@ -750,19 +841,11 @@ int cosine_search(const char* name, bool topk, const float* q, int ldq, const fl
     CVCL_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace is not 16-byte aligned", name);
 
     const int splits = cosine_splits(Nq, Nb);
-    char* ws = (char*)workspace;
-    double* invq = (double*)(ws + w.invq);
-    double* invb = (double*)(ws + w.invb);
-    KnnDev p;
-    p.q = q; p.b = base; p.ldq = ldq; p.ldb = ldb; p.Nq = Nq; p.Nb = Nb; p.D = D; p.k = k;
-    p.invq = invq; p.invb = invb; p.qg = q_group; p.bg = base_group;
-    p.pval = (float*)(ws + w.pval); p.pidx = (int32_t*)(ws + w.pidx);
-    p.nbt = cvcl_div_up(Nb, CT);
-    p.vec = (((uintptr_t)q | (uintptr_t)base) & 15) == 0 && ldq % 4 == 0 && ldb % 4 == 0 && D % 4 == 0;
     hipStream_t st = (hipStream_t)stream;
     CvclProfScope prof(stream, CVCL_K_HEAD);
-    nn_inv_norm_kernel<<<cvcl_div_up(Nq, 4), 256, 0, st>>>(q, ldq, Nq, D, eps, invq);
-    nn_inv_norm_kernel<<<cvcl_div_up(Nb, 4), 256, 0, st>>>(base, ldb, Nb, D, eps, invb);
+    KnnDev p;
+    p.k = k;
+    cosine_begin(p, q, ldq, base, ldb, Nq, Nb, D, eps, q_group, base_group, workspace, w, st);
     const dim3 grid(cvcl_div_up(Nq, CT), splits);
     if (topk) {
         if (p.vec) knn_cosine_kernel<true><<<grid, 256, 0, st>>>(p);
@@ -803,6 +886,46 @@ extern "C" int cvcl_knn_cosine(const float* q, int ldq, const float* base, int l
                                int64_t* top_idx, void* workspace, size_t workspace_bytes, void* stream) {
     return cosine_search("cvcl_knn_cosine", true, q, ldq, base, ldb, Nq, Nb, D, k, eps, q_group, base_group, idx_offset, accumulate,
                          top_cos, top_idx, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t cvcl_rank_cosine_workspace_bytes(int Nq, int Nb, int D) {
+    if (Nq < 1 || Nb < 1 || D < 1) return 0;
+    return cosine_workspace(Nq, Nb, 1).bytes;
+}
+
+// cvcl_rank_cosine: the arg-max search's workspace layout (its pval piece stays unused), the keys in the group slots
+extern "C" int cvcl_rank_cosine(const float* q, int ldq, const float* base, int ldb, int Nq, int Nb, int D, float eps,
+                                const int32_t* q_key, const int32_t* base_key, const float* thr_cos, const int64_t* thr_idx,
+                                int64_t idx_offset, int accumulate, int64_t* rank, void* workspace, size_t workspace_bytes, void* stream) {
+    CVCL_CHECK_ARG(q && base, "cvcl_rank_cosine: null pointer (q / base)");
+    CVCL_CHECK_ARG(q_key && base_key, "cvcl_rank_cosine: null pointer (q_key / base_key)");
+    CVCL_CHECK_ARG(thr_cos && thr_idx, "cvcl_rank_cosine: null pointer (thr_cos / thr_idx)");
+    CVCL_CHECK_ARG(rank, "cvcl_rank_cosine: null pointer (rank)");
+    CVCL_CHECK_ARG(Nq >= 1, "cvcl_rank_cosine: Nq %d < 1", Nq);
+    CVCL_CHECK_ARG(Nb >= 1, "cvcl_rank_cosine: Nb %d < 1", Nb);
+    CVCL_CHECK_ARG(D >= 1, "cvcl_rank_cosine: D %d < 1", D);
+    CVCL_CHECK_ARG(ldq >= D, "cvcl_rank_cosine: ldq %d < D %d", ldq, D);
+    CVCL_CHECK_ARG(ldb >= D, "cvcl_rank_cosine: ldb %d < D %d", ldb, D);
+    CVCL_CHECK_ARG(eps >= 0.f, "cvcl_rank_cosine: eps %g < 0", (double)eps);
+    CVCL_CHECK_ARG(idx_offset >= 0, "cvcl_rank_cosine: idx_offset %lld < 0", (long long)idx_offset);
+    CVCL_CHECK_ARG(accumulate == 0 || accumulate == 1, "cvcl_rank_cosine: accumulate %d outside {0, 1}", accumulate);
+    CVCL_CHECK_ARG(workspace, "cvcl_rank_cosine: null pointer (workspace)");
+    const CosineWs w = cosine_workspace(Nq, Nb, 1);
+    CVCL_CHECK_ARG(workspace_bytes >= w.bytes, "cvcl_rank_cosine: workspace_bytes %zu < %zu", workspace_bytes, w.bytes);
+    CVCL_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "cvcl_rank_cosine: workspace is not 16-byte aligned");
+
+    const int splits = cosine_splits(Nq, Nb);
+    hipStream_t st = (hipStream_t)stream;
+    CvclProfScope prof(stream, CVCL_K_HEAD);
+    RankDev p;
+    p.thr_cos = thr_cos; p.thr_idx = thr_idx; p.idx_offset = (long)idx_offset;
+    cosine_begin(p, q, ldq, base, ldb, Nq, Nb, D, eps, q_key, base_key, workspace, w, st);
+    const dim3 grid(cvcl_div_up(Nq, CT), splits);
+    if (p.vec) rank_cosine_kernel<true><<<grid, 256, 0, st>>>(p);
+    else rank_cosine_kernel<false><<<grid, 256, 0, st>>>(p);
+    rank_cosine_merge_kernel<<<cvcl_div_up(Nq, 256), 256, 0, st>>>(p.pidx, splits, Nq, thr_idx, accumulate, rank);
+    CVCL_LAUNCH_CHECK();
+    return CVCL_OK;
 }
 
 extern "C" int cvcl_knn_vote(const float* top_cos, const int64_t* top_idx, int Nq, int k, const int32_t* base_label, int64_t Nb, int C,

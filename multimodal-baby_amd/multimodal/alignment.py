@@ -343,8 +343,9 @@ def parser():
     return ap
 
 
-def build_model(args, device):
-    """the two-tower model: a checkpoint, or the reference's CVCL configuration (embedding text encoder, E = 512) at random weights"""
+def build_model(args, device, normalize_features=False):
+    """the two-tower model: a checkpoint, or the reference's CVCL configuration (embedding text encoder, E = 512) at random weights
+    (``normalize_features``: of the random model; a checkpoint keeps its own)"""
     import argparse
     from .multimodal import TextEncoder, VisionEncoder
     from .multimodal_data_module import read_vocab
@@ -356,9 +357,9 @@ def build_model(args, device):
         cfg = argparse.Namespace(
             embedding_type="flat", embedding_dim=512, pretrained_cnn=False, cnn_model="resnext50_32x4d", cnn_dino=False, vit_dino=False,
             finetune_cnn=False, text_encoder="embedding", captioning=False, attention=False, attention_gate=False, crange=1,
-            dropout_i=0.5, dropout_o=0.0, pos_embed_type="no_pos_embed", normalize_features=False, sim="max", temperature=0.07,
-            fix_temperature=True, tie=True, bias=True, lr=1e-4, weight_decay=0.1, lambda_mm=1.0, lambda_lm=0.0, lambda_ar=0.0,
-            optimize_unused=True, lr_scheduler=True, optimizer=torch.optim.AdamW)
+            dropout_i=0.5, dropout_o=0.0, pos_embed_type="no_pos_embed", normalize_features=bool(normalize_features), sim="max",
+            temperature=0.07, fix_temperature=True, tie=True, bias=True, lr=1e-4, weight_decay=0.1, lambda_mm=1.0, lambda_lm=0.0,
+            lambda_ar=0.0, optimize_unused=True, lr_scheduler=True, optimizer=torch.optim.AdamW)
         lit = MultiModalLitModel(VisionEncoder(cfg), TextEncoder(read_vocab(), 2048, cfg), cfg)
     else:
         raise SystemExit("--checkpoint PATH or --random_init")
