@@ -1178,6 +1178,38 @@ int cvcl_attn_overlay(const float* maps, int M, int h, int w, const float* image
                       float vmax, const int64_t* dst_offset, int64_t row_pitch, int64_t out_elems, float* out_f32, uint8_t* out_u8,
                       float* out_map, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Map faithfulness (csrc/faithfulness.hip, ABI v7 additive): the pieces of the deletion / insertion curves of an attention map
+ * (Petsiuk et al., RISE, 2018; multimodal/map_faithfulness.py; DESIGN.md "Map faithfulness").  Everything is validated before anything
+ * is enqueued (CVCL_EINVAL, cvcl_last_error names the argument, nothing is written); the kernels run on the caller's stream only and
+ * use no global atomics: two calls give the same bits.  CVCL_K_OTHER.
+ * cvcl_map_ranks: maps [M, HW] f32 -> ranks [M, HW] int32: ranks[m][p] = the position of pixel p when map m's pixels are ordered by
+ *   value descending.  Values compare as floats (-0.0 == +0.0; subnormals order by value, nothing is flushed), ties go to the lower
+ *   flat index: every map's ranks are a permutation of 0 .. HW - 1.  NaN is not supported (the ranks stay a permutation, in an
+ *   unspecified order).  Limits: 1 <= HW <= 65536, M >= 1.  scratch: 16-byte aligned, >= cvcl_map_ranks_scratch_bytes(M, HW) bytes
+ *   (0 = refused sizes): two (key, index) buffers of 6 bytes per pixel per map.  One workgroup per map.
+ * cvcl_map_perturb: work item i writes out[i] [C, H, W] from m = item_map[i], n = image_of_map[m] (NULL: n = m, needs M <= N),
+ *   k = item_count[i] in [0, H W]:  item_mode[i] == 0 (deletion): pixel p is baseline[n] where ranks[m][p] < k, else images[n];
+ *   item_mode[i] == 1 (insertion): images[n] where ranks[m][p] < k, else baseline[n].  A select: the output has the inputs' bits.
+ *   images, baseline [N, C, H, W] f32 (baseline NULL: zeros), ranks [M, H W] int32 and out [n_items, C, H, W] are on the device;
+ *   image_of_map [M], item_map, item_count, item_mode [n_items] are HOST arrays: every entry is checked against N, M, H W and {0, 1}
+ *   here, and the items travel to the kernel in its argument block, 256 per launch.  H W <= 65536; any H, W (rows need no alignment).
+ * cvcl_gaussian_blur_f32: y = the separable k-tap filter w of x [planes, H, W], along the rows (x axis) first, then along the columns,
+ *   with reflect padding that does not repeat the edge (torch's "reflect"), taps added in index order in fp32.  w: a HOST array of k
+ *   floats; k odd, k <= 129, k / 2 < min(H, W).  scratch: planes H W floats on the device; x, y and scratch are distinct.
+ * cvcl_pair_dot: out[r] = sum_e rows[r][e] targets[target_of_row[r]][e], rows [R, E], targets [M, E] f32, target_of_row [R] int32 on
+ *   the device; a row whose index is outside [0, M) reads nothing and gets NaN.  One wave per row: lane l adds e = l, l + 64, ...
+ * cvcl_curve_auc: auc[k][m] = sum_{s < S} (x[s + 1] - x[s]) (y[k][s][m] + y[k][s + 1][m]) / 2, y [K, S + 1, M], x [S + 1], auc [K, M]
+ *   f32 on the device; S >= 1.                                                                                                     */
+size_t cvcl_map_ranks_scratch_bytes(int M, int HW);
+int cvcl_map_ranks(const float* maps, int32_t* ranks, int M, int HW, void* scratch, size_t scratch_bytes, void* stream);
+int cvcl_map_perturb(const float* images, const float* baseline, const int32_t* ranks, const int32_t* image_of_map,
+                     const int32_t* item_map, const int32_t* item_count, const int32_t* item_mode, int n_items, int N, int M, int C,
+                     int H, int W, float* out, void* stream);
+int cvcl_gaussian_blur_f32(const float* x, float* y, const float* w, int k, int planes, int H, int W, void* scratch, void* stream);
+int cvcl_pair_dot(const float* rows, const float* targets, const int32_t* target_of_row, float* out, int R, int M, int E, void* stream);
+int cvcl_curve_auc(const float* y, const float* x, float* auc, int K, int S, int M, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
