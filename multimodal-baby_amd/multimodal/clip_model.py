@@ -25,6 +25,7 @@ from torch import nn
 from . import _hip as H
 from . import ops
 from .multimodal_data_module import CLIP_MEAN, CLIP_STD      # the frame statistics of CLIP's transform (noqa: F401, re-exported)
+from .trunk_runtime import TrunkRuntime, fingerprint, strip
 from .vit_hip import _Trunk, _ln
 
 MAX_TOKENS = 288                       # cvcl_attention's bf16 MFMA kernel (ViT-L/14 at 224: 257; ViT-L/14@336 has 577: refused)
@@ -36,8 +37,13 @@ def _f(p):
     return p.detach().float().contiguous()
 
 
-def _version_key(module, *extra):
-    return extra + tuple((p.data_ptr(), p._version) for p in module.parameters())
+def _getstate(self):
+    return strip(self.__dict__, "runtime")            # (__dict__: the instance's own state is what pickles; the runtime never is)
+
+
+def _setstate(self, d):
+    nn.Module.__setstate__(self, strip(d, "runtime"))     # (a pickle of an earlier version: its ``_cache`` is dropped)
+    self.runtime = TrunkRuntime()
 
 
 class _Held(nn.Module):
@@ -96,14 +102,15 @@ class VisionTransformer(_Held):
         self.ln_post = nn.LayerNorm(width)
         self.proj = nn.Parameter(torch.empty(width, output_dim))
         self.compute_dtype = torch.float32
-        self._cache = {}
+        self.runtime = TrunkRuntime()
+
+    __getstate__, __setstate__ = _getstate, _setstate
 
     def packed_weights(self, dt, device):
         """vit_hip._Trunk's packed-weight dict for this tower (cast once per weight version)."""
-        key = _version_key(self, str(dt), str(device))
-        hit = self._cache.get("w")
-        if hit is not None and hit[0] == key:
-            return hit[1]
+        return self.runtime.cache.get("w", fingerprint(self.parameters(), str(dt), str(device)), lambda: self._pack(dt, device))
+
+    def _pack(self, dt, device):
         D, p = self.embed_dim, self.patch_size
         K = 3 * p * p
         Kpad = (K + 7) // 8 * 8
@@ -116,7 +123,6 @@ class VisionTransformer(_Held):
              "proj": _f(self.proj.t())}                     # [E, D]: cvcl_gemm's W layout
         if torch.device(device).type == "cuda":
             torch.cuda.current_stream(device).synchronize()
-        self._cache["w"] = (key, w)
         return w
 
 
@@ -139,8 +145,10 @@ class CLIP(nn.Module):
         self.ln_final = nn.LayerNorm(transformer_width)
         self.text_projection = nn.Parameter(torch.empty(transformer_width, embed_dim))
         self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
-        self._cache = {}
+        self.runtime = TrunkRuntime()
         self.initialize_parameters()
+
+    __getstate__, __setstate__ = _getstate, _setstate
 
     def initialize_parameters(self):
         """The ``clip`` package's random initialisation (model.py: initialize_parameters)."""
@@ -191,14 +199,10 @@ class CLIP(nn.Module):
 
     def _text_weights(self, device):
         mods = nn.ModuleList([self.transformer, self.token_embedding, self.ln_final])
-        key = _version_key(mods, str(device)) + tuple((p.data_ptr(), p._version) for p in (self.positional_embedding, self.text_projection))
-        hit = self._cache.get("t")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        w = {"table": _f(self.token_embedding.weight), "pos": _f(self.positional_embedding), "blocks": self.transformer.packed_blocks(_F),
-             "nw": _f(self.ln_final.weight), "nb": _f(self.ln_final.bias), "neps": self.ln_final.eps, "proj": _f(self.text_projection.t())}
-        self._cache["t"] = (key, w)
-        return w
+        key = fingerprint([*mods.parameters(), self.positional_embedding, self.text_projection], str(device))
+        return self.runtime.cache.get("t", key, lambda: {
+            "table": _f(self.token_embedding.weight), "pos": _f(self.positional_embedding), "blocks": self.transformer.packed_blocks(_F),
+            "nw": _f(self.ln_final.weight), "nb": _f(self.ln_final.bias), "neps": self.ln_final.eps, "proj": _f(self.text_projection.t())})
 
     @torch.no_grad()
     def encode_text(self, text):

@@ -20,6 +20,7 @@ from . import ops, parallel, resnext, text_train
 from ._hip import CvclError
 from .attention_maps import Hook
 from .multimodal_data_module import EOS_TOKEN_ID, MAX_LEN_UTTERANCE, PAD_TOKEN_ID, SOS_TOKEN_ID
+from .trunk_runtime import fingerprint, runtime_of, strip
 from .utils import load_model
 
 TEXT_ENCODER = "embedding"
@@ -62,6 +63,19 @@ def set_parameter_requires_grad(model, feature_extracting=True):
             param.requires_grad = False
 
 
+class _EvalGraphs:
+    """VisionEncoder's HIP-graph state: the switch (None = $CVCL_EVAL_GRAPH decides), the captured entries per input shape and the
+    cached parameter list their fingerprints are taken over."""
+
+    def __init__(self):
+        self.on, self.entries, self.params = None, {}, None
+
+    def drop(self, graphs=True):
+        if graphs:
+            self.entries = {}
+        self.params = None
+
+
 class VisionEncoder(nn.Module):
     """ResNeXt-50 / DINO ViT image encoder + linear projection to the embedding space."""
 
@@ -75,6 +89,7 @@ class VisionEncoder(nn.Module):
         self.cnn_dino = self.args.get("cnn_dino", CNN_DINO)
         self.vit_dino = self.args.get("vit_dino", VIT_DINO)
         self.finetune_cnn = self.args.get("finetune_cnn")
+        self._eval_graphs = _EvalGraphs()                     # never pickled
         self.model = self._load_pretrained_cnn()
 
     @staticmethod
@@ -117,29 +132,36 @@ class VisionEncoder(nn.Module):
     # through ``_load_from_state_dict`` and never calls the child's ``load_state_dict``), an optimizer step.  ``train()`` and the
     # two load paths also drop the graphs outright.
     def enable_hip_graphs(self, on: bool = True):
-        self.__dict__["_hip_graphs"] = bool(on)
-        self.__dict__["_graphs"] = {}
+        self._eval_graphs.on, self._eval_graphs.entries = bool(on), {}
         return self
 
+    @property
+    def _graphs(self):
+        """The captured entries, keyed by (input shape, device, compute dtype, trunk arithmetic)."""
+        return self._eval_graphs.entries
+
+    def _trunk_runtime(self):
+        return runtime_of(getattr(self.model, "_resnet", self.model))     # (spatial embeddings: the Sequential wraps the ResNet that owns it)
+
     def _graph_eligible(self, x):
-        on = self.__dict__.get("_hip_graphs")
+        on = self._eval_graphs.on
         if on is None:
             on = os.environ.get("CVCL_EVAL_GRAPH") == "1"
-        trunk = getattr(self.model, "_resnet", self.model)          # (spatial embeddings: the Sequential wraps the ResNet that owns the caches)
         return bool(on and not self.training and not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
-                    and trunk.__dict__.get("_trunk_stream") is None and not torch.cuda.is_current_stream_capturing())
+                    and self._trunk_runtime().stream is None and not torch.cuda.is_current_stream_capturing())
 
     def _graph_forward(self, x):
-        graphs = self.__dict__.setdefault("_graphs", {})
+        state = self._eval_graphs
+        graphs = state.entries
         key = (tuple(x.shape), str(x.device), getattr(self.model, "compute_dtype", None), getattr(self.model, "trunk_arithmetic", None))
         # (the parameter LIST is cached: the module-tree walk of ~160 parameters cost more host time per call than reading their
         # pointers and versions.  It is valid while no nn.Module anywhere registered a parameter or a sub-module since it was
         # taken -- ``model.fc = nn.Linear(...)``, ``load_state_dict(assign=True)``, ``register_parameter`` all pass torch's
         # global registration hooks, which advance _REGISTRATIONS; in-place edits and ``.data`` swaps show in the fingerprint)
-        plist = self.__dict__.get("_graph_params")
+        plist = state.params
         if plist is None or plist[0] != _REGISTRATIONS[0]:
-            plist = self.__dict__["_graph_params"] = (_REGISTRATIONS[0], list(self.model.parameters()))
-        fp = tuple((p.data_ptr(), p._version) for p in plist[1])
+            plist = state.params = (_REGISTRATIONS[0], list(self.model.parameters()))
+        fp = fingerprint(plist[1])
         entry = graphs.get(key)
         if entry is not None and entry[5] != fp:              # weights changed since the capture: the packed copies are stale
             entry = None
@@ -157,40 +179,34 @@ class VisionEncoder(nn.Module):
             with torch.cuda.graph(graph):
                 feats, fmap = self._eager_forward(static_x)
             # (the trunk's cached workspaces are referenced by the graph: keep them alive whatever other shapes run later)
-            trunk = getattr(self.model, "_resnet", self.model)
-            keep = list(getattr(trunk, "_ws_cache", {}).values()) + [dict(getattr(trunk, "_pack_cache", None) or {}), dict(getattr(trunk, "_cache", None) or {})]
-            entry = graphs[key] = (graph, static_x, feats, fmap, keep, fp)
+            entry = graphs[key] = (graph, static_x, feats, fmap, self._trunk_runtime().keep_alive(), fp)
         graph, static_x, feats, fmap, _keep, _fp = entry
         static_x.copy_(x, non_blocking=True)
         graph.replay()
         return feats.clone(), (fmap.clone() if fmap is not None else None)
 
     def train(self, mode: bool = True):
-        if mode and self.__dict__.get("_graphs"):
-            self.__dict__["_graphs"] = {}
-        self.__dict__["_graph_params"] = None
+        self._eval_graphs.drop(graphs=mode)
         return super().train(mode)
 
     def load_state_dict(self, *a, **k):
-        self.__dict__["_graphs"] = {}
-        self.__dict__["_graph_params"] = None
+        self._eval_graphs.drop()
         return super().load_state_dict(*a, **k)
 
     def _load_from_state_dict(self, *a, **k):                 # a parent's load_state_dict reaches this module here, not above
-        self.__dict__["_graphs"] = {}
-        self.__dict__["_graph_params"] = None
+        self._eval_graphs.drop()
         return super()._load_from_state_dict(*a, **k)
 
     def _apply(self, fn, *a, **k):                            # .to() / .cuda() / .float(): new storage, maybe new Parameter objects
-        self.__dict__["_graphs"] = {}
-        self.__dict__["_graph_params"] = None
+        self._eval_graphs.drop()
         return super()._apply(fn, *a, **k)
 
     def __getstate__(self):                                   # (checkpoints pickle whole encoders: graphs are never part of them)
-        d = dict(self.__dict__)
-        d.pop("_graphs", None)
-        d.pop("_graph_params", None)
-        return d
+        return strip(self.__dict__, "_eval_graphs")           # (__dict__: the instance's own state is what pickles)
+
+    def __setstate__(self, d):                                # (also pickles of the reference's class and of earlier versions of this one)
+        super().__setstate__(strip(d, "_eval_graphs"))
+        self._eval_graphs = _EvalGraphs()
 
     def _forward_unbatched(self, x):
         """reference :106-114: one image at a time through self.model (what tests/test_batching.py compares with)."""
@@ -401,7 +417,7 @@ class TextEncoder(nn.Module):
             layer = self.transformer_encoder.layers[0]
             if self.training or torch.is_grad_enabled():
                 ret, raw_output = text_train.transformer_text_train(self.embedding.weight, layer, pos, x, x_len, self.training,
-                                                                    split=bool(self.__dict__.get("fp32_split", False)))
+                                                                    split=bool(getattr(self, "fp32_split", False)))
             else:
                 ret, raw_output = ops.transformer_text(self.embedding.weight, layer, pos, x, x_len)
         else:

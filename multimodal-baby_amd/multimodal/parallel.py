@@ -35,6 +35,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .trunk_runtime import runtime_of
+
 
 # collectives issued by this module since import: {"all_gather": n, "all_reduce": n, "broadcast": n} -- read by bench.py's multi-rank
 # line (collectives per step) and by the tests (one feature all-gather per step)
@@ -387,10 +389,11 @@ class OverlappedUpdate:
         self.pending = False
         trunk = getattr(vision_encoder, "model", None)
         head_names = ("fc.", "head.")
-        self.can_defer = trunk is not None and hasattr(trunk, "_pre_head_callback") and not any(
+        rt = runtime_of(trunk)              # (a trunk whose forward runs the callback between its frozen part and its head)
+        self.can_defer = rt is not None and rt.defers and not any(
             p.requires_grad for n, p in trunk.named_parameters() if not n.startswith(head_names))
         if self.can_defer:
-            trunk._pre_head_callback = self.flush
+            rt.pre_head_callback = self.flush
 
     def flush(self):
         if self.pending:

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import _hip as H
 from . import ops
+from .trunk_runtime import TrunkRuntime, fingerprint, strip
 
 LAYERS = (3, 4, 6, 3)
 GROUPS, WIDTH_PER_GROUP = 32, 4
@@ -54,6 +55,108 @@ class _Stage(nn.Sequential):
         return feature_map
 
 
+class StorageCentres:
+    """Centred storage of the raw convolution outputs (include/cvcl_hip.h "Centred storage"): the centres a ResNet holds.
+
+    A raw conv output y whose per-channel batch mean is large next to its spread loses precision when it is rounded to bf16
+    before BatchNorm subtracts the mean.  BatchNorm(y - c) == BatchNorm(y), so the kernels store round(y - c) with c close to
+    the batch mean.  The frozen trunk takes c from ONE calibration pass -- the batch means of the first train-mode batch it
+    sees after its weights (re)appeared -- and keeps it: a forward pass stays a pure function of (input, weights, BatchNorm
+    buffers, centres), whatever the stream schedule.  c only has to be within ~sigma of the batch mean, which a stationary
+    input distribution guarantees; ``reset()`` drops it (e.g. after a change of data distribution).
+    Eval mode centres on the running means (the library's default for centres == NULL).  The fine-tuning twin
+    (trunk_train) tracks instead: its weights move every step, so each layer's c follows the previous step's batch mean.
+    $CVCL_CENTRED_STORAGE=0 switches the whole mechanism off (plain storage, the round-2 numerics; ResNet.centred_storage).
+
+    The class launches nothing: ``calibrated`` is handed the calibration pass as a callable."""
+
+    def __init__(self):
+        self.frozen = None                  # (weights key, [53, 2048] f32, ready event or None): calibrated, frozen path
+        self.restored = None                # "frozen" centres of a checkpoint, not yet adopted by a pass
+        self.tracked = None                 # [53, 2048] f32 on the device: fine-tuning path
+        self.tracked_restored = None        # "tracking" centres of a checkpoint, not yet adopted
+        self.sync_pending = False
+
+    def reset(self):
+        """Forget the calibrated and the tracked centres.  Data parallel: all ranks call it, and all ranks' next train-mode pass
+        adopts rank 0's new calibration (``request_sync``)."""
+        self.frozen = self.restored = self.tracked = self.tracked_restored = None
+        from . import parallel
+        if parallel.is_distributed():
+            self.request_sync()
+
+    def request_sync(self):
+        """Data parallel: ask the NEXT ``calibrated`` call to take part in one broadcast of rank 0's storage centres, whatever this
+        replica's own state says (hit, restored from a checkpoint, freshly calibrated).  Raised only at rank-synchronous points --
+        ``DataParallelEngine.attach`` and ``reset`` -- so either every rank enters the broadcast or none does: the decision never
+        depends on a rank's local state (a checkpoint resumed on some ranks only, a weight re-allocated on one rank, a rank-local
+        extra forward).  A miss WITHOUT a pending request recalibrates locally and talks to nobody."""
+        self.sync_pending = True
+
+    def export(self):
+        """Checkpoint form (CPU tensors) {"frozen", "tracking"}, or None when there are none yet."""
+        out = {}
+        if self.frozen is not None:
+            if self.frozen[2] is not None:
+                self.frozen[2].synchronize()
+            out["frozen"] = self.frozen[1].detach().cpu()
+        elif self.restored is not None:
+            out["frozen"] = self.restored.detach().cpu()
+        if self.tracked is not None:
+            out["tracking"] = self.tracked.detach().cpu()
+        return out or None
+
+    def import_(self, state):
+        """Adopt what ``export`` saved: the next train-mode pass uses it instead of calibrating (whatever the weights' new storage
+        addresses are), so a resumed bf16 run evaluates the same forward function as the run that saved it.  A checkpoint carries
+        rank 0's centres (the ones every replica of a data-parallel run holds after the broadcast at its first step); on resume
+        ``DataParallelEngine.attach`` requests the same broadcast again, so the replicas agree even when only some ranks restored."""
+        self.frozen = self.tracked = None
+        self.restored = state["frozen"].clone() if state.get("frozen") is not None else None
+        self.tracked_restored = state["tracking"].clone() if state.get("tracking") is not None else None
+
+    def tracking(self, device):
+        t = self.tracked
+        if t is None or t.device != device:
+            pend, self.tracked_restored = self.tracked_restored, None
+            t = self.tracked = pend.to(device) if pend is not None else torch.zeros(53, 2048, dtype=torch.float32, device=device)
+        return t
+
+    def calibrated(self, x, key, calibrate):
+        """-> [53, 2048] f32 centres for a train-mode pass over ``x``'s distribution with the weights ``key``: the cached ones, the
+        restored ones (restored wins over calibrating), or ``calibrate()``'s."""
+        from . import parallel
+        sync = self.sync_pending and parallel.is_distributed()
+        hit = self.frozen
+        if hit is not None and hit[0] == key:
+            if hit[2] is not None:
+                torch.cuda.current_stream(x.device).wait_event(hit[2])     # (calibrated on another trunk stream)
+            if not sync:
+                return hit[1]
+            centres = hit[1]
+        else:
+            pend, self.restored = self.restored, None
+            if pend is not None:                                  # restored from a checkpoint: no calibration pass
+                centres = pend.to(device=x.device, dtype=torch.float32).contiguous()
+                if not sync:
+                    self.frozen = (key, centres, None)
+                    return centres
+            else:
+                centres = calibrate()
+        if sync:
+            # data parallel: every replica must evaluate the SAME bf16 forward function, so rank 0's centres are adopted by all (a
+            # centre only has to be within ~sigma of a rank's batch mean; the ranks see shards of one distribution).  Every rank is
+            # here: the request was raised at a rank-synchronous point (request_sync), not by this rank's cache state
+            self.sync_pending = False
+            centres = parallel.broadcast_from_rank0(centres.clone() if hit is not None and centres is hit[1] else centres)
+        ready = None
+        if x.is_cuda:
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(x.device))
+        self.frozen = (key, centres, ready)
+        return centres
+
+
 class ResNet(nn.Module):
     def __init__(self, num_classes: int = 1000):
         super().__init__()
@@ -84,10 +187,8 @@ class ResNet(nn.Module):
         # products of the trunk's convolutions when compute_dtype is fp32: "exact" (fp32 MFMA, the parity mode) or "split"
         # (split-bf16 parts on the bf16 MFMA, CVCL_F32X3: the "32-split" precision; storage stays fp32)
         self.trunk_arithmetic = "exact"
-        self._pack_cache = {}
-        self._ws_cache = {}
-        self._pre_head_callback = None                  # parallel.OverlappedUpdate: runs between the trunk and fc
-        self._centres = None                            # storage centres of the 53 raw conv outputs (see storage_centres)
+        self.runtime = TrunkRuntime(defers=True)       # never pickled: packed weights, workspaces, trunk stream, callback
+        self.centres = StorageCentres()                # never pickled either (checkpoints carry export_centres())
 
     # ---- (conv, bn) pairs in torchvision state_dict order -----------------------------------
     def conv_bn_pairs(self):
@@ -104,10 +205,10 @@ class ResNet(nn.Module):
     def _packed_layers(self, dt: int, device):
         """Re-lay-out conv weights for the kernels (once per weight version) and build the C array."""
         pairs = self.conv_bn_pairs()
-        key = (dt, str(device)) + tuple((c.weight.data_ptr(), c.weight._version, b.running_mean.data_ptr()) for c, b, _ in pairs)
-        hit = self._pack_cache.get("k")
-        if hit is not None and hit[0] == key:
-            return hit[1]
+        key = fingerprint([c.weight for c, _, _ in pairs], dt, str(device), *(b.running_mean.data_ptr() for _, b, _ in pairs))
+        return self.runtime.cache.get("pack", key, lambda: self._pack_layers(pairs, dt, device))
+
+    def _pack_layers(self, pairs, dt, device):
         lib = H.lib()
         arr = (H.ConvBnParams * len(pairs))()
         keep = []
@@ -127,127 +228,31 @@ class ResNet(nn.Module):
             arr[i].num_batches_tracked = H.ptr(bn.num_batches_tracked, torch.int64)
         if device.type == "cuda":
             torch.cuda.current_stream(device).synchronize()   # packed once, then read by every stream that runs the trunk
-        self._pack_cache["k"] = (key, (arr, keep))
         return arr, keep
 
-    # ---- centred storage of the raw convolution outputs (include/cvcl_hip.h "Centred storage") ------------------------
-    # A raw conv output y whose per-channel batch mean is large next to its spread loses precision when it is rounded to bf16
-    # before BatchNorm subtracts the mean.  BatchNorm(y - c) == BatchNorm(y), so the kernels store round(y - c) with c close to
-    # the batch mean.  The frozen trunk takes c from ONE calibration pass -- the batch means of the first train-mode batch it
-    # sees after its weights (re)appeared -- and keeps it: a forward pass stays a pure function of (input, weights, BatchNorm
-    # buffers, centres), whatever the stream schedule.  c only has to be within ~sigma of the batch mean, which a stationary
-    # input distribution guarantees; ``recalibrate_centres()`` drops it (e.g. after a change of data distribution).
-    # Eval mode centres on the running means (the library's default for centres == NULL).  The fine-tuning twin
-    # (trunk_train) tracks instead: its weights move every step, so each layer's c follows the previous step's batch mean.
-    # $CVCL_CENTRED_STORAGE=0 switches the whole mechanism off (plain storage, the round-2 numerics).
+    # ---- centred storage: StorageCentres (above) under the names the callers know ------------------------------------------
     def recalibrate_centres(self):
-        """Forget the calibrated (frozen path) and the tracked (fine-tuning path) centres: the next train-mode pass starts over.
-        Data parallel: a COLLECTIVE call, like every other state change of a replicated model -- all ranks call it, and all ranks'
-        next train-mode pass adopts rank 0's new calibration (``request_centre_sync``)."""
-        self.__dict__["_centres"] = None
-        self.__dict__["_track_centres"] = None
-        self.__dict__["_centres_restored"] = None
-        self.__dict__["_track_restored"] = None
-        from . import parallel
-        if parallel.is_distributed():
-            self.request_centre_sync()
+        self.centres.reset()                             # (data parallel: a collective call)
 
     def request_centre_sync(self):
-        """Data parallel: ask this replica's NEXT train-mode pass to take part in one broadcast of rank 0's storage centres, whatever
-        its own cache says (hit, restored from a checkpoint, freshly calibrated).  Raised only at rank-synchronous points --
-        ``DataParallelEngine.attach`` and ``recalibrate_centres`` -- so either every rank enters the broadcast or none does: the
-        decision never depends on a rank's local cache state (a checkpoint resumed on some ranks only, a weight re-allocated on one
-        rank, a rank-local extra forward).  A cache miss WITHOUT a pending request recalibrates locally and talks to nobody."""
-        self.__dict__["_centre_sync_pending"] = True
+        self.centres.request_sync()
 
     def export_centres(self):
-        """Checkpoint form of the calibrated / tracked centres (CPU tensors), or None when there are none yet."""
-        out = {}
-        hit = self.__dict__.get("_centres")
-        if hit is not None:
-            if hit[2] is not None:
-                hit[2].synchronize()
-            out["frozen"] = hit[1].detach().cpu()
-        t = self.__dict__.get("_track_centres")
-        if t is not None:
-            out["tracking"] = t.detach().cpu()
-        pend = self.__dict__.get("_centres_restored")
-        if pend is not None and "frozen" not in out:
-            out["frozen"] = pend.detach().cpu()
-        return out or None
+        return self.centres.export()
 
     def import_centres(self, state):
-        """Adopt centres saved by ``export_centres``: the next train-mode pass uses them instead of calibrating (whatever the
-        weights' new storage addresses are), so a resumed bf16 run evaluates the same forward function as the run that saved it.
-        A checkpoint carries rank 0's centres (the ones every replica of a data-parallel run holds after the broadcast at its first
-        step); on resume ``DataParallelEngine.attach`` requests the same broadcast again, so the replicas agree even when only some
-        ranks restored a checkpoint."""
-        self.__dict__["_centres"] = None
-        self.__dict__["_centres_restored"] = state["frozen"].clone() if state.get("frozen") is not None else None
-        self.__dict__["_track_centres"] = None
-        self.__dict__["_track_restored"] = state["tracking"].clone() if state.get("tracking") is not None else None
+        self.centres.import_(state)
 
     def centred_storage(self) -> bool:
         return os.environ.get("CVCL_CENTRED_STORAGE", "1") != "0" and self.compute_dtype == torch.bfloat16
 
     def tracking_centres(self, device):
         """[53, 2048] f32 centres of the fine-tuning path, updated in place by every BatchNorm forward (trunk_train)."""
-        if not self.centred_storage():
-            return None
-        t = self.__dict__.get("_track_centres")
-        if t is None or t.device != device:
-            pend = self.__dict__.pop("_track_restored", None)
-            t = pend.to(device) if pend is not None else torch.zeros(53, 2048, dtype=torch.float32, device=device)
-            self.__dict__["_track_centres"] = t
-        return t
-
-    def _calibrated_centres(self, x, dt, arr, ws, nb, key):
-        """-> [53, 2048] f32 centres for a train-mode pass over ``x``'s distribution (calibrating first if need be), or None."""
-        if not self.centred_storage():
-            return None
-        from . import parallel
-        sync = bool(self.__dict__.get("_centre_sync_pending")) and parallel.is_distributed()
-        hit = self.__dict__.get("_centres")
-        if hit is not None and hit[0] == key:
-            if hit[2] is not None:
-                torch.cuda.current_stream(x.device).wait_event(hit[2])     # (calibrated on another trunk stream)
-            if not sync:
-                return hit[1]
-            centres = hit[1]
-        else:
-            pend = self.__dict__.pop("_centres_restored", None)
-            if pend is not None:                                  # restored from a checkpoint: no calibration pass
-                centres = pend.to(device=x.device, dtype=torch.float32).contiguous()
-                if not sync:
-                    self.__dict__["_centres"] = (key, centres, None)
-                    return centres
-            else:
-                lib = H.lib()
-                B, _, Hh, Ww = x.shape
-                moments = torch.empty(lib.cvcl_resnext50_moments_floats(), dtype=torch.float32, device=x.device)
-                fmap = torch.empty(B, Hh // 32, Ww // 32, 2048, dtype=self.compute_dtype, device=x.device)
-                pooled = torch.empty(B, 2048, dtype=torch.float32, device=x.device)
-                # a plain-storage train-mode pass that leaves every layer's batch mean behind and touches no BatchNorm buffer
-                H.check(lib.cvcl_resnext50_fwd_deferred_stats(dt, B, Hh, Ww, H.ptr(x), arr, len(arr), H.ptr(ws), nb, H.ptr(fmap),
-                                                              H.ptr(pooled), BN_EPS, H.ptr(moments), None, H.stream_ptr()),
-                        "cvcl_resnext50_fwd_deferred_stats")
-                centres = moments.view(53, 2, 2048)[:, 0, :].contiguous()
-        if sync:
-            # data parallel: every replica must evaluate the SAME bf16 forward function, so rank 0's centres are adopted by all (a
-            # centre only has to be within ~sigma of a rank's batch mean; the ranks see shards of one distribution).  Every rank is
-            # here: the request was raised at a rank-synchronous point (request_centre_sync), not by this rank's cache state
-            self.__dict__["_centre_sync_pending"] = False
-            centres = parallel.broadcast_from_rank0(centres.clone() if hit is not None and centres is hit[1] else centres)
-        ready = None
-        if x.is_cuda:
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(x.device))
-        self.__dict__["_centres"] = (key, centres, ready)
-        return centres
+        return self.centres.tracking(device) if self.centred_storage() else None
 
     def trunk(self, x: torch.Tensor, defer_wait: bool = False, bn_groups: int | None = None):
         """conv1 .. layer4 + avgpool.  -> (pooled [B,2048] f32, layer4 map as a logical NCHW view).  With a trunk stream and
-        ``defer_wait`` the result is a handle for ``self._trunk_stream.wait`` (the caller's stream has not waited yet).
+        ``defer_wait`` the result is a handle for ``self.runtime.stream.wait`` (the caller's stream has not waited yet).
         ``bn_groups=G`` in train mode: every BatchNorm normalises each consecutive group of G images on that group's own batch
         statistics (``cvcl_resnext50_fwd_grouped``; running statistics untouched) -- each group's outputs are those of a
         train-mode pass over its G images alone.  In eval mode the running statistics serve every image and G changes nothing."""
@@ -261,7 +266,7 @@ class ResNet(nn.Module):
         if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
             raise H.CvclError(f"expected NCHW fp32 images, got {tuple(x.shape)} {x.dtype}")
         x = x.contiguous()
-        ts = self.__dict__.get("_trunk_stream")
+        ts = self.runtime.stream
         if ts is not None and x.is_cuda:                  # frozen trunk on its own stream (H.TrunkStream)
             handle = ts.launch(lambda slot: self._trunk_launch(x, slot), x)
             if defer_wait:
@@ -273,12 +278,12 @@ class ResNet(nn.Module):
     def grouped_bn(self, bn_groups: int):
         """``with model.grouped_bn(G): logits = model(imgs)`` -- forward with ``trunk(x, bn_groups=G)`` (the linear probe's
         trial scoring: each G-image trial normalised on its own batch statistics, as the reference's train-mode model does)."""
-        prev = self.__dict__.get("_bn_groups")
-        self.__dict__["_bn_groups"] = int(bn_groups)
+        rt = self.runtime
+        prev, rt.bn_groups = rt.bn_groups, int(bn_groups)
         try:
             yield self
         finally:
-            self.__dict__["_bn_groups"] = prev
+            rt.bn_groups = prev
 
     def _trunk_grouped(self, x, G):
         dt = self.trunk_dtype()
@@ -296,13 +301,7 @@ class ResNet(nn.Module):
         with torch.no_grad():
             arr, _keep = self._packed_layers(dt, x.device)
             nb = lib.cvcl_resnext50_fwd_grouped_workspace_bytes(dt, B, Hh, Ww, G)
-            wkey = ("grouped", nb, str(x.device))
-            ws = self._ws_cache.get(wkey)
-            if ws is None:
-                for k in [k for k in self._ws_cache if k[0] == "grouped"]:
-                    del self._ws_cache[k]
-                ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
-                self._ws_cache[wkey] = ws
+            ws = self.runtime.workspace(nb, x.device, "grouped")
             fmap = torch.empty(B, Hh // 32, Ww // 32, 2048, dtype=torch.float32, device=x.device)
             pooled = torch.empty(B, 2048, dtype=torch.float32, device=x.device)
             H.check(lib.cvcl_resnext50_fwd_grouped(dt, B, Hh, Ww, G, H.ptr(x), arr, len(arr), H.ptr(ws), nb, H.ptr(fmap), H.ptr(pooled),
@@ -316,13 +315,11 @@ class ResNet(nn.Module):
         ``cvcl_resnext50_apply_moments`` (same values as the one-stream schedule, bit for bit)."""
         if n_streams is None:
             n_streams = 1 if stream is not None else int(os.environ.get("CVCL_TRUNK_STREAMS", "2"))
-        self.__dict__["_trunk_stream"] = H.TrunkStream(device, inputs, stream, n_streams) if inputs else None
-        self.__dict__["_ema_done"] = None
-        return self.__dict__["_trunk_stream"]
+        return self.runtime.set_stream(H.TrunkStream(device, inputs, stream, n_streams) if inputs else None)
 
     def trunk_dtype(self) -> int:
         """The library dtype the trunk forward runs in: compute_dtype's, or CVCL_F32X3 for fp32 storage with split products."""
-        if self.compute_dtype == torch.float32 and self.__dict__.get("trunk_arithmetic", "exact") == "split":
+        if self.compute_dtype == torch.float32 and self.trunk_arithmetic == "split":
             return H.F32X3
         return H.cvcl_dtype(self.compute_dtype)
 
@@ -333,87 +330,67 @@ class ResNet(nn.Module):
         with torch.no_grad():
             arr, _keep = self._packed_layers(dt, x.device)
             nb = lib.cvcl_resnext50_workspace_bytes(dt, B, Hh, Ww)
-            ts = self.__dict__.get("_trunk_stream")
+            rt = self.runtime
+            ts = rt.stream
             piped = slot is not None and ts is not None and ts.n_streams > 1    # passes on two streams: scratch per stream
             sidx = ts.stream_index if piped else None
-            wkey = (nb, str(x.device), sidx)
-            ws = self._ws_cache.get(wkey)
-            if ws is None:
-                for k in [k for k in self._ws_cache if isinstance(k[0], int) and k[:2] != wkey[:2]]:    # other batch shapes' scratch
-                    del self._ws_cache[k]
-                ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-                self._ws_cache[wkey] = ws
-            if slot is None:
-                fmap = torch.empty(B, Hh // 32, Ww // 32, 2048, dtype=self.compute_dtype, device=x.device)
-                pooled = torch.empty(B, 2048, dtype=torch.float32, device=x.device)
-            else:                                         # side-stream mode: a ring of persistent output sets (H.TrunkStream.launch)
-                key = ("out", slot, B, Hh, Ww, self.compute_dtype, str(x.device))
-                if key not in self._ws_cache:
-                    self._ws_cache[key] = (torch.empty(B, Hh // 32, Ww // 32, 2048, dtype=self.compute_dtype, device=x.device),
-                                           torch.empty(B, 2048, dtype=torch.float32, device=x.device))
-                fmap, pooled = self._ws_cache[key]
-            centres = self._calibrated_centres(x, dt, arr, ws, nb, self._pack_cache["k"][0]) if self.training else None
+            ws = rt.workspace(nb, x.device, sidx)
+
+            def outputs():
+                return (torch.empty(B, Hh // 32, Ww // 32, 2048, dtype=self.compute_dtype, device=x.device),
+                        torch.empty(B, 2048, dtype=torch.float32, device=x.device))
+            # (side-stream mode: a ring of persistent output sets, H.TrunkStream.launch)
+            fmap, pooled = outputs() if slot is None else rt.buffer(("out", slot, B, Hh, Ww, self.compute_dtype, str(x.device)), outputs)
+
+            def batch_means():
+                # the calibration pass: plain storage, train mode, leaves every layer's batch mean behind, touches no BatchNorm buffer
+                moments = torch.empty(lib.cvcl_resnext50_moments_floats(), dtype=torch.float32, device=x.device)
+                f, p = outputs()
+                H.check(lib.cvcl_resnext50_fwd_deferred_stats(dt, B, Hh, Ww, H.ptr(x), arr, len(arr), H.ptr(ws), nb, H.ptr(f), H.ptr(p),
+                                                              BN_EPS, H.ptr(moments), None, H.stream_ptr()), "cvcl_resnext50_fwd_deferred_stats")
+                return moments.view(53, 2, 2048)[:, 0, :].contiguous()
+            centred = self.training and self.centred_storage()
+            centres = self.centres.calibrated(x, rt.cache.slots["pack"][0], batch_means) if centred else None
             if piped and self.training:
                 # the pass leaves its batch moments behind; the 53 running-statistics updates run as one launch behind the
                 # previous pass's (other stream), so they are applied in pass order with the one-stream arithmetic
-                mkey = ("moments", sidx, str(x.device))
-                if mkey not in self._ws_cache:
-                    self._ws_cache[mkey] = torch.empty(lib.cvcl_resnext50_moments_floats(), dtype=torch.float32, device=x.device)
-                moments = self._ws_cache[mkey]
+                moments = rt.buffer(("moments", sidx, str(x.device)), lambda: torch.empty(
+                    lib.cvcl_resnext50_moments_floats(), dtype=torch.float32, device=x.device))
                 H.check(lib.cvcl_resnext50_fwd_deferred_stats(dt, B, Hh, Ww, H.ptr(x), arr, len(arr), H.ptr(ws), nb, H.ptr(fmap),
                                                               H.ptr(pooled), BN_EPS, H.ptr(moments), H.ptr(centres), H.stream_ptr()),
                         "cvcl_resnext50_fwd_deferred_stats")
                 cur = torch.cuda.current_stream(x.device)
-                prev = self.__dict__.get("_ema_done")
-                if prev is not None:
-                    cur.wait_event(prev)
+                if rt.ema_done is not None:
+                    cur.wait_event(rt.ema_done)
                 H.check(lib.cvcl_resnext50_apply_moments(arr, len(arr), H.ptr(moments), BN_MOMENTUM, H.stream_ptr()),
                         "cvcl_resnext50_apply_moments")
-                done = torch.cuda.Event()
-                done.record(cur)
-                self.__dict__["_ema_done"] = done
+                rt.ema_done = torch.cuda.Event()
+                rt.ema_done.record(cur)
             else:
-                prev = self.__dict__.get("_ema_done")
-                if prev is not None and x.is_cuda:           # this pass reads / updates the running statistics in place: behind
-                    torch.cuda.current_stream(x.device).wait_event(prev)     # the last deferred update, whatever stream ran it
+                if rt.ema_done is not None and x.is_cuda:    # this pass reads / updates the running statistics in place: behind
+                    torch.cuda.current_stream(x.device).wait_event(rt.ema_done)     # the last deferred update, whatever stream ran it
                 # (eval mode: centres None = the library centres every stored tensor on its running mean)
                 H.check(lib.cvcl_resnext50_fwd(dt, B, Hh, Ww, int(self.training), H.ptr(x), arr, len(arr), H.ptr(ws), nb,
                                                H.ptr(fmap), H.ptr(pooled), BN_MOMENTUM, BN_EPS, H.ptr(centres), H.stream_ptr()),
                         "cvcl_resnext50_fwd")
         return pooled, fmap.permute(0, 3, 1, 2)
 
-    # caches hold ctypes arrays / device buffers: never pickled (save_hyperparameters pickles whole encoder modules)
+    # the runtime holds ctypes arrays / device buffers / streams: never pickled (save_hyperparameters pickles whole encoder modules)
     def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_pack_cache"], d["_ws_cache"] = {}, {}
-        d["_pre_head_callback"] = None
-        d["_trunk_stream"] = None
-        d["_ema_done"] = None
-        d["_centres"] = None
-        d["_track_centres"] = None
-        d["_centres_restored"] = None
-        d["_track_restored"] = None
-        d["_centre_sync_pending"] = False
-        return d
+        return strip(self.__dict__, "runtime", "centres")       # (__dict__: the instance's own state is what pickles)
 
     def __setstate__(self, d):
-        self.__dict__.update(d)
-        self.__dict__.setdefault("compute_dtype", torch.float32)      # objects pickled by torchvision lack these
-        self.__dict__.setdefault("trunk_arithmetic", "exact")
-        self.__dict__.setdefault("_pack_cache", {})
-        self.__dict__.setdefault("_ws_cache", {})
-        self.__dict__.setdefault("_pre_head_callback", None)
-        self.__dict__.setdefault("_trunk_stream", None)
-        self.__dict__.setdefault("_centres", None)
+        # (objects pickled by torchvision lack the two settings; a pickle of an earlier version carries cache keys: dropped)
+        self.__dict__.update({"compute_dtype": torch.float32, "trunk_arithmetic": "exact", **strip(d, "runtime", "centres")})
+        self.runtime, self.centres = TrunkRuntime(defers=True), StorageCentres()
 
     def forward(self, x):
-        ts = self.__dict__.get("_trunk_stream")
-        G = self.__dict__.get("_bn_groups")
+        rt = self.runtime
+        ts, G = rt.stream, rt.bn_groups
         # (the batch path keeps its call exactly: callers may stand a plain function in for ``trunk``)
         out = self.trunk(x, defer_wait=True) if G is None else self.trunk(x, defer_wait=True, bn_groups=G)
-        cb = self.__dict__.get("_pre_head_callback")
-        if cb is not None:
-            cb()                                         # deferred all-reduce wait + optimizer step of the previous step
+        if rt.pre_head_callback is not None:
+            rt.pre_head_callback()                       # deferred all-reduce wait + optimizer step of the previous step
         if ts is not None and isinstance(out, tuple) and len(out) == 2 and isinstance(out[1], torch.cuda.Event):
             out = ts.wait(out)                           # (with a trunk stream the update above overlapped the trunk)
         pooled, fmap = out

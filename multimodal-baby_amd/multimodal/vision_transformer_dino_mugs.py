@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip as H
+from .trunk_runtime import TrunkRuntime, strip
 
 
 def trunc_normal_(tensor, mean=0., std=1., a=-2., b=2.):
@@ -79,8 +80,7 @@ class VisionTransformer(nn.Module):
         trunc_normal_(self.cls_token, std=.02)
         self.apply(self._init_weights)
         self.compute_dtype = torch.float32
-        self._cache = {}
-        self._pre_head_callback = None                  # parallel.OverlappedUpdate: runs between the trunk and the head
+        self.runtime = TrunkRuntime(defers=True)        # never pickled: packed weights, trunk stream, output ring, callback
 
     def _init_weights(self, m):
         if isinstance(m, nn.Linear):
@@ -92,25 +92,19 @@ class VisionTransformer(nn.Module):
             nn.init.constant_(m.weight, 1.0)
 
     def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_cache"] = {}
-        d["_pre_head_callback"] = None
-        d.pop("_trunk_stream", None)          # streams / ring buffers of H.TrunkStream are never pickled
-        d.pop("_trunk_out", None)
-        return d
+        return strip(self.__dict__, "runtime")            # (__dict__: the instance's own state is what pickles)
 
     def __setstate__(self, d):
-        self.__dict__.update(d)
-        self.__dict__.setdefault("compute_dtype", torch.float32)
-        self.__dict__.setdefault("_cache", {})
-        self.__dict__.setdefault("_pre_head_callback", None)
+        d = {"compute_dtype": torch.float32, **strip(d, "runtime")}     # (a pickle of an earlier version: its cache keys are dropped)
         # instances pickled by the reference's own class (hyper_parameters of its Lightning checkpoints) carry only what
         # reference :174-197 sets: recover the two attributes the HIP forward reads from the submodules
-        mods = self.__dict__.get("_modules", {})
-        if "patch_size" not in self.__dict__ and "patch_embed" in mods:
-            self.__dict__["patch_size"] = int(mods["patch_embed"].patch_size)
-        if "num_heads" not in self.__dict__ and len(mods.get("blocks", ())) > 0:
-            self.__dict__["num_heads"] = int(mods["blocks"][0].attn.num_heads)
+        mods = d.get("_modules", {})
+        if "patch_size" not in d and "patch_embed" in mods:
+            d["patch_size"] = int(mods["patch_embed"].patch_size)
+        if "num_heads" not in d and len(mods.get("blocks", ())) > 0:
+            d["num_heads"] = int(mods["blocks"][0].attn.num_heads)
+        self.__dict__.update(d)
+        self.runtime = TrunkRuntime(defers=True)
 
     def enable_trunk_stream(self, device, inputs="caller", stream=None, n_streams=None):
         """Run the frozen ViT on a stream of its own so it overlaps the previous step's trainable tail (see H.TrunkStream)."""

@@ -19,6 +19,7 @@ import os
 import torch
 
 from . import _hip as H
+from .trunk_runtime import fingerprint
 
 
 def _ln_folded(lin, norm):
@@ -40,10 +41,11 @@ def _quant_weight(wf, device):
 
 def _packed(model, dt, device):
     fp8w = bool(getattr(model, "fp8_linears", False))
-    key = (str(dt), str(device), fp8w) + tuple((p.data_ptr(), p._version) for p in model.parameters())
-    hit = model._cache.get("w")
-    if hit is not None and hit[0] == key:
-        return hit[1]
+    key = fingerprint(model.parameters(), str(dt), str(device), fp8w)
+    return model.runtime.cache.get("w", key, lambda: _pack(model, dt, device, fp8w))
+
+
+def _pack(model, dt, device, fp8w):
     D, p = model.embed_dim, model.patch_size
     K = 3 * p * p
     Kpad = (K + 7) // 8 * 8
@@ -90,7 +92,6 @@ def _packed(model, dt, device):
     w["nw"], w["nb"], w["neps"] = model.norm.weight.detach().float().contiguous(), model.norm.bias.detach().float().contiguous(), model.norm.eps
     if torch.device(device).type == "cuda":
         torch.cuda.current_stream(device).synchronize()      # packed once, then read by every stream that runs the trunk
-    model._cache["w"] = (key, w)
     return w
 
 
@@ -150,8 +151,7 @@ def vit_forward(model, x: torch.Tensor) -> torch.Tensor:
     if torch.is_grad_enabled() and any(p.requires_grad for n, p in model.named_parameters() if not n.startswith("head.")):
         from .vit_train import vit_trunk_train         # --finetune_cnn: differentiable twin (saves activations)
         return vit_trunk_train(model, x)
-    ts = model.__dict__.get("_trunk_stream")
-    cb = model.__dict__.get("_pre_head_callback")        # parallel.OverlappedUpdate: the previous step's all-reduce wait + optimizer
+    ts, cb = model.runtime.stream, model.runtime.pre_head_callback      # cb: the previous step's all-reduce wait + optimizer
     if ts is not None and x.is_cuda:          # frozen ViT on its own stream: overlaps the previous step's text encoder / loss /
         x = x.contiguous()                    # backward / optimizer, which stay on the caller's stream (H.TrunkStream)
         handle = ts.launch(lambda slot: _vit_forward(model, x, slot), x)
@@ -169,8 +169,7 @@ def enable_trunk_stream(model, device, inputs="caller", stream=None, n_streams=N
     other (the forward keeps no state between passes: per-pass activations come from the stream's own allocator pool)."""
     if n_streams is None:                     # measured at B = 256 with two: fp8 linears 10.03 -> 9.33 ms/step, bf16 14.47 -> 14.28
         n_streams = 1 if stream is not None else int(os.environ.get("CVCL_VIT_TRUNK_STREAMS", "2"))
-    model.__dict__["_trunk_stream"] = H.TrunkStream(device, inputs, stream, n_streams) if inputs else None
-    return model.__dict__["_trunk_stream"]
+    return model.runtime.set_stream(H.TrunkStream(device, inputs, stream, n_streams) if inputs else None)
 
 
 def _vit_forward(model, x: torch.Tensor, slot) -> torch.Tensor:
@@ -178,7 +177,7 @@ def _vit_forward(model, x: torch.Tensor, slot) -> torch.Tensor:
     # instead of taking turns at whole-chip launches (cvcl_set_gemm_cu_share).  Measured at B = 256, same box, A/B: ViT-B/16 bf16
     # 11.98 -> 11.75 ms per step; NOT for the e4m3 linears (8.4 -> 9.7 ms) and not at patch 14 (65 792 token rows: 15.86 -> 16.41 ms,
     # two passes' activations no longer share the Infinity Cache) -- hence the policy below; $CVCL_VIT_CU_SHARE=0 / 1 forces it
-    ts = model.__dict__.get("_trunk_stream")
+    ts = model.runtime.stream
     share = 0
     # (only while the OTHER stream's pass is really in flight: a validation loop with a host sync per batch, or a host-bound step,
     # runs one pass at a time, and half-chip grids would then leave half the CUs idle)
@@ -222,13 +221,10 @@ class _Trunk:
         s, dev = H.stream_ptr(), x.device
         pos = w["pos"]
         if not self.native:                                      # resampled table (reference :210-230), cached
-            key = ("pos", Hh, Ww, model.pos_embed.data_ptr(), model.pos_embed._version)
-            hit = model._cache.get("pos_interp")
-            if hit is None or hit[0] != key:
+            def resampled():
                 probe = torch.empty(1, T, 1, device="meta")
-                hit = (key, model.interpolate_pos_encoding(probe, Hh, Ww).detach().reshape(-1, D).float().contiguous())
-                model._cache["pos_interp"] = hit
-            pos = hit[1]
+                return model.interpolate_pos_encoding(probe, Hh, Ww).detach().reshape(-1, D).float().contiguous()
+            pos = model.runtime.cache.get("pos_interp", fingerprint([model.pos_embed], Hh, Ww), resampled)
         self.cols = torch.empty(B * (T - 1), w["Kpad"], dtype=dt, device=dev)
         H.check(self.lib.cvcl_im2col_patches(cd, H.ptr(x), H.ptr(self.cols), B, Hh, Ww, p, w["Kpad"], s), "cvcl_im2col_patches")
         tok = H.gemm(self.cols, w["pe_w"], bias=w["pe_b"])
@@ -420,12 +416,8 @@ def _vit_forward_impl(model, x: torch.Tensor, slot) -> torch.Tensor:
         else:                                 # the LayerNorm kernel + plain GEMMs
             for bw in blocks:
                 t.block(bw)
-        if slot is None:
-            cls = torch.empty(B, D, dtype=torch.float32, device=dev)
-        else:                                 # side-stream mode: a ring of persistent outputs (see H.TrunkStream.launch)
-            ring = model.__dict__.setdefault("_trunk_out", {})
-            key = (slot, B, D, str(dev))
-            if key not in ring:
-                ring[key] = torch.empty(B, D, dtype=torch.float32, device=dev)
-            cls = ring[key]
+        def output():
+            return torch.empty(B, D, dtype=torch.float32, device=dev)
+        # side-stream mode: a ring of persistent outputs (see H.TrunkStream.launch)
+        cls = output() if slot is None else model.runtime.buffer(("out", slot, B, D, str(dev)), output)
         return t.features(cls_out=cls)

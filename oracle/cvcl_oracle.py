@@ -482,7 +482,7 @@ def reordered_conv2d(x, w, bias, stride, pad, dil, groups):
 
 def resnext50_batch_means(p: Dict[str, Tensor], x: Tensor, quant: Quant = None) -> Dict[str, Tensor]:
     """conv name -> per-channel batch mean of its raw output in a plain-storage train-mode pass: what the HIP trunk's
-    calibration pass leaves behind as storage centres (multimodal/resnext.py ``_calibrated_centres``)."""
+    calibration pass leaves behind as storage centres (multimodal/resnext.py ``StorageCentres.calibrated``)."""
     taps: Dict[str, Tensor] = {}
     resnext50_forward(p, x, True, quant, taps=taps)
     return {k[:-4]: v.mean(dim=(0, 2, 3)) for k, v in taps.items() if k.endswith(".raw")}

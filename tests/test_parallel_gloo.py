@@ -135,25 +135,28 @@ def _centre_worker(rank, world, port, out):
     dist.init_process_group(backend="gloo")
     net = resnext.ResNet.__new__(resnext.ResNet)                 # the protocol only: no parameters, no device
     torch.nn.Module.__init__(net)
-    net.__dict__.update(compute_dtype=torch.bfloat16, _centres=None, _centres_restored=None)
+    net.compute_dtype, net.centres = torch.bfloat16, resnext.StorageCentres()
     x = torch.zeros(1)
     key = ("weights", 1)
     mine = torch.full((53, 2048), float(rank + 1))
     if rank == 0:
-        net.__dict__["_centres"] = (key, mine.clone(), None)                     # calibrated earlier on this rank
+        net.centres.frozen = (key, mine.clone(), None)                           # calibrated earlier on this rank
     else:
         net.import_centres({"frozen": mine.clone()})                             # this rank resumed a checkpoint
     n0 = parallel.COLLECTIVES["broadcast"]
-    first = net._calibrated_centres(x, None, None, None, 0, key).clone()         # no request pending: nobody talks
+
+    def calibrate():                                                             # (a hit or a restore on every rank: no pass)
+        raise AssertionError("the calibration pass must not run")
+    first = net.centres.calibrated(x, key, calibrate).clone()                    # no request pending: nobody talks
     assert parallel.COLLECTIVES["broadcast"] == n0 and torch.equal(first, mine)
     holder = torch.nn.Module()
     holder.trunk = net
     holder.w = torch.nn.Parameter(torch.zeros(3))
     parallel.DataParallelEngine(torch.device("cpu")).attach(holder)             # the rank-synchronous point
-    assert net.__dict__["_centre_sync_pending"] is True
-    second = net._calibrated_centres(x, None, None, None, 0, key).clone()        # every rank enters ONE broadcast
-    assert parallel.COLLECTIVES["broadcast"] == n0 + 1 and net.__dict__["_centre_sync_pending"] is False
-    third = net._calibrated_centres(x, None, None, None, 0, key).clone()         # cached again: no further collective
+    assert net.centres.sync_pending is True
+    second = net.centres.calibrated(x, key, calibrate).clone()                   # every rank enters ONE broadcast
+    assert parallel.COLLECTIVES["broadcast"] == n0 + 1 and net.centres.sync_pending is False
+    third = net.centres.calibrated(x, key, calibrate).clone()                    # cached again: no further collective
     assert parallel.COLLECTIVES["broadcast"] == n0 + 1
     out.put((rank, first.numpy(), second.numpy(), third.numpy()))                # by value (see _worker)
     dist.barrier()

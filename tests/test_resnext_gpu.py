@@ -367,7 +367,7 @@ def test_deferred_statistics_pass_is_the_in_place_pass(H, dev, dt):
         before = {k: v.clone() for k, v in alt.state_dict().items() if "running" in k or "tracked" in k}
         fmap = torch.empty(B, S // 32, S // 32, 2048, dtype=_t(dt), device=dev)
         pooled = torch.empty(B, 2048, dtype=torch.float32, device=dev)
-        cen = ref.__dict__["_centres"][1] if ref.__dict__.get("_centres") else None      # bf16: the storage centres ref calibrated
+        cen = ref.centres.frozen[1] if ref.centres.frozen else None      # bf16: the storage centres ref calibrated
         assert (cen is not None) == (dt == "bf16")
         H.check(lib.cvcl_resnext50_fwd_deferred_stats(cd, B, S, S, H.ptr(x), arr, len(arr), H.ptr(ws), nb, H.ptr(fmap), H.ptr(pooled),
                                                       BN_EPS, H.ptr(moments), H.ptr(cen), H.stream_ptr()), "deferred")

@@ -262,8 +262,7 @@ def test_frozen_forward_untouched(dev, dt):
         assert torch.equal(before, after) and torch.equal(before, again)
         assert attn.shape == (4, 12, 197, 197) and len(layers) == 2
     finally:
-        m.__dict__.pop("_trunk_stream", None)
-        m.__dict__.pop("_trunk_out", None)
+        m.enable_trunk_stream(dev, inputs=None)
         m.compute_dtype = torch.float32
 
 
